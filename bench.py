@@ -7,9 +7,13 @@ omr_render_batch_device call over a batch of tiles already resident in HBM (K1 t
 K2 quantize/composite).  Multi-GPU: one process per GPU, each rendering its own batch (tiles
 are independent — no collective on the data path; barrier + max-over-ranks timing only).
 
-Also reported: roofline of K2 (HIP events around every K2 launch on its stream), p50 tile
-latency (device-resident and host-fed), and the reference-CPU proxy (oracle/liboracle.so,
-per-request LUT rebuild + render, on the host cores) on a bounded sample.
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps and prints the
+result line; `--dump-outputs DIR` also writes a seeded sample of the last step's ARGB pixels.
+
+With `--full` also reported: roofline of K2 (HIP events around every K2 launch on its stream),
+p50 tile latency (device-resident and host-fed), the JPEG / PNG / host-fed / C3 / C5 sections,
+and the reference-CPU proxy (oracle/liboracle.so, per-request LUT rebuild + render, on the host
+cores) on a bounded sample.
 """
 import argparse
 import json
@@ -45,6 +49,25 @@ def build_batch(torch, batch, unique, device):
     table = torch.tensor([[base + (t * CHANNELS + c) * plane_bytes for c in range(CHANNELS)]
                           for t in range(batch)], dtype=torch.int64, device=device)
     return data, uniq, table
+
+
+DUMP_SEED = 20261019
+DUMP_PIXELS = 1 << 21           # sampled pixels per array: [2^21][4] float32 = 32 MiB
+
+
+def dump_outputs(torch, out_dir, out, name):
+    """--dump-outputs: what the last timed step left in `out` ([batch][1024][1024] packed ARGB), as
+    out_dir/<name>.npy.  The whole batch is 1 GiB, so a fixed sample is written: DUMP_PIXELS pixel
+    positions drawn over the batch (with replacement) from a seeded numpy generator, the same
+    positions for the same batch size, each as its four bytes A, R, G, B in float32 (exact:
+    0..255), shape [DUMP_PIXELS][4]."""
+    import numpy as np
+    flat = out.reshape(-1)
+    idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, flat.numel(), size=DUMP_PIXELS))
+    px = flat[torch.from_numpy(idx).to(flat.device)].cpu().numpy().view(np.uint32)
+    argb = np.stack([(px >> s) & 0xFF for s in (24, 16, 8, 0)], axis=-1).astype(np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, name + ".npy"), argb)
 
 
 def pmc_traffic(batch):
@@ -1482,7 +1505,17 @@ def main():
                     help="untimed device warm-up before the W warm-up steps: the first ~25 K2 launches "
                          "after idle run 0.77 -> 0.60 ms while the GPU clocks ramp (profiles/r02/"
                          "k2_series_*.json); 0 disables")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline steps also run everything else the bench measures: the "
+                         "per-launch K2 roofline pass, tile latencies, the JPEG / PNG / host-fed / C3 / C5 "
+                         "sections and the CPU baselines (each still subject to its --no-* switch); "
+                         "without it only the headline is measured")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step rendered to DIR/<name>.npy "
+                         "(float32; a fixed seeded sample of the batch's ARGB pixels)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args.gpus))
@@ -1581,24 +1614,29 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    # Second pass, same K steps, kernel timing ON: per-launch K2 durations (HIP events around
-    # each K2 launch on its stream) for the roofline.
-    ctx.kernel_timings()
-    ctx.enable_kernel_timing(True)
-    for _ in range(args.steps):
-        step()
-    ctx.synchronize()
-    ctx.enable_kernel_timing(False)
-    k2 = sorted(ms for ms, kind in ctx.kernel_timings() if kind == 2)
+    if args.dump_outputs:
+        dump_outputs(torch, args.dump_outputs, out, "argb" if world == 1 else f"argb_rank{rank}")
 
     tiles = (args.total_tiles or world * B) * args.steps
     value = tiles / elapsed
-    k2_ms = sum(k2) / len(k2) if k2 else float("nan")
-    achieved = BYTES_PER_TILE * B / (k2_ms * 1e-3) / 1e9
-    traffic = pmc_traffic(B)
+
+    k2 = []
+    if args.full:
+        # Second pass, same K steps, kernel timing ON: per-launch K2 durations (HIP events around
+        # each K2 launch on its stream) for the roofline.
+        ctx.kernel_timings()
+        ctx.enable_kernel_timing(True)
+        for _ in range(args.steps):
+            step()
+        ctx.synchronize()
+        ctx.enable_kernel_timing(False)
+        k2 = sorted(ms for ms, kind in ctx.kernel_timings() if kind == 2)
+        k2_ms = sum(k2) / len(k2) if k2 else float("nan")
+        achieved = BYTES_PER_TILE * B / (k2_ms * 1e-3) / 1e9
+        traffic = pmc_traffic(B)
 
     extra = {}
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         threads, _, _ = host_cores()
         if not args.no_latency:
             extra["p50_tile_latency_ms"] = latencies(torch, omr, ctx, qdef, chans, data)
@@ -1666,7 +1704,16 @@ def main():
                 "ranks_share_devices": world > n_dev,
                 "control_backend": backend,
             },
-            "roofline": {
+            "region_event_ms_per_step": round(region_ms / args.steps, 5),
+            "full": args.full,
+            "prewarm": {"ms": args.prewarm_ms, "steps": n_pre,
+                        "why": "untimed, before the W warm-up steps: GPU clock ramp out of idle "
+                               "(first ~25 K2 launches 0.77 -> 0.60 ms vs 0.55 sustained)"},
+        }
+        if args.dump_outputs:
+            line["dump_outputs"] = args.dump_outputs
+        if args.full:
+            line["roofline"] = {
                 "bound": "hbm",
                 "kernel": "k_render<u16,BE,4ch> (K2)",
                 "achieved": round(achieved, 1),
@@ -1683,16 +1730,12 @@ def main():
                 "timing": "second pass of the same K steps with per-launch HIP events on the "
                           "K2 stream; the throughput pass runs with kernel timing off",
                 "region_event_ms_per_step": round(region_ms / args.steps, 5),
-            },
-            "hbm_gbs": round(achieved, 1),
-            "prewarm": {"ms": args.prewarm_ms, "steps": n_pre,
-                        "why": "untimed, before the W warm-up steps: GPU clock ramp out of idle "
-                               "(first ~25 K2 launches 0.77 -> 0.60 ms vs 0.55 sustained)"},
-        }
-        line.update(extra)
-        if "cpu_baseline" not in line:
-            line["cpu_baseline"] = None
-        line["sections"] = sections_summary(line)      # last: the part of the line a tail keeps
+            }
+            line["hbm_gbs"] = round(achieved, 1)
+            line.update(extra)
+            if "cpu_baseline" not in line:
+                line["cpu_baseline"] = None
+            line["sections"] = sections_summary(line)      # last: the part of the line a tail keeps
         print(json.dumps(line), flush=True)
     ctx.close()
     if dist:

@@ -97,9 +97,51 @@ def test_c4_4096_tiles_sharded_over_8_ranks(c2_sources):
 
 
 @pytest.mark.gpu
+def test_bench_plain_run_dumps_the_last_steps_pixels(tmp_path, oracle):
+    """A plain run (no --full): K timed steps, the headline keys and nothing of the other sections;
+    --dump-outputs writes the seeded sample of the last step's ARGB pixels, equal to the CPU
+    restatement's render of the same seeded tiles at the same positions."""
+    import importlib.util
+    import torch
+    spec = importlib.util.spec_from_file_location("omr_bench", os.path.join(REPO, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    B, uniq = 8, 2
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+           "--batch", str(B), "--unique", str(uniq), "--prewarm-ms", "0", "--dump-outputs", str(tmp_path)]
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == 2 and d["unit"] == "tiles/s" and d["higher_is_better"] is True and d["dtype"] == "u16"
+    assert d["ms_per_step"] > 0 and d["value"] == pytest.approx(B / (d["ms_per_step"] * 1e-3), rel=1e-3)
+    for moved in ("roofline", "p50_tile_latency_ms", "jpeg", "png", "host_fed", "c3_projection", "c5_float",
+                  "cpu_baseline", "sections"):
+        assert moved not in d
+    assert sorted(os.listdir(tmp_path)) == ["argb.npy"]
+    got = np.load(tmp_path / "argb.npy")
+    assert got.dtype == np.float32 and got.shape == (bench.DUMP_PIXELS, 4) and got.nbytes <= 64 << 20
+    # the bench's inputs: tile t = seeded source tile t % uniq, stored big-endian
+    native = torch_tiles_u16(uniq, C, TILE, TILE, "cuda:0")
+    host = native.cpu().numpy().view(np.uint16).astype(">u2")
+    exp = []
+    for t in range(uniq):
+        st, e = oracle.render(c2_channels(C), [np.ascontiguousarray(host[t, c]) for c in range(C)],
+                              _lib.PIXELS_UINT16, TILE, TILE, big_endian=True)
+        assert st == 0
+        exp.append(e.reshape(-1))
+    idx = np.sort(np.random.default_rng(bench.DUMP_SEED).integers(0, B * TILE * TILE, size=bench.DUMP_PIXELS))
+    px = np.stack(exp)[(idx // (TILE * TILE)) % uniq, idx % (TILE * TILE)].astype(np.uint32)
+    want = np.stack([(px >> s) & 0xFF for s in (24, 16, 8, 0)], axis=-1).astype(np.float32)
+    assert np.array_equal(got, want)
+
+
+@pytest.mark.gpu
 def test_bench_gpus_2_spawns_two_ranks():
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--batch", "8", "--unique", "2", "--no-cpu-baseline", "--no-jpeg", "--no-configs", "--no-latency"]
+           "--batch", "8", "--unique", "2", "--full", "--no-cpu-baseline", "--no-jpeg", "--no-configs", "--no-latency"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stderr[-2000:]

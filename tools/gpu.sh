@@ -8,7 +8,7 @@
 #
 #   tests[=<pytest -k expr>]   the -m gpu suite (or the matching subset), one process
 #   smoke                      __graft_entry__.smoke()
-#   bench[=<extra args>]       bench.py --steps 20 --warmup 5 (the driver command) -> bench.json
+#   bench[=<extra args>]       bench.py --full --steps 20 --warmup 5 (every section) -> bench.json
 #   trace[=<extra args>]       rocprofv3 --kernel-trace --stats over that bench command
 #                              -> kernels.csv (per kernel+grid: launches, avg, median) + kernel_stats.csv
 #   headline                   the same trace over the headline leg alone (no JPEG / configs /
@@ -69,11 +69,11 @@ for step in "$@"; do
         run 300 smoke.log python -u -c "import __graft_entry__ as g; g.smoke(); print('SMOKE OK')"
         tail -1 $O/smoke.log ;;
     bench)
-        timeout -k 10 900 python -u bench.py --steps 20 --warmup 5 $arg > $O/bench.json 2> $O/bench.err \
+        timeout -k 10 900 python -u bench.py --full --steps 20 --warmup 5 $arg > $O/bench.json 2> $O/bench.err \
             || { echo "bench failed"; tail -30 $O/bench.err; exit 1; }
         tail -c 400 $O/bench.json; echo ;;
     trace|headline)
-        extra=$arg
+        extra="--full $arg"
         [ $name = headline ] && extra="--no-jpeg --no-configs --no-latency --no-cpu-baseline $arg"
         ( cd /tmp && timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/t_$name -o t \
             -- python3 $R/bench.py --steps 20 --warmup 5 $extra ) > $O/${name}_bench.json 2> $O/$name.err \
