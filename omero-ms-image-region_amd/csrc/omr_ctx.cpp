@@ -190,6 +190,8 @@ omr_status omr_ctx_create(int32_t device_ordinal, omr_ctx** out) {
         const int k = std::atoi(v);
         c->k2_eval_cpt = (k == 4 || k == 2 || k == -1 || k == -3) ? k : -2;
     }
+    // byte budget of the device LUT cache (64 KiB .. 256 MiB; the default is the upper bound)
+    if (const char* v = std::getenv("OMR_LUT_CACHE_KB")) c->dev_lut_budget = lut_cache_budget(std::atoll(v));
     *out = c;
     return OMR_OK;
 }

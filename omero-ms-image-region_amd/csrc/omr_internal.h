@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "omr/omr.h"
+#include "omr_lut_policy.h"
 
 struct omr_ctx;
 
@@ -136,10 +137,11 @@ struct Ctx {
     // Device cache of the kModeLut16 byte LUTs (non-linear 16-bit families, noise reduction): a
     // setting's LUT is built on the host once (host_quant_lut) and uploaded once, and every later
     // request with that setting reads it in place (omr_render.hip device_quant_lut).  LRU, at most
-    // kDevLutEntries LUTs and kDevLutBytes in all.
+    // kDevLutEntries LUTs and dev_lut_budget bytes in all (env OMR_LUT_CACHE_KB, 64 KiB .. 256 MiB),
+    // except that the LUTs of the plan being prepared always stay (omr_lut_policy.h).
     struct DevLut { std::vector<uint8_t> key; uint8_t* d = nullptr; size_t bytes = 0; uint64_t used = 0; };
     static constexpr int kDevLutEntries = 64;
-    static constexpr size_t kDevLutBytes = (size_t)256 << 20;
+    size_t dev_lut_budget = kLutCacheMaxBytes;
     std::vector<DevLut> dev_luts;
     size_t dev_lut_bytes = 0;
     uint64_t dev_lut_clock = 0;

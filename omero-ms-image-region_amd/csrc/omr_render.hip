@@ -228,8 +228,9 @@ template <int PT> __device__ __forceinline__ uint32_t raw_key(uint32_t raw) {
 #endif
 constexpr int kBucketsLog2 = OMR_K2_BUCKETS_LOG2, kBuckets = 1 << kBucketsLog2;
 // Buckets per channel: kBuckets u32 entries (8 KiB) for up to 4 threshold channels, half as many
-// above, so 8 channels' threshold + bucket tables still fit K2's 48 KiB (the 16-byte bucket maps
-// ride on top).
+// above.  kMaxThreshActive (8) channels then take 8 x (1 KiB contrib + 1 KiB thresholds + 4 KiB
+// buckets + the 16-byte map) = 49,280 bytes of K2's dynamic LDS: 128 bytes past 48 KiB, which
+// gfx950 grants (a workgroup may take up to the CU's 160 KiB; three such workgroups share a CU).
 __host__ __device__ constexpr int k2_buckets_log2(int na) { return na <= 4 ? kBucketsLog2 : kBucketsLog2 - 1; }
 __host__ __device__ constexpr int k2_buckets(int na) { return 1 << k2_buckets_log2(na); }
 // the launch's bucket count: k2_buckets, or for measurement OMR_K2_BUCKETS_LG (10..11: 2^lg) /
@@ -916,8 +917,11 @@ static void host_thresholds(const ChanParam& p, int32_t pt, int cds, int cde, ui
 
 // The device copy of a channel's kModeLut16 byte LUT, from the context's LRU cache (Ctx::dev_luts).
 // A miss builds the LUT on the host (host_quant_lut) and uploads it once; a hit costs a key compare:
-// no host evaluation, no PCIe traffic and no pinned-slot growth per request.
-static omr_status device_quant_lut(Ctx* ctx, const ChanParam& p, int cds, int cde, bool mono, uint64_t* addr) {
+// no host evaluation, no PCIe traffic and no pinned-slot growth per request.  `pin` is the cache
+// clock when the plan's prepare_plan began: entries stamped above it hold addresses this plan has
+// already taken and stay (omr_lut_policy.h).
+static omr_status device_quant_lut(Ctx* ctx, const ChanParam& p, int cds, int cde, bool mono, uint64_t pin,
+                                   uint64_t* addr) {
     const QuantLutKey key = quant_lut_key(p, cds, cde, mono);
     const uint8_t* kb = reinterpret_cast<const uint8_t*>(&key);
     const size_t n = (size_t)((int64_t)p.gmax - p.gmin + 1);
@@ -927,17 +931,28 @@ static omr_status device_quant_lut(Ctx* ctx, const ChanParam& p, int cds, int cd
             *addr = reinterpret_cast<uint64_t>(e.d);
             return OMR_OK;
         }
-    // evict least recently used entries past the count / byte budget; queued kernels of this
-    // context's stream may still read them, so the stream drains first (misses only)
-    bool drained = false;
-    while (!ctx->dev_luts.empty() && ((int)ctx->dev_luts.size() >= Ctx::kDevLutEntries ||
-                                      ctx->dev_lut_bytes + n > Ctx::kDevLutBytes)) {
-        if (!drained) { OMR_HIP(ctx, hipStreamSynchronize(ctx->stream)); drained = true; }
-        auto lru = std::min_element(ctx->dev_luts.begin(), ctx->dev_luts.end(),
-                                    [](const Ctx::DevLut& a, const Ctx::DevLut& b) { return a.used < b.used; });
-        OMR_HIP(ctx, hipFree(lru->d));
-        ctx->dev_lut_bytes -= lru->bytes;
-        ctx->dev_luts.erase(lru);
+    // evict least recently used entries past the count / byte budget, never one of this plan's;
+    // queued kernels of this context's stream may still read them, so the stream drains first
+    // (misses only)
+    std::vector<LutSlot> slots;
+    slots.reserve(ctx->dev_luts.size());
+    for (const auto& e : ctx->dev_luts) slots.push_back({e.bytes, e.used});
+    std::vector<size_t> victims;
+    lut_cache_victims(slots.data(), slots.size(), pin, n, (size_t)Ctx::kDevLutEntries, ctx->dev_lut_budget, victims);
+    if (!victims.empty()) {
+        OMR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        std::vector<Ctx::DevLut> keep;
+        std::vector<char> gone(slots.size(), 0);
+        for (size_t v : victims) gone[v] = 1;
+        hipError_t first = hipSuccess;
+        for (size_t i = 0; i < ctx->dev_luts.size(); ++i) {
+            if (!gone[i]) { keep.push_back(std::move(ctx->dev_luts[i])); continue; }
+            const hipError_t er = hipFree(ctx->dev_luts[i].d);
+            if (er != hipSuccess && first == hipSuccess) first = er;
+            ctx->dev_lut_bytes -= ctx->dev_luts[i].bytes;
+        }
+        ctx->dev_luts.swap(keep);
+        OMR_HIP(ctx, first);
     }
     std::vector<uint8_t> host(n);
     host_quant_lut(p, cds, cde, mono, host.data());
@@ -1055,17 +1070,18 @@ static omr_status prepare_plan(Ctx* ctx, const omr_quantum_def* q, const omr_cha
         ++na;
     }
     P.n_active = na;
-    if (na > kMaxThreshActive)   // threshold + bucket tables (6 KiB of LDS per channel): K2 within 48 KiB
+    if (na > kMaxThreshActive)   // threshold + bucket tables (6 KiB of LDS per channel): K2 at 49,280 bytes
         for (int i = 0; i < na; ++i)
             if (P.ch[i].mode == kModeThresh) P.ch[i].mode = kModeEval;
     pp.plan_bytes = offsetof(RenderPlan, ch) + sizeof(ChanParam) * (size_t)(na > 0 ? na : 1);
     if (pp.n_lut > 0) {
         const bool int_bounds = (P.sem & OMR_SEM_WINDOW_INT_BOUNDS) != 0;   // x in [(int)ws, ws): may wrap
         OMR_HIP(ctx, hipSetDevice(ctx->device));
+        const uint64_t pin = ctx->dev_lut_clock;   // this plan's hits and uploads stamp above it
         for (int i = 0; i < na; ++i)
             if (P.ch[i].mode == kModeLut16) {
                 const omr_status st = device_quant_lut(ctx, P.ch[i], q->cd_start, q->cd_end,
-                                                       !int_bounds && monotone_q(P.ch[i], *q), &P.ch[i].lut_addr);
+                                                       !int_bounds && monotone_q(P.ch[i], *q), pin, &P.ch[i].lut_addr);
                 if (st) return st;
             }
     }

@@ -65,10 +65,12 @@ def _window(rng, dtype):
     return a, b
 
 
-def _config(seed):
+def _config(seed, n_range=(1, 5)):
+    """Random settings for seed; n_range: the channel count's [low, high) (5..12 channels:
+    test_many_channels_gpu.py)."""
     rng = np.random.default_rng(seed)
     pt, dtype = TYPES[seed % len(TYPES)]
-    n = int(rng.integers(1, 5))
+    n = int(rng.integers(*n_range))
     chans = []
     for c in range(n):
         ws, we = _window(rng, dtype)
