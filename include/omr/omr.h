@@ -219,6 +219,67 @@ omr_status omr_render_pixel_buffer_tiles(omr_ctx* ctx, const omr_pixel_buffer* p
                                          int32_t height, int32_t flip_h, int32_t flip_v,
                                          uint32_t* argb_out, int32_t out_on_device);
 
+/* ---- plane statistics and histograms (K9) ---------------------------------- */
+/*
+ * What webgateway/histogram_json serves, and what fills omr_channel_binding.global_min /
+ * global_max (OMERO's StatsInfo) when the caller has none.  The reference snapshot predates the
+ * endpoint, so the rule is this library's own, modelled on RawPixelsStore.getHistogram.
+ *
+ * A plane is width x height pixels of one OMR_PIXELS_* type, big-endian (file order) or native,
+ * row_stride_px pixels between row starts (0 = width); region NULL = the whole plane.  Every
+ * pixel v is taken as a double (exact for every type).
+ *   statistics  nan_count = NaN pixels; count = w*h - nan_count; min / max over the others
+ *               (+-Infinity take part); min = +Infinity, max = -Infinity when count is 0.
+ *   histogram   NaN -> nan_count; v < lo -> below; v > hi -> above; else, in IEEE double with one
+ *               rounding per operation,
+ *                   range = hi - lo + 1.0;  bin_range = range / (double)bin_count;
+ *                   bin   = min((int64)((v - lo) / bin_range), bin_count - 1)
+ *               (the + 1.0 for every type, float included: OMERO's rule).
+ *               sum(counts) + below + above + nan_count == w*h.
+ * OMR_INVALID_ARGUMENT, decided before any launch (the context stays usable): a NULL pointer, an
+ * unknown pixel type, n_planes outside 1..32, bin_count outside 1..OMR_HIST_MAX_BINS, lo, hi or
+ * hi - lo not finite, lo > hi, width, height or a region side <= 0, a region that leaves the
+ * plane, 0 < row_stride_px < width, a region of 2^32 pixels or more, a plane pointer that is not
+ * a multiple of the pixel size.
+ */
+typedef struct omr_plane_stats { double min, max; uint64_t count, nan_count; } omr_plane_stats;
+typedef struct omr_histogram_info { double lo, hi; uint64_t below, above, nan_count; } omr_histogram_info;
+enum {
+    OMR_HIST_RANGE_TYPE = 0,      /* the pixel-type range of omr_create_rendering_def (usePixelsTypeRange) */
+    OMR_HIST_RANGE_PLANE = 1,     /* the region's own min / max; no non-NaN pixel: every count 0, OMR_OK */
+    OMR_HIST_RANGE_EXPLICIT = 2   /* the caller's lo / hi (e.g. StatsInfo) */
+};
+enum { OMR_HIST_MAX_BINS = 4096 };
+
+/* The rule, on the host: bin index, or -1 below, -2 above, -3 NaN. */
+int32_t    omr_histogram_bin_of(double v, double lo, double hi, int32_t bin_count);
+
+/* d_planes: HOST array of n_planes device pointers; results in HOST memory; synchronous, on the
+ * context's stream. */
+omr_status omr_plane_stats_device(omr_ctx* ctx, const void* const* d_planes, int32_t n_planes,
+                                  int32_t pixel_type, int32_t big_endian, int32_t width, int32_t height,
+                                  int64_t row_stride_px, const omr_region* region,
+                                  omr_plane_stats* stats_out /* [n_planes] */);
+omr_status omr_histogram_device(omr_ctx* ctx, const void* const* d_planes, int32_t n_planes,
+                                int32_t pixel_type, int32_t big_endian, int32_t width, int32_t height,
+                                int64_t row_stride_px, const omr_region* region,
+                                const double* lo, const double* hi /* [n_planes] */, int32_t bin_count,
+                                uint32_t* counts_out /* [n_planes][bin_count] */,
+                                omr_histogram_info* info_out /* [n_planes] */);
+/* One host plane (rows packed): upload, statistics pass when range_mode or stats_out (may be
+ * NULL) needs it, histogram.  lo / hi are read in OMR_HIST_RANGE_EXPLICIT only. */
+omr_status omr_histogram(omr_ctx* ctx, const void* plane, int32_t pixel_type, int32_t big_endian,
+                         int32_t width, int32_t height, const omr_region* region, int32_t range_mode,
+                         double lo, double hi, int32_t bin_count, uint32_t* counts_out,
+                         omr_histogram_info* info_out, omr_plane_stats* stats_out);
+/* histogram_json for plane (z, c, t) of a ROMIO buffer: only the region's rows are read (the tile
+ * read, into pinned memory), copied on the copy stream and counted on the context's.
+ * OMR_INVALID_ARGUMENT for z, c or t outside the image, as omr_pixel_buffer_get_tile. */
+omr_status omr_pixel_buffer_histogram(omr_ctx* ctx, const omr_pixel_buffer* pb, int32_t z, int32_t c,
+                                      int32_t t, const omr_region* region, int32_t range_mode,
+                                      double lo, double hi, int32_t bin_count, uint32_t* counts_out,
+                                      omr_histogram_info* info_out, omr_plane_stats* stats_out);
+
 /* ---- request batching ------------------------------ */
 /*
  * Concurrent render_image_region requests coalesced into GPU batches.  The reference runs each

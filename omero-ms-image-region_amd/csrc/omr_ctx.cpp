@@ -170,7 +170,10 @@ omr_status omr_ctx_create(int32_t device_ordinal, omr_ctx** out) {
     for (int i = 0; i < Ctx::kPinSlots && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&c->pin_ev[i], hipEventDisableTiming);
     if (e == hipSuccess) {
         hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, device_ordinal) == hipSuccess) c->cu_count = prop.multiProcessorCount;
+        if (hipGetDeviceProperties(&prop, device_ordinal) == hipSuccess) {
+            c->cu_count = prop.multiProcessorCount;
+            if (prop.sharedMemPerBlock) c->lds_per_block = prop.sharedMemPerBlock;
+        }
     }
     if (e != hipSuccess) {
         omr_ctx_destroy(c);

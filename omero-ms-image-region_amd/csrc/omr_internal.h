@@ -115,6 +115,7 @@ struct Ctx {
     hipEvent_t pin_ev[kPinSlots] = {};
     int pin_slot = 0;
     int cu_count = 256;
+    size_t lds_per_block = 64 * 1024;   // LDS one workgroup may allocate (K9 sizes its tables by it)
     bool k2_nt_store = false;   // env OMR_K2_NT_STORE=1: non-temporal ARGB stores (measurement switch)
     uint32_t sem = 0;            // OMR_SEM_* (omr_ctx_set_semantics)
     // projection glue through the fused K3R kernel (env OMR_K3R=1; measured slower than K3 + K2
@@ -234,7 +235,19 @@ uint64_t pixel_buffer_serial(const omr_pixel_buffer* pb);
 // The (c, t) Z-stack of a pixel buffer into device memory on ctx's stream (omr_pixbuf.cpp).
 omr_status pixel_buffer_upload_stack(omr_ctx* ctx, const omr_pixel_buffer* pb, int32_t c, int32_t t, void* d_dst);
 
-#define OMR_HIP(ctx, expr)                                          \
+// K9 (omr_stats.hip) for one plane that a caller has put in device memory itself (omr_histogram,
+// omr_pixel_buffer_histogram): argument check (no launch), scratch size, and the synchronous run
+// (statistics pass when the range mode or stats_out asks for it, then the histogram).
+omr_status validate_histogram_plane(Ctx* c, int32_t pixel_type, int32_t width, int32_t height,
+                                    const omr_region* region, int32_t range_mode, double lo, double hi,
+                                    int32_t bin_count, const void* counts_out, const void* info_out);
+size_t histogram_plane_ws_bytes(int32_t pixel_type, int32_t bin_count);
+omr_status histogram_plane_uploaded(Ctx* c, const void* d_plane, uint8_t* scratch, int32_t pixel_type,
+                                    int32_t big_endian, int32_t width, int32_t height, const omr_region* region,
+                                    int32_t range_mode, double lo, double hi, int32_t bin_count,
+                                    uint32_t* counts_out, omr_histogram_info* info_out, omr_plane_stats* stats_out);
+
+#define OMR_HIP(ctx, expr)                                         \
     do {                                                            \
         hipError_t _e = (expr);                                     \
         if (_e != hipSuccess) return ::omr::hip_fail((ctx), _e, #expr); \

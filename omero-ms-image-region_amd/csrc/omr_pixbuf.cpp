@@ -338,6 +338,42 @@ omr_status omr_pixel_buffer_get_tile(const omr_pixel_buffer* pb, int32_t z, int3
     return read_tile(pb, z, c, t, x, y, w, h, static_cast<uint8_t*>(dst)) ? OMR_OK : OMR_INTERNAL;
 }
 
+// histogram_json for one plane: the region's rows (the tile read) into pinned memory, to the
+// workspace on the copy stream, then K9 on the context's stream (omr_stats.hip).
+omr_status omr_pixel_buffer_histogram(omr_ctx* ctx, const omr_pixel_buffer* pb, int32_t z, int32_t c, int32_t t,
+                                      const omr_region* region, int32_t range_mode, double lo, double hi,
+                                      int32_t bin_count, uint32_t* counts_out, omr_histogram_info* info_out,
+                                      omr_plane_stats* stats_out) {
+    if (!ctx) return OMR_INVALID_ARGUMENT;
+    if (!pb) return fail(ctx, OMR_INVALID_ARGUMENT, "null pixel buffer");
+    if (!tile_in_bounds(pb, z, c, t, 0, 0, 0, 0)) return fail(ctx, OMR_INVALID_ARGUMENT, "plane outside the image");
+    omr_status st = validate_histogram_plane(ctx, pb->pt, pb->sx, pb->sy, region, range_mode, lo, hi, bin_count,
+                                             counts_out, info_out);
+    if (st) return st;
+    const int32_t x = region ? region->x : 0, y = region ? region->y : 0;
+    const int32_t w = region ? region->width : pb->sx, h = region ? region->height : pb->sy;
+    OMR_HIP(ctx, hipSetDevice(ctx->device));
+    PixPipe* P = nullptr;
+    st = get_pipe(ctx, P);
+    if (st) return st;
+    const size_t bytes = (size_t)w * h * pb->bpp, plane_al = align_up(bytes, 256);
+    st = grow(ctx, P, bytes, 0, false);
+    if (st) return st;
+    st = ensure_workspace(ctx, plane_al + histogram_plane_ws_bytes(pb->pt, bin_count));
+    if (st) return st;
+    OMR_HIP(ctx, hipEventSynchronize(P->h2d[0]));                      // pinned slot 0 is free
+    if (!read_tile(pb, z, c, t, x, y, w, h, static_cast<uint8_t*>(P->pin_in[0])))
+        return fail(ctx, OMR_INTERNAL, "pixel buffer read failed");
+    uint8_t* ws = static_cast<uint8_t*>(ctx->ws);
+    OMR_HIP(ctx, hipEventRecord(P->rend[0], ctx->stream));             // earlier work is done with the workspace
+    OMR_HIP(ctx, hipStreamWaitEvent(P->copy, P->rend[0], 0));
+    OMR_HIP(ctx, hipMemcpyAsync(ws, P->pin_in[0], bytes, hipMemcpyHostToDevice, P->copy));
+    OMR_HIP(ctx, hipEventRecord(P->h2d[0], P->copy));
+    OMR_HIP(ctx, hipStreamWaitEvent(ctx->stream, P->h2d[0], 0));
+    return histogram_plane_uploaded(ctx, ws, ws + plane_al, pb->pt, 1, w, h, nullptr, range_mode, lo, hi, bin_count,
+                                    counts_out, info_out, stats_out);
+}
+
 omr_status omr_ctx_set_pixel_buffer_dma(omr_ctx* ctx, int32_t enable) {
     if (!ctx) return OMR_INVALID_ARGUMENT;
     ctx->pixbuf_direct = enable != 0;

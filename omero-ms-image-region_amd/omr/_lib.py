@@ -97,6 +97,19 @@ class Region(ctypes.Structure):
                 ("width", ctypes.c_int32), ("height", ctypes.c_int32)]
 
 
+class PlaneStats(ctypes.Structure):
+    _fields_ = [("min", ctypes.c_double), ("max", ctypes.c_double),
+                ("count", ctypes.c_uint64), ("nan_count", ctypes.c_uint64)]
+
+
+class HistogramInfo(ctypes.Structure):
+    _fields_ = [("lo", ctypes.c_double), ("hi", ctypes.c_double), ("below", ctypes.c_uint64),
+                ("above", ctypes.c_uint64), ("nan_count", ctypes.c_uint64)]
+
+
+HIST_RANGE_TYPE, HIST_RANGE_PLANE, HIST_RANGE_EXPLICIT = 0, 1, 2
+HIST_MAX_BINS = 4096
+
 _NCH = 64
 
 
@@ -152,6 +165,13 @@ _SIGS = {
     "omr_pixel_buffer_plane_offset": (_i64, [_vp, _i32, _i32, _i32]),
     "omr_pixel_buffer_get_tile": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _sz]),
     "omr_ctx_set_pixel_buffer_dma": (_i32, [_vp, _i32]),
+    "omr_histogram_bin_of": (_i32, [ctypes.c_double, ctypes.c_double, ctypes.c_double, _i32]),
+    "omr_plane_stats_device": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i64, _vp, _vp]),
+    "omr_histogram_device": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i64, _vp, _vp, _vp, _i32, _vp, _vp]),
+    "omr_histogram": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, ctypes.c_double, ctypes.c_double, _i32,
+                             _vp, _vp, _vp]),
+    "omr_pixel_buffer_histogram": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _i32, ctypes.c_double, ctypes.c_double,
+                                          _i32, _vp, _vp, _vp]),
     "omr_batcher_create": (_i32, [_i32, _i32, _i32, ctypes.POINTER(_vp)]),
     "omr_batcher_destroy": (None, [_vp]),
     "omr_batcher_submit": (_i32, [_vp, _vp, ctypes.POINTER(ctypes.c_uint64)]),

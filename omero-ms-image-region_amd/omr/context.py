@@ -25,6 +25,17 @@ def _ptr(a):
     raise TypeError(f"cannot take the address of {type(a)}")
 
 
+def _region(region):
+    """omr_region* of (x, y, width, height), or NULL for the whole plane."""
+    if region is None:
+        return None
+    return ctypes.pointer(_lib.Region(*[int(v) for v in region]))
+
+
+def _info_dict(i):
+    return {"lo": i.lo, "hi": i.hi, "below": int(i.below), "above": int(i.above), "nan_count": int(i.nan_count)}
+
+
 def make_bindings(channels):
     """ChannelBinding[] from a list of dicts / ChannelSettings; keeps LUT buffers alive."""
     n = len(channels)
@@ -266,6 +277,62 @@ class Context:
                                               int(flip_v), _ptr(out)), self.h)
         return out
 
+    # ---- statistics and histograms (K9) --------------------------------------------------
+    def _device_planes(self, planes):
+        """Device addresses of planes: numpy arrays are uploaded (bytes as they are), tensors and
+        addresses used in place.  Returns (ctypes pointer array, tensors to keep alive)."""
+        import torch
+        keep = []
+        for p in planes:
+            if isinstance(p, np.ndarray):
+                host = np.ascontiguousarray(p).view(np.uint8).reshape(-1)
+                p = torch.from_numpy(host).to(torch.device("cuda", self.device))
+            keep.append(p)
+        return (ctypes.c_void_p * max(len(keep), 1))(*[_ptr(p) for p in keep]), keep
+
+    def plane_stats(self, planes, pixel_type, width, height, big_endian=False, row_stride=0, region=None):
+        """[{min, max, count, nan_count}] of each plane's region (omr_plane_stats_device): what
+        fills a channel's global_min / global_max when no StatsInfo is at hand."""
+        ptrs, keep = self._device_planes(planes)
+        n = len(planes)
+        out = (_lib.PlaneStats * max(n, 1))()
+        check(lib.omr_plane_stats_device(self.h, ptrs, n, pixel_type, int(big_endian), width, height, row_stride,
+                                         _region(region), out), self.h)
+        return [{"min": s.min, "max": s.max, "count": int(s.count), "nan_count": int(s.nan_count)} for s in out[:n]]
+
+    def histogram(self, planes, pixel_type, width, height, ranges, bins=256, big_endian=False, row_stride=0,
+                  region=None):
+        """Histograms of each plane's region over ranges = [(lo, hi)] (one pair: every plane):
+        (counts[n][bins] uint32, [{lo, hi, below, above, nan_count}]) (omr_histogram_device)."""
+        ptrs, keep = self._device_planes(planes)
+        n = len(planes)
+        ranges = list(ranges)
+        if len(ranges) == 2 and not hasattr(ranges[0], "__len__"):
+            ranges = [tuple(ranges)]
+        if len(ranges) == 1:
+            ranges = ranges * n
+        if len(ranges) != n:
+            raise ValueError("one (lo, hi) per plane")
+        lo = (ctypes.c_double * max(n, 1))(*[float(r[0]) for r in ranges])
+        hi = (ctypes.c_double * max(n, 1))(*[float(r[1]) for r in ranges])
+        counts = np.zeros((n, max(int(bins), 0)), dtype=np.uint32)
+        info = (_lib.HistogramInfo * max(n, 1))()
+        check(lib.omr_histogram_device(self.h, ptrs, n, pixel_type, int(big_endian), width, height, row_stride,
+                                       _region(region), lo, hi, int(bins), counts.ctypes.data, info), self.h)
+        return counts, [_info_dict(i) for i in info[:n]]
+
+    def histogram_host(self, plane, pixel_type, width, height, bins=256, range_mode=_lib.HIST_RANGE_TYPE, lo=None,
+                       hi=None, big_endian=False, region=None):
+        """One host plane through omr_histogram: (counts[bins], info, stats)."""
+        plane = np.ascontiguousarray(plane)
+        counts = np.zeros(max(int(bins), 0), dtype=np.uint32)
+        info, stats = _lib.HistogramInfo(), _lib.PlaneStats()
+        check(lib.omr_histogram(self.h, plane.ctypes.data, pixel_type, int(big_endian), width, height,
+                                _region(region), int(range_mode), float(lo or 0.0), float(hi or 0.0), int(bins),
+                                counts.ctypes.data, ctypes.byref(info), ctypes.byref(stats)), self.h)
+        return counts, _info_dict(info), {"min": stats.min, "max": stats.max, "count": int(stats.count),
+                                          "nan_count": int(stats.nan_count)}
+
     # ---- encode ------------------------------------------------------------------------
     def _encode(self, fn, src, *args, cap):
         out = np.empty(cap, dtype=np.uint8)
@@ -410,5 +477,6 @@ def _torch_ordered(fn):
     return call
 
 
-for _name in [n for n in vars(Context) if n.endswith("_device") or n == "encode_jpeg_batch"]:
+for _name in [n for n in vars(Context)
+              if n.endswith("_device") or n in ("encode_jpeg_batch", "plane_stats", "histogram")]:
     setattr(Context, _name, _torch_ordered(getattr(Context, _name)))

@@ -74,6 +74,19 @@ class PixelBuffer:
                                                      host[z].ctypes.data, host[z].nbytes))
         return torch.from_numpy(host.view(np.uint8).reshape(-1)).to(device)
 
+    def histogram(self, ctx, z, c, t, bins=256, range_mode=_lib.HIST_RANGE_TYPE, lo=None, hi=None, region=None):
+        """Histogram of plane (z, c, t), or of its region (x, y, w, h), on ctx's GPU
+        (omr_pixel_buffer_histogram): (counts[bins] uint32, info, stats) with info = {lo, hi, below,
+        above, nan_count} and stats = {min, max, count, nan_count} of the region."""
+        from .context import _info_dict, _region
+        counts = np.zeros(max(int(bins), 0), dtype=np.uint32)
+        info, stats = _lib.HistogramInfo(), _lib.PlaneStats()
+        _lib.check(lib.omr_pixel_buffer_histogram(ctx.h, self.h, z, c, t, _region(region), int(range_mode),
+                                                  float(lo or 0.0), float(hi or 0.0), int(bins), counts.ctypes.data,
+                                                  ctypes.byref(info), ctypes.byref(stats)), ctx.h)
+        return counts, _info_dict(info), {"min": stats.min, "max": stats.max, "count": int(stats.count),
+                                          "nan_count": int(stats.nan_count)}
+
     def plane_offset(self, z, c, t):
         return lib.omr_pixel_buffer_plane_offset(self.h, z, c, t)
 
