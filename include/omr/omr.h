@@ -111,7 +111,9 @@ omr_status  omr_ctx_create(int32_t device_ordinal, omr_ctx** out);
 void        omr_ctx_destroy(omr_ctx* ctx);
 const char* omr_last_error(const omr_ctx* ctx);
 omr_status  omr_ctx_synchronize(omr_ctx* ctx);
-/* Run subsequent device-side calls on a caller-owned hipStream_t (NULL = ctx's own). */
+/* Run subsequent device-side calls on a caller-owned hipStream_t (NULL = ctx's own).  A change of
+ * stream waits for the work queued on the previous one when the context holds cached render
+ * settings (their tables are ordered by the stream), so the previous stream must still exist. */
 omr_status  omr_ctx_set_stream(omr_ctx* ctx, void* hip_stream);
 void*       omr_ctx_get_stream(omr_ctx* ctx);
 /*
@@ -178,6 +180,12 @@ enum {
 /* Semantics of every later call on this context (renders, projections' renders, JPEG). */
 omr_status omr_ctx_set_semantics(omr_ctx* ctx, uint32_t flags);
 uint32_t   omr_ctx_get_semantics(const omr_ctx* ctx);
+/*
+ * Debug / test hook: lookups of the context's device cache of staged render settings that found
+ * their setting (hits: no table-building launch in front of the render kernel) and that did not
+ * (misses) since the context was created.  Both stay 0 with OMR_PLAN_CACHE=0.
+ */
+omr_status omr_debug_plan_cache_stats(omr_ctx* ctx, uint64_t* hits, uint64_t* misses);
 
 /* ---- pixel buffer: ROMIO repository file -> pinned staging -> HBM ---------- */
 /*

@@ -185,6 +185,11 @@ omr_status omr_ctx_create(int32_t device_ordinal, omr_ctx** out) {
     if (const char* v = std::getenv("OMR_PNG_DEVICE_D3")) c->png_device_d3 = std::atoi(v) != 0;
     if (const char* v = std::getenv("OMR_PNG_SINGLE_BATCHED")) c->png_single_batched = std::atoi(v) != 0;
     if (const char* v = std::getenv("OMR_F1_F32")) c->f1_f32 = std::atoi(v) != 0;
+    if (const char* v = std::getenv("OMR_PLAN_CACHE")) c->plan_cache = std::atoi(v) != 0;
+    {
+        const char* v = std::getenv("OMR_PLAN_CACHE_SLOTS");
+        c->plan_slots.resize((size_t)plan_cache_slot_count(v ? std::atoll(v) : 0));
+    }
     // B4a / B6 grids for 0.4 B per pixel (C2 q 0.9 streams are 0.37; longer ones loop): same-box A/B
     // 210.2k (1.0 B/px, the round-3 sizing) -> 213.5k C2 tiles/s fused (profiles/r04/ab_jpeg_est_groups.txt)
     c->jpeg_est_centibpp = 40;
@@ -240,6 +245,7 @@ void omr_ctx_destroy(omr_ctx* c) {
     if (c->aux) (void)hipFree(c->aux);
     if (c->d_crc_pow) (void)hipFree(c->d_crc_pow);
     for (auto& l : c->dev_luts) (void)hipFree(l.d);
+    if (c->d_plan_slots) (void)hipFree(c->d_plan_slots);
     if (c->d_flag) (void)hipFree(c->d_flag);
     if (c->h_flag) (void)hipHostFree(c->h_flag);
     if (c->h_out) (void)hipHostFree(c->h_out);
@@ -262,7 +268,18 @@ omr_status omr_ctx_synchronize(omr_ctx* c) {
 
 omr_status omr_ctx_set_stream(omr_ctx* c, void* s) {
     if (!c) return OMR_INVALID_ARGUMENT;
-    c->stream = s ? static_cast<hipStream_t>(s) : c->own_stream;
+    hipStream_t ns = s ? static_cast<hipStream_t>(s) : c->own_stream;
+    if (ns == c->stream) return OMR_OK;
+    // the plan cache's slots are ordered by the stream their kernels run on: kernels queued on the
+    // old stream may still read them, so it drains before a kernel on the new one may refill any
+    bool cached = false;
+    for (const auto& sl : c->plan_slots) cached |= !sl.key.empty();
+    if (cached) {
+        OMR_HIP(c, hipSetDevice(c->device));
+        OMR_HIP(c, hipStreamSynchronize(c->stream));
+        for (auto& sl : c->plan_slots) sl = PlanSlot();
+    }
+    c->stream = ns;
     return OMR_OK;
 }
 
@@ -274,6 +291,13 @@ omr_status omr_ctx_set_semantics(omr_ctx* c, uint32_t flags) {
 }
 
 uint32_t omr_ctx_get_semantics(const omr_ctx* c) { return c ? c->sem : 0u; }
+
+omr_status omr_debug_plan_cache_stats(omr_ctx* c, uint64_t* hits, uint64_t* misses) {
+    if (!c) return OMR_INVALID_ARGUMENT;
+    if (hits) *hits = c->plan_hits;
+    if (misses) *misses = c->plan_misses;
+    return OMR_OK;
+}
 
 void* omr_ctx_get_stream(omr_ctx* c) { return c ? static_cast<void*>(c->stream) : nullptr; }
 

@@ -16,6 +16,7 @@
 
 #include "omr/omr.h"
 #include "omr_lut_policy.h"
+#include "omr_plan_cache.h"
 
 struct omr_ctx;
 
@@ -146,6 +147,19 @@ struct Ctx {
     std::vector<DevLut> dev_luts;
     size_t dev_lut_bytes = 0;
     uint64_t dev_lut_clock = 0;
+    // Device cache of staged render settings (omr_render.hip plan_tables): per setting, the staged
+    // RenderPlan and the tables K1 builds from it (contrib, thresholds, buckets + maps), so that a
+    // request whose settings a slot already holds launches nothing in front of K2.  plan_slots.size()
+    // slots of plan_slot_bytes each in one device allocation of its own (the workspace arena is
+    // freed and reallocated as it grows), made on first use.  Slots are written and read only by
+    // kernels on `stream`, so a refill orders itself behind queued readers; omr_ctx_set_stream
+    // drains the old stream and empties the cache.  OMR_PLAN_CACHE=0: off (tables in the workspace,
+    // rebuilt per call); OMR_PLAN_CACHE_SLOTS: slot count.
+    bool plan_cache = true;
+    std::vector<PlanSlot> plan_slots;
+    uint8_t* d_plan_slots = nullptr;
+    size_t plan_slot_bytes = 0;
+    uint64_t plan_clock = 0, plan_hits = 0, plan_misses = 0;
     // kernel timing (omr_ctx_enable_kernel_timing)
     bool timing = false;
     struct Timed { hipEvent_t start, stop; int kind; };

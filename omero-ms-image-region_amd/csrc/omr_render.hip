@@ -1002,7 +1002,7 @@ static omr_status prepare_plan(Ctx* ctx, const omr_quantum_def* q, const omr_cha
         if (b.family < OMR_FAMILY_LINEAR || b.family > OMR_FAMILY_EXPONENTIAL)
             return fail(ctx, OMR_INVALID_ARGUMENT, "unknown family");
         ChanParam& p = P.ch[na];
-        std::memset(&p, 0, offsetof(ChanParam, lut_rgb));   // the 768-byte LUT copy only when used
+        std::memset(&p, 0, offsetof(ChanParam, lut_rgb));
         p.index = c;
         p.family = b.family;
         if (b.family == OMR_FAMILY_LOGARITHMIC && (P.sem & OMR_SEM_LOG_UNGUARDED)) p.family = kFamLogRaw;
@@ -1010,7 +1010,9 @@ static omr_status prepare_plan(Ctx* ctx, const omr_quantum_def* q, const omr_cha
         p.nr = b.noise_reduction != 0 && !(P.sem & OMR_SEM_NOISE_REDUCTION_OFF);
         p.reverse = b.reverse != 0;
         p.has_lut = b.lut != nullptr;
+        // every staged byte is defined: the plan bytes are the plan cache's key (plan_tables)
         if (b.lut) std::memcpy(p.lut_rgb, b.lut, 768);
+        else std::memset(p.lut_rgb, 0, 768);
         p.ws = b.input_start;
         p.we = b.input_end;
         p.k = b.coefficient;
@@ -1103,6 +1105,96 @@ static RenderLayout layout_for(const PreparedPlan&, size_t extra) {
     L.extra_off = L.bucket_off + align_up((size_t)kMaxActive * (kBuckets * 4 + sizeof(BucketMap)), 256);
     L.total = L.extra_off + extra;
     return L;
+}
+
+// The device tables of one render call: the staged plan, K1's contribution table and, for
+// kModeThresh channels, the code thresholds and their buckets.
+struct PlanTables {
+    RenderPlan* plan = nullptr;
+    uint32_t *contrib = nullptr, *thresh = nullptr, *buckets = nullptr;
+    PlanSlot* slot = nullptr;        // the plan-cache slot holding them (null: the workspace, cache off)
+    int bk_n = 0;                    // k2_launch_buckets(n_active)
+    bool use_thresh = false;
+};
+
+// Stage the plan and build its tables -- or find them where an earlier call with the same settings
+// left them.  With the plan cache (Ctx::plan_slots) a setting's tables live in a slot of the
+// context's own allocation at the workspace layout's offsets; a lookup that finds the setting (the
+// normal case: a viewer pans one image with one set of settings, the batcher groups requests by
+// settings) launches nothing, and a miss refills the least recently used slot exactly as the
+// uncached path fills the workspace at `ws` -- except that K1 always runs, so that a slot filled
+// by a small launch (which builds its contributions in LDS from the plan) also serves a full one.
+// need_contrib: the uncached path runs K1.  A host plane-pointer table (ptr_src, ptr_bytes) goes
+// to d_ptrs with the plan's staging launch, or on a hit with one of its own.
+static omr_status plan_tables(Ctx* ctx, PreparedPlan& pp, int32_t pixel_type, uint8_t* ws, const RenderLayout& L,
+                              bool need_contrib, void* d_ptrs, const void* ptr_src, size_t ptr_bytes,
+                              PlanTables& T) {
+    const int na = pp.plan.n_active;
+    T.bk_n = k2_launch_buckets(na);
+    for (int i = 0; i < na; ++i) T.use_thresh |= pp.plan.ch[i].mode == kModeThresh;
+    if (!ptr_src) ptr_bytes = 0;
+    uint8_t* base = ws;
+    bool hit = false;
+    if (ctx->plan_cache && !ctx->plan_slots.empty()) {
+        if (!ctx->d_plan_slots) {
+            const size_t slot_bytes = layout_for(pp, 0).extra_off;
+            void* d = nullptr;
+            if (hipMalloc(&d, slot_bytes * ctx->plan_slots.size()) != hipSuccess)
+                return fail(ctx, OMR_OOM, "plan cache allocation failed");
+            ctx->d_plan_slots = static_cast<uint8_t*>(d);
+            ctx->plan_slot_bytes = slot_bytes;
+        }
+        static thread_local std::vector<uint8_t> key;
+        // the channel slots in use only (a plan without active channels stages one unset slot)
+        plan_cache_key(&pp.plan, offsetof(RenderPlan, ch) + sizeof(ChanParam) * (size_t)na, pixel_type, T.bk_n, key);
+        int i = plan_cache_find(ctx->plan_slots, key);
+        hit = i >= 0;
+        if (hit) {
+            ++ctx->plan_hits;
+        } else {
+            ++ctx->plan_misses;
+            i = plan_cache_victim(ctx->plan_slots);
+            ctx->plan_slots[i] = PlanSlot();
+            ctx->plan_slots[i].key = key;
+        }
+        T.slot = &ctx->plan_slots[i];
+        T.slot->used = ++ctx->plan_clock;
+        base = ctx->d_plan_slots + (size_t)i * ctx->plan_slot_bytes;
+    }
+    T.plan = reinterpret_cast<RenderPlan*>(base + L.plan_off);
+    T.contrib = reinterpret_cast<uint32_t*>(base + L.contrib_off);
+    T.thresh = reinterpret_cast<uint32_t*>(base + L.thresh_off);
+    T.buckets = reinterpret_cast<uint32_t*>(base + L.bucket_off);
+    if (hit) return ptr_bytes ? stage_h2d(ctx, d_ptrs, ptr_src, ptr_bytes) : OMR_OK;
+    auto fill = [&]() -> omr_status {
+        std::vector<uint32_t> thr;
+        if (T.use_thresh) {                             // the code thresholds, on the host (exact)
+            thr.assign((size_t)na * 256, 0u);
+            for (int i = 0; i < na; ++i)
+                if (pp.plan.ch[i].mode == kModeThresh)
+                    host_thresholds(pp.plan.ch[i], pixel_type, pp.plan.cd_start, pp.plan.cd_end, thr.data() + 256 * i);
+        }
+        const bool thr_with_plan = T.use_thresh && !ptr_bytes;   // one staging launch for both
+        omr_status st = thr_with_plan
+                            ? stage_h2d2(ctx, T.plan, &pp.plan, pp.plan_bytes, T.thresh, thr.data(), thr.size() * 4)
+                            : stage_h2d2(ctx, T.plan, &pp.plan, pp.plan_bytes, d_ptrs, ptr_src, ptr_bytes);
+        if (st != OMR_OK) return st;
+        if (T.use_thresh && !thr_with_plan && (st = stage_h2d(ctx, T.thresh, thr.data(), thr.size() * 4))) return st;
+        if (na > 0 && (T.slot || need_contrib)) {
+            hipLaunchKernelGGL(k_build_contrib, dim3(na), dim3(256), 0, ctx->stream, T.plan, T.contrib,
+                               pixel_type == OMR_PIXELS_INT8 ? 1 : 0);
+            OMR_HIP(ctx, hipGetLastError());
+        }
+        if (T.use_thresh) {
+            hipLaunchKernelGGL(k_build_buckets, dim3(T.bk_n / 256, na), dim3(256), 0, ctx->stream, T.plan, T.thresh,
+                               T.buckets, T.bk_n);
+            OMR_HIP(ctx, hipGetLastError());
+        }
+        return OMR_OK;
+    };
+    const omr_status st = fill();
+    if (st != OMR_OK && T.slot) *T.slot = PlanSlot();   // never hit a slot whose fill did not go out
+    return st;
 }
 
 // The pipelined float kernel holds two work blocks in registers (87 VGPRs at three channels: 5
@@ -1323,28 +1415,7 @@ static omr_status enqueue_render(Ctx* ctx, PreparedPlan& pp, int32_t pixel_type,
                                  const void* ptr_src = nullptr, size_t ptr_bytes = 0) {
     // ptr_bytes > 0: the host plane-pointer table ptr_src goes to d_plane_ptrs in the same
     // staging launch as the plan
-    uint8_t* ws = static_cast<uint8_t*>(ctx->ws);
-    RenderPlan* d_plan = reinterpret_cast<RenderPlan*>(ws + L.plan_off);
-    uint32_t* d_contrib = reinterpret_cast<uint32_t*>(ws + L.contrib_off);
     const int na = pp.plan.n_active;
-    bool use_thresh = false;
-    for (int i = 0; i < na; ++i) use_thresh |= pp.plan.ch[i].mode == kModeThresh;
-    uint32_t* d_thresh = reinterpret_cast<uint32_t*>(ws + L.thresh_off);
-    uint32_t* d_buckets = reinterpret_cast<uint32_t*>(ws + L.bucket_off);
-    std::vector<uint32_t> thr;
-    if (use_thresh) {                               // the code thresholds, on the host (exact)
-        thr.assign((size_t)na * 256, 0u);
-        for (int i = 0; i < na; ++i)
-            if (pp.plan.ch[i].mode == kModeThresh)
-                host_thresholds(pp.plan.ch[i], pixel_type, pp.plan.cd_start, pp.plan.cd_end, thr.data() + 256 * i);
-    }
-    const bool thr_with_plan = use_thresh && !(ptr_src && ptr_bytes);   // one staging launch for both
-    omr_status st = thr_with_plan
-                        ? stage_h2d2(ctx, d_plan, &pp.plan, pp.plan_bytes, d_thresh, thr.data(), thr.size() * 4)
-                        : stage_h2d2(ctx, d_plan, &pp.plan, pp.plan_bytes, const_cast<const void**>(d_plane_ptrs),
-                                     ptr_src, ptr_src ? ptr_bytes : 0);
-    if (st != OMR_OK) return st;
-    if (use_thresh && !thr_with_plan && (st = stage_h2d(ctx, d_thresh, thr.data(), thr.size() * 4))) return st;
     const int bpp = bytes_per_pixel(pixel_type);
     const int vec = aligned ? (bpp <= 2 ? 8 : 16 / bpp) : 1;
     const uint64_t cpr = (uint64_t)width / vec;
@@ -1352,20 +1423,16 @@ static omr_status enqueue_render(Ctx* ctx, PreparedPlan& pp, int32_t pixel_type,
     const uint64_t total = cpt * (uint64_t)n_tiles;
     // one chunk per thread for launches too small to fill the chip (launch_render_na); those
     // K2 instantiations (1..4 active channels) build the contribution tables in LDS themselves
+    // from the staged plan
     const bool small = bpp <= 2 && k2_small_launch(total, ctx->cu_count);
     const bool k2_builds_contrib = small && na >= 1 && na <= 4;
-    if (na > 0) {
-        if (!k2_builds_contrib) {
-            hipLaunchKernelGGL(k_build_contrib, dim3(na), dim3(256), 0, ctx->stream, d_plan, d_contrib,
-                               pixel_type == OMR_PIXELS_INT8 ? 1 : 0);
-            OMR_HIP(ctx, hipGetLastError());
-        }
-    }
-    if (use_thresh) {
-        hipLaunchKernelGGL(k_build_buckets, dim3(k2_launch_buckets(na) / 256, na), dim3(256), 0,
-                           ctx->stream, d_plan, d_thresh, d_buckets, k2_launch_buckets(na));
-        OMR_HIP(ctx, hipGetLastError());
-    }
+    PlanTables T;
+    const omr_status st = plan_tables(ctx, pp, pixel_type, static_cast<uint8_t*>(ctx->ws), L, !k2_builds_contrib,
+                                      const_cast<const void**>(d_plane_ptrs), ptr_src, ptr_bytes, T);
+    if (st != OMR_OK) return st;
+    RenderPlan* d_plan = T.plan;
+    uint32_t *d_contrib = T.contrib, *d_thresh = T.thresh, *d_buckets = T.buckets;
+    const bool use_thresh = T.use_thresh;
     if (total == 0) return OMR_OK;
     if (total >= (1ull << 31)) return fail(ctx, OMR_INVALID_ARGUMENT, "batch too large for one launch");
     K2Args a;
@@ -1381,7 +1448,7 @@ static omr_status enqueue_render(Ctx* ctx, PreparedPlan& pp, int32_t pixel_type,
     a.contrib = d_contrib;
     a.thresh = d_thresh;
     a.buckets = d_buckets;
-    a.bk_n = k2_launch_buckets(na);
+    a.bk_n = T.bk_n;
     a.use_thresh = use_thresh ? 1 : 0;
     a.out = d_out;
     a.status = d_status;
@@ -1508,16 +1575,14 @@ omr_status render_fused_stage(Ctx* ctx, FusedPlanBuf* fp, size_t ws_off, FusedRe
     PreparedPlan& pp = fp->pp;
     const RenderLayout& L = fp->L;
     uint8_t* ws = static_cast<uint8_t*>(ctx->ws) + ws_off;
-    RenderPlan* d_plan = reinterpret_cast<RenderPlan*>(ws + L.plan_off);
-    uint32_t* d_contrib = reinterpret_cast<uint32_t*>(ws + L.contrib_off);
     const int na = pp.plan.n_active;
-    omr_status st = stage_h2d(ctx, d_plan, &pp.plan, pp.plan_bytes);
+    // the staged plan is the unbiased one whatever bias_int16 says (the bias moves kernarg values
+    // only), so a fused call and a plain render of one setting share a plan-cache slot
+    PlanTables T;
+    const omr_status st = plan_tables(ctx, pp, fp->pixel_type, ws, L, build_contrib, nullptr, nullptr, 0, T);
     if (st) return st;
-    if (build_contrib) {
-        hipLaunchKernelGGL(k_build_contrib, dim3(na), dim3(256), 0, ctx->stream, d_plan, d_contrib,
-                           fp->pixel_type == OMR_PIXELS_INT8 ? 1 : 0);
-        OMR_HIP(ctx, hipGetLastError());
-    }
+    RenderPlan* d_plan = T.plan;
+    uint32_t* d_contrib = T.contrib;
     std::memset(&F, 0, sizeof(F));
     double tlo, thi;
     type_bounds(fp->pixel_type, tlo, thi);

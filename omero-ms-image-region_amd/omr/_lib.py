@@ -156,6 +156,7 @@ _SIGS = {
     "omr_ctx_get_stream": (_vp, [_vp]),
     "omr_ctx_set_semantics": (_i32, [_vp, ctypes.c_uint32]),
     "omr_ctx_get_semantics": (ctypes.c_uint32, [_vp]),
+    "omr_debug_plan_cache_stats": (_i32, [_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
     "omr_ctx_enable_kernel_timing": (_i32, [_vp, _i32]),
     "omr_ctx_kernel_timings": (_i32, [_vp, _vp, _vp, _i32]),
     "omr_pinned_alloc": (_vp, [_vp, _sz]),
