@@ -121,7 +121,8 @@ void*       omr_ctx_get_stream(omr_ctx* ctx);
  * every hot-kernel launch (K2 render, K3 projection, K4 JPEG) is bracketed by HIP events on
  * the stream it is launched on.  omr_ctx_kernel_timings synchronises, writes up to `cap`
  * per-launch durations in ms (launch order) and clears the record; returns the count.
- * kind_out (optional) receives 2 = render, 3 = projection, 4 = jpeg per entry.
+ * kind_out (optional) receives 2 = render, 3 = projection, 4 = jpeg per entry (10 = fused scaled
+ * render, 11 = ARGB scaler: omr_render_scaled_batch_device).
  */
 omr_status  omr_ctx_enable_kernel_timing(omr_ctx* ctx, int32_t enable);
 int32_t     omr_ctx_kernel_timings(omr_ctx* ctx, float* ms_out, int32_t* kind_out, int32_t cap);
@@ -430,6 +431,72 @@ omr_status omr_render_batch_strided_device(omr_ctx* ctx, const omr_quantum_def* 
                                            int32_t flip_h, int32_t flip_v,
                                            uint32_t* d_argb_out, int32_t* d_status);
 
+/* ---- scaled rendering: thumbnails and bird's-eye views (K10) ------------- */
+/*
+ * The scaling rule (the library's own; the reference snapshot has no thumbnail code): an exact
+ * area-weighted mean, rounded half up.  Source W x H, output tw x th with 1 <= tw <= W and
+ * 1 <= th <= H (downscale or identity; anything else is OMR_INVALID_ARGUMENT), W*H < 2^31.
+ * In units of 1/tw source column x covers [x*tw, (x+1)*tw) and output column i covers
+ * [i*W, (i+1)*W); wx[i][x] is the length of their overlap, an integer in 0..tw with
+ * sum_x wx[i][x] = W.  wy[j][y] is the same from H and th.  For each of the four bytes b of the
+ * packed ARGB, in non-negative integers with floor division:
+ *
+ *     out[j][i].b = (sum_y sum_x wy[j][y] * wx[i][x] * src[y][x].b + (W*H)/2) / (W*H)
+ *
+ * The alpha byte goes through the same formula (a render writes 0xFF, which stays 0xFF); the
+ * identity size returns the source.  Flips apply to the full-size render first, as in
+ * omr_render_*, which for this rule equals flipping the small image.  The sums are integers and
+ * order-free: two calls return identical bytes, and the result is exact at every size (sums are
+ * 64-bit once 255*W*H + W*H/2 no longer fits 32 bits, from about 4100 x 4100).
+ *
+ * omr_scale_argb_device: the rule on n ARGB images already in HBM, image k at
+ * d_src + k*src_image_stride_px with rows src_row_stride_px apart (0 = packed), into
+ * d_dst [n][dst_h][dst_w].  Asynchronous on the context stream.
+ */
+omr_status omr_scale_argb_device(omr_ctx* ctx, const uint32_t* d_src, int32_t n, int32_t src_w, int32_t src_h,
+                                 int64_t src_row_stride_px, int64_t src_image_stride_px, uint32_t* d_dst,
+                                 int32_t dst_w, int32_t dst_h);
+/*
+ * render_thumbnail / render_birds_eye_view: omr_render_batch_device followed by the rule, i.e.
+ * n_tiles whole planes rendered with one setting and handed back out_w x out_h each
+ * (d_argb_out: device [n_tiles][out_h][out_w]; one image is n_tiles = 1, which must be >= 1).
+ * d_status (optional, device int32[n_tiles]): per-image OMR_OK / OMR_QUANTIZATION.
+ * 8/16-bit integer pixels with 1..4 active channels go through one kernel that quantizes,
+ * composites and reduces (the full-size ARGB never reaches HBM) when width is a multiple of 8
+ * pixels and every plane and row starts on an 8-pixel boundary, i.e. 16-byte aligned for 16-bit and
+ * 8-byte aligned for 8-bit pixels (pointer-table planes: the caller's contract, as for
+ * omr_render_batch_device), out_w <= 1024 and width*out_w < 2^31.  Everything
+ * else, and every call of a context created with OMR_SCALE_FUSED=0 in the environment, renders
+ * full size into a context buffer and scales that: identical bytes either way.
+ * omr_ctx_kernel_timings reports kind 10 for the fused kernel and kind 11 for the ARGB scaler
+ * (behind a kind-2 render on the unfused route).  Asynchronous on the context stream.
+ */
+omr_status omr_render_scaled_batch_device(omr_ctx* ctx, const omr_quantum_def* qdef,
+                                          const omr_channel_binding* channels, int32_t size_c,
+                                          const void* const* d_plane_ptrs, int32_t n_tiles,
+                                          int64_t row_stride, int32_t pixel_type, int32_t big_endian,
+                                          int32_t width, int32_t height,
+                                          int32_t flip_h, int32_t flip_v,
+                                          uint32_t* d_argb_out, int32_t* d_status,
+                                          int32_t out_w, int32_t out_h);
+/* Same with the strided plane layout of omr_render_batch_strided_device. */
+omr_status omr_render_scaled_batch_strided_device(omr_ctx* ctx, const omr_quantum_def* qdef,
+                                                  const omr_channel_binding* channels, int32_t size_c,
+                                                  const void* d_base, int64_t tile_stride_bytes,
+                                                  int64_t channel_stride_bytes, int32_t n_tiles,
+                                                  int64_t row_stride, int32_t pixel_type, int32_t big_endian,
+                                                  int32_t width, int32_t height,
+                                                  int32_t flip_h, int32_t flip_v,
+                                                  uint32_t* d_argb_out, int32_t* d_status,
+                                                  int32_t out_w, int32_t out_h);
+/*
+ * Thumbnail size by OMERO's longest-side rule, host only.  big = max(size_x, size_y): when
+ * big <= longest_side the image keeps its own size (no upscaling, unlike OMERO); otherwise the
+ * long side becomes longest_side and the short side max(1, short*longest_side / big) (int64
+ * floor division).  longest_side < 1 or a non-positive size is OMR_INVALID_ARGUMENT.
+ */
+omr_status omr_thumbnail_size(int32_t size_x, int32_t size_y, int32_t longest_side, int32_t* out_w, int32_t* out_h);
+
 /*
  * Standalone output flip of an already-rendered ARGB buffer on the device
  * (ImageRegionRequestHandler.flip, :616-642).  src and dest must not alias.
@@ -554,6 +621,20 @@ omr_status omr_render_jpeg_batch_device(omr_ctx* ctx, const omr_quantum_def* qde
                                         int32_t flip_h, int32_t flip_v, float quality, uint8_t* d_out,
                                         size_t out_cap, uint64_t* d_offsets, uint32_t* d_lengths,
                                         int32_t* d_status);
+/*
+ * Thumbnails as JPEG files: omr_render_scaled_batch_device into a context buffer, then
+ * omr_encode_jpeg_batch_device's pipeline on the n_tiles out_w x out_h images (out_w, out_h <=
+ * 4096).  Files, offsets, lengths and statuses exactly as omr_render_jpeg_batch_device.
+ * Asynchronous on the context stream.
+ */
+omr_status omr_render_thumbnail_jpeg_batch_device(omr_ctx* ctx, const omr_quantum_def* qdef,
+                                                  const omr_channel_binding* channels, int32_t size_c,
+                                                  const void* const* d_plane_ptrs, int32_t n_tiles,
+                                                  int64_t row_stride, int32_t pixel_type, int32_t big_endian,
+                                                  int32_t width, int32_t height, int32_t flip_h, int32_t flip_v,
+                                                  int32_t out_w, int32_t out_h, float quality, uint8_t* d_out,
+                                                  size_t out_cap, uint64_t* d_offsets, uint32_t* d_lengths,
+                                                  int32_t* d_status);
 /* Same, host output: files packed in out (cap bytes), offsets/lengths host arrays; synchronous. */
 omr_status omr_encode_jpeg_batch(omr_ctx* ctx, const uint32_t* d_argb, int64_t tile_stride_px,
                                  int32_t n_tiles, int32_t width, int32_t height, float quality,

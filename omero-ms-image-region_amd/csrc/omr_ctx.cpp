@@ -186,6 +186,7 @@ omr_status omr_ctx_create(int32_t device_ordinal, omr_ctx** out) {
     if (const char* v = std::getenv("OMR_PNG_SINGLE_BATCHED")) c->png_single_batched = std::atoi(v) != 0;
     if (const char* v = std::getenv("OMR_F1_F32")) c->f1_f32 = std::atoi(v) != 0;
     if (const char* v = std::getenv("OMR_PLAN_CACHE")) c->plan_cache = std::atoi(v) != 0;
+    if (const char* v = std::getenv("OMR_SCALE_FUSED")) c->scale_fused = std::atoi(v) != 0;
     {
         const char* v = std::getenv("OMR_PLAN_CACHE_SLOTS");
         c->plan_slots.resize((size_t)plan_cache_slot_count(v ? std::atoll(v) : 0));
@@ -303,7 +304,9 @@ void* omr_ctx_get_stream(omr_ctx* c) { return c ? static_cast<void*>(c->stream) 
 
 void* omr_pinned_alloc(omr_ctx* c, size_t bytes) {
     void* p = nullptr;
-    if (!c || hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) return nullptr;
+    // a live context always has a stream (omr_ctx_create); anything else is not one, and handing it
+    // staging would let the caller go on to render with it
+    if (!c || !c->stream || hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) return nullptr;
     return p;
 }
 

@@ -160,6 +160,9 @@ struct Ctx {
     uint8_t* d_plan_slots = nullptr;
     size_t plan_slot_bytes = 0;
     uint64_t plan_clock = 0, plan_hits = 0, plan_misses = 0;
+    // scaled renders through the fused kernel where it applies (omr_scale.hip, K10); env
+    // OMR_SCALE_FUSED=0: always K2 into aux, then k_scale_argb (the A/B and test reference route)
+    bool scale_fused = true;
     // kernel timing (omr_ctx_enable_kernel_timing)
     bool timing = false;
     struct Timed { hipEvent_t start, stop; int kind; };
@@ -260,6 +263,16 @@ omr_status histogram_plane_uploaded(Ctx* c, const void* d_plane, uint8_t* scratc
                                     int32_t big_endian, int32_t width, int32_t height, const omr_region* region,
                                     int32_t range_mode, double lo, double hi, int32_t bin_count,
                                     uint32_t* counts_out, omr_histogram_info* info_out, omr_plane_stats* stats_out);
+
+// K10 (omr_scale.hip): the scaled render behind omr_render_scaled_batch_*_device (d_base: the
+// strided form, else the pointer table d_ptrs).  aux != nullptr (the thumbnail JPEG path): the
+// [n][th][tw] ARGB goes to the start of ctx->aux and the per-image statuses to aux + status_off,
+// both inside the first `total` bytes, which the call itself makes room for.
+struct ScaledAux { size_t status_off, total; };
+omr_status render_scaled(Ctx* ctx, const omr_quantum_def* qdef, const omr_channel_binding* channels, int32_t size_c,
+                         const void* d_base, int64_t tile_stride, int64_t chan_stride, const void* const* d_ptrs,
+                         int32_t n, int64_t row_stride, int32_t pt, int32_t be, int32_t W, int32_t H, int32_t fh,
+                         int32_t fv, uint32_t* d_out, int32_t* d_status, int32_t tw, int32_t th, const ScaledAux* aux);
 
 #define OMR_HIP(ctx, expr)                                         \
     do {                                                            \

@@ -2255,6 +2255,38 @@ omr_status omr_render_jpeg_batch_device(omr_ctx* ctx, const omr_quantum_def* qde
                                   d_offsets, d_lengths, d_status);
 }
 
+omr_status omr_render_thumbnail_jpeg_batch_device(omr_ctx* ctx, const omr_quantum_def* qdef,
+                                                  const omr_channel_binding* channels, int32_t size_c,
+                                                  const void* const* d_plane_ptrs, int32_t n_tiles,
+                                                  int64_t row_stride, int32_t pixel_type, int32_t big_endian,
+                                                  int32_t width, int32_t height, int32_t flip_h, int32_t flip_v,
+                                                  int32_t out_w, int32_t out_h, float quality, uint8_t* d_out,
+                                                  size_t out_cap, uint64_t* d_offsets, uint32_t* d_lengths,
+                                                  int32_t* d_status) {
+    using namespace omr;
+    if (!ctx) return OMR_INVALID_ARGUMENT;
+    if (!d_plane_ptrs) return fail(ctx, OMR_INVALID_ARGUMENT, "null plane table");
+    if (n_tiles <= 0 || n_tiles > (1 << 20)) return fail(ctx, OMR_INVALID_ARGUMENT, "JPEG batch: n_tiles out of range");
+    if (out_w <= 0 || out_h <= 0 || out_w > kJpegBatchMaxDim || out_h > kJpegBatchMaxDim)
+        return fail(ctx, OMR_INVALID_ARGUMENT, "JPEG batch: tile dimensions must be 1..4096");
+    if (!d_out || !d_offsets || !d_lengths) return fail(ctx, OMR_INVALID_ARGUMENT, "null batch output");
+    // the small ARGB and the render's per-image statuses at the front of the aux buffer, then the
+    // batched encoder on them (B5 merges the statuses), as the unfused render -> JPEG path
+    const size_t argb_bytes = align_up((size_t)n_tiles * out_w * out_h * 4, 256);
+    const ScaledAux aux{argb_bytes, argb_bytes + align_up((size_t)n_tiles * 4, 256)};
+    omr_status st = render_scaled(ctx, qdef, channels, size_c, nullptr, 0, 0, d_plane_ptrs, n_tiles, row_stride,
+                                  pixel_type, big_endian, width, height, flip_h, flip_v, nullptr, nullptr, out_w, out_h,
+                                  &aux);
+    if (st) return st;
+    const uint32_t* argb = static_cast<const uint32_t*>(ctx->aux);
+    const int32_t* rstat = reinterpret_cast<const int32_t*>(static_cast<const uint8_t*>(ctx->aux) + aux.status_off);
+    const JpegBatchLayout L = jpeg_batch_layout(out_w, out_h, n_tiles, 0);
+    st = ensure_workspace(ctx, L.total);
+    if (st) return st;
+    return encode_jpeg_batch_ws_rstat(ctx, argb, (int64_t)out_w * out_h, n_tiles, out_w, out_h, quality, d_out, out_cap,
+                                      d_offsets, d_lengths, d_status, L, rstat);
+}
+
 omr_status omr_encode_jpeg_batch_device(omr_ctx* ctx, const uint32_t* d_argb, int64_t tile_stride_px,
                                         int32_t n_tiles, int32_t width, int32_t height, float quality,
                                         uint8_t* d_out, size_t out_cap, uint64_t* d_offsets,

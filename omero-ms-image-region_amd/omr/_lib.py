@@ -202,6 +202,14 @@ _SIGS = {
                                        _i32, _i32, _vp, _vp]),
     "omr_render_batch_strided_device": (_i32, [_vp, _QD, _CB, _i32, _vp, _i64, _i64, _i32, _i64, _i32, _i32,
                                                _i32, _i32, _i32, _i32, _vp, _vp]),
+    "omr_scale_argb_device": (_i32, [_vp, _vp, _i32, _i32, _i32, _i64, _i64, _vp, _i32, _i32]),
+    "omr_render_scaled_batch_device": (_i32, [_vp, _QD, _CB, _i32, _vp, _i32, _i64, _i32, _i32, _i32, _i32,
+                                              _i32, _i32, _vp, _vp, _i32, _i32]),
+    "omr_render_scaled_batch_strided_device": (_i32, [_vp, _QD, _CB, _i32, _vp, _i64, _i64, _i32, _i64, _i32, _i32,
+                                                      _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32]),
+    "omr_render_thumbnail_jpeg_batch_device": (_i32, [_vp, _QD, _CB, _i32, _vp, _i32, _i64, _i32, _i32, _i32, _i32,
+                                                      _i32, _i32, _i32, _i32, _f32, _vp, _sz, _vp, _vp, _vp]),
+    "omr_thumbnail_size": (_i32, [_i32, _i32, _i32, ctypes.POINTER(_i32), ctypes.POINTER(_i32)]),
     "omr_flip_argb_device": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32]),
     "omr_flip_mask_device": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32]),
     "omr_project_stack": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,

@@ -73,6 +73,13 @@ def make_qdef(model, cd_start=0, cd_end=255, bit_resolution=255):
     return q
 
 
+def thumbnail_size(size_x, size_y, longest_side=96):
+    """(width, height) of a thumbnail by the longest-side rule (omr_thumbnail_size): no upscaling."""
+    w, h = ctypes.c_int32(0), ctypes.c_int32(0)
+    check(lib.omr_thumbnail_size(int(size_x), int(size_y), int(longest_side), ctypes.byref(w), ctypes.byref(h)))
+    return w.value, h.value
+
+
 class Context:
     """One omr_ctx.  Its launches run on the context's own non-blocking HIP stream.
 
@@ -155,7 +162,7 @@ class Context:
 
     def kernel_timings(self, cap=1 << 16):
         """[(ms, kind)] of the timed hot-kernel launches since the last call (kind 2 render,
-        3 projection, 4 jpeg); synchronises the stream."""
+        3 projection, 4 jpeg, 10 fused scaled render, 11 ARGB scaler); synchronises the stream."""
         ms = np.zeros(cap, np.float32)
         kind = np.zeros(cap, np.int32)
         n = lib.omr_ctx_kernel_timings(self.h, ms.ctypes.data, kind.ctypes.data, cap)
@@ -213,6 +220,50 @@ class Context:
                                                   height, int(flip_h), int(flip_v), _ptr(out),
                                                   _ptr(status)), self.h)
         return out
+
+    # ---- scaled render: thumbnails, bird's-eye views (K10) ---------------------------------
+    def scale_argb_device(self, src, n, src_w, src_h, dst, dst_w, dst_h, row_stride=0, image_stride=0):
+        """The scaling rule (exact area-weighted mean, rounded half up; omr.h) on n device ARGB
+        images [n][src_h][row_stride] -> dst [n][dst_h][dst_w]."""
+        check(lib.omr_scale_argb_device(self.h, _ptr(src), n, src_w, src_h, row_stride, image_stride, _ptr(dst),
+                                        dst_w, dst_h), self.h)
+        return dst
+
+    def render_scaled_batch_device(self, qdef, channels, d_plane_ptrs, n_tiles, pixel_type, width, height,
+                                   out, out_w, out_h, status=None, big_endian=False, flip_h=False, flip_v=False,
+                                   row_stride=0, bindings=None):
+        """render_batch_device at out_w x out_h: out is [n_tiles][out_h][out_w]."""
+        arr, keep = make_bindings(channels) if bindings is None else bindings
+        check(lib.omr_render_scaled_batch_device(self.h, ctypes.byref(qdef), arr, len(channels),
+                                                 _ptr(d_plane_ptrs), n_tiles, row_stride, pixel_type,
+                                                 int(big_endian), width, height, int(flip_h), int(flip_v),
+                                                 _ptr(out), _ptr(status), out_w, out_h), self.h)
+        return out
+
+    def render_scaled_batch_strided_device(self, qdef, channels, d_base, tile_stride, channel_stride, n_tiles,
+                                           pixel_type, width, height, out, out_w, out_h, status=None,
+                                           big_endian=False, flip_h=False, flip_v=False, row_stride=0,
+                                           bindings=None):
+        """render_batch_strided_device at out_w x out_h."""
+        arr, keep = make_bindings(channels) if bindings is None else bindings
+        check(lib.omr_render_scaled_batch_strided_device(self.h, ctypes.byref(qdef), arr, len(channels),
+                                                         _ptr(d_base), tile_stride, channel_stride, n_tiles,
+                                                         row_stride, pixel_type, int(big_endian), width, height,
+                                                         int(flip_h), int(flip_v), _ptr(out), _ptr(status),
+                                                         out_w, out_h), self.h)
+        return out
+
+    def render_thumbnail_jpeg_batch_device(self, qdef, channels, d_plane_ptrs, n_tiles, pixel_type, width, height,
+                                           out_w, out_h, quality, d_out, d_offsets, d_lengths, d_status=None,
+                                           big_endian=False, flip_h=False, flip_v=False, row_stride=0,
+                                           bindings=None):
+        """Scaled render + JPEG of n_tiles planes sets: files packed in d_out, as
+        render_jpeg_batch_device."""
+        arr, keep = make_bindings(channels) if bindings is None else bindings
+        check(lib.omr_render_thumbnail_jpeg_batch_device(
+            self.h, ctypes.byref(qdef), arr, len(channels), _ptr(d_plane_ptrs), n_tiles, row_stride, pixel_type,
+            int(big_endian), width, height, int(flip_h), int(flip_v), out_w, out_h, float(quality), _ptr(d_out),
+            d_out.numel(), _ptr(d_offsets), _ptr(d_lengths), _ptr(d_status)), self.h)
 
     def render_pixel_buffer_tiles(self, qdef, channels, pixbuf, requests, width, height, out=None,
                                   flip_h=False, flip_v=False, bindings=None):

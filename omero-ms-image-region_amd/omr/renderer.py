@@ -165,6 +165,26 @@ class Renderer:
                                                  self.pixel_type, width, height, out, big_endian,
                                                  flip_h, flip_v, row_stride)
 
+    def renderThumbnail(self, planes, longest_side=96, big_endian=True, flip_h=False, flip_v=False):
+        """render_thumbnail / render_birds_eye_view: the whole size_x x size_y plane rendered with
+        the current settings and scaled on the device to omr.thumbnail_size(size_x, size_y,
+        longest_side) (exact area-weighted mean, omr.h).  planes[c]: host array or device tensor of
+        channel c (None for an inactive channel).  Returns the small ARGB, numpy uint32 [h][w]."""
+        import torch
+        from .context import thumbnail_size
+        w, h = thumbnail_size(self.size_x, self.size_y, longest_side)
+        dev = torch.device("cuda", self.ctx.device)
+        ptrs, keep = self.ctx._device_planes([p for p in planes if p is not None])
+        it = iter(ptrs)
+        table = [int(next(it) or 0) if p is not None else 0 for p in planes]
+        d_ptrs = torch.tensor(table + [0] * (self.size_c - len(table)), dtype=torch.int64, device=dev)
+        out = torch.empty((h, w), dtype=torch.int32, device=dev)
+        self.ctx.render_scaled_batch_device(self.qdef(), self.rdef.channels, d_ptrs, 1, self.pixel_type,
+                                            self.size_x, self.size_y, out, w, h, big_endian=big_endian,
+                                            flip_h=flip_h, flip_v=flip_v)
+        self.ctx.synchronize()
+        return out.cpu().numpy().view(np.uint32)
+
 
 def flip(ctx, src, size_x, size_y, flip_h, flip_v):
     """ImageRegionRequestHandler.flip on a device ARGB tensor: returns src when not flipping,
