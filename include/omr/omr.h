@@ -122,7 +122,8 @@ void*       omr_ctx_get_stream(omr_ctx* ctx);
  * the stream it is launched on.  omr_ctx_kernel_timings synchronises, writes up to `cap`
  * per-launch durations in ms (launch order) and clears the record; returns the count.
  * kind_out (optional) receives 2 = render, 3 = projection, 4 = jpeg per entry (10 = fused scaled
- * render, 11 = ARGB scaler: omr_render_scaled_batch_device).
+ * render, 11 = ARGB scaler: omr_render_scaled_batch_device; 12 = pyramid levels:
+ * omr_pyramid_build_device).
  */
 omr_status  omr_ctx_enable_kernel_timing(omr_ctx* ctx, int32_t enable);
 int32_t     omr_ctx_kernel_timings(omr_ctx* ctx, float* ms_out, int32_t* kind_out, int32_t cap);
@@ -288,6 +289,99 @@ omr_status omr_pixel_buffer_histogram(omr_ctx* ctx, const omr_pixel_buffer* pb, 
                                       int32_t t, const omr_region* region, int32_t range_mode,
                                       double lo, double hi, int32_t bin_count, uint32_t* counts_out,
                                       omr_histogram_info* info_out, omr_plane_stats* stats_out);
+
+/* ---- resolution pyramids (K11) ---------------------------------------------- */
+/*
+ * The levels behind tile=res,x,y[,w,h] (getResolutionLevels / getResolutionDescriptions,
+ * ImageRegionRequestHandler.java:446-454, :792-795, :840-853).  The reference snapshot has no
+ * pyramid writer (OMERO's PixelsService.makePyramid is not vendored), so the rule below is the
+ * library's own, as for K9 and K10.
+ *
+ * Level sizes.  Level k (0 = full size) is floor(W / 2^k) x floor(H / 2^k); n_levels counts
+ * level 0.  A valid pyramid has 1 <= n_levels <= OMR_PYRAMID_MAX_LEVELS and
+ * n_levels <= 1 + floor(log2(min(W, H))): every level then has both sides >= 1 and every 2x2 box
+ * lies inside its source.  A trailing odd row or column of a level contributes nothing to the next.
+ *
+ * Downsampling.  Both rules cascade: level k is made from the stored level k-1.
+ *   OMR_PYRAMID_SUBSAMPLE  L_k[j][i] = L_{k-1}[2j][2i], i.e. level-0 pixel (i*2^k, j*2^k); the
+ *                          bytes are copied verbatim (NaN payloads survive).
+ *   OMR_PYRAMID_MEAN       with a, b, c, d = L_{k-1}[2j][2i], [2j][2i+1], [2j+1][2i], [2j+1][2i+1]:
+ *                          8-, 16- and 32-bit integers, signed and unsigned:
+ *                              floor((a + b + c + d + 2) / 4) in int64 (half rounds towards
+ *                              +infinity, an arithmetic shift for negatives; always fits the type);
+ *                          float:  (float)((((double)a + (double)b) + ((double)c + (double)d)) * 0.25);
+ *                          double: ((a + b) + (c + d)) * 0.25;
+ *                          one IEEE rounding per operation (no fused multiply-add); NaN propagates.
+ * Levels keep the byte order of level 0; output planes are packed (row stride = level width).
+ */
+enum { OMR_PYRAMID_SUBSAMPLE = 0, OMR_PYRAMID_MEAN = 1 };
+#define OMR_PYRAMID_MAX_LEVELS 16
+#define OMR_PYRAMID_DEFAULT_MIN_SIDE 256   /* OMERO's tile side */
+/* The smallest n >= 1 with max(size_x >> (n-1), size_y >> (n-1)) <= min_side, capped by the bounds
+ * above; negative (-OMR_INVALID_ARGUMENT) for min_side < 1 or a non-positive size.  Host only. */
+int32_t    omr_pyramid_level_count(int32_t size_x, int32_t size_y, int32_t min_side);
+/* (w, h) pairs of levels 0..n_levels-1 into sizes_out[2*n_levels], largest first: the order of
+ * getResolutionDescriptions and of omr_get_region_def's level_sizes.  OMR_INVALID_ARGUMENT for an
+ * n_levels outside the bounds above.  Host only. */
+omr_status omr_pyramid_level_sizes(int32_t size_x, int32_t size_y, int32_t n_levels, int32_t* sizes_out);
+/*
+ * K11: levels 1..n_levels-1 of n_planes (1..32) planes already in HBM.  d_planes is a HOST array
+ * of n_planes device pointers (rows row_stride_px pixels apart, 0 = width); d_levels_out is a HOST
+ * array of n_levels-1 device bases: plane p of level k goes to d_levels_out[k-1] + p * w_k*h_k*bpp.
+ * All eight pixel types.  Level 0 is read once: one launch writes up to four levels (three for 32-
+ * and 64-bit pixels) from registers and further levels come from re-running the kernel on the last
+ * level written; omr_ctx_kernel_timings reports kind 12 per launch.  No atomics: two calls give
+ * identical bytes.  Planes, strides or widths off the 16-byte grid take a per-pixel form of the
+ * same rule; no shape is refused.  OMR_INVALID_ARGUMENT, decided before any launch (the context
+ * stays usable): a NULL pointer, an unknown type or rule, n_planes outside 1..32, n_levels outside
+ * the bounds above, 0 < row_stride_px < width, width*height >= 2^31, a plane or level pointer that
+ * is not a multiple of the pixel size.  n_levels == 1 is OMR_OK and launches nothing.
+ * Asynchronous on the context stream.
+ */
+omr_status omr_pyramid_build_device(omr_ctx* ctx, const void* const* d_planes, int32_t n_planes,
+                                    int32_t pixel_type, int32_t big_endian, int32_t width, int32_t height,
+                                    int64_t row_stride_px, int32_t rule, int32_t n_levels,
+                                    void* const* d_levels_out);
+/*
+ * Pyramid sidecar file of a ROMIO pixel buffer.  A 64-byte little-endian header:
+ *     bytes  0..7   magic "OMRPYR1\0"
+ *     uint32 version (1), rule (OMR_PYRAMID_*), pixel_type, n_levels            (bytes  8..23)
+ *     int32  size_x, size_y, size_z, size_c, size_t of level 0                  (bytes 24..43)
+ *     zero padding                                                              (bytes 44..63)
+ * then levels 1..n_levels-1, each in ROMIO layout (big-endian planes in XYZCT order at the
+ * level's size), each starting at the next multiple of 4096 bytes; gaps are zero and the file
+ * ends with the last level's last byte.  The same input and rule give identical bytes.
+ *
+ * build_pyramid: reads pb's planes, runs K11 on groups of up to 32 planes (the next group's copy
+ * overlaps the current group's kernel), copies the levels back and writes sidecar_path + ".tmp",
+ * then renames it to sidecar_path.  n_levels <= 0: omr_pyramid_level_count(size_x, size_y, 256).
+ * Synchronous.  An I/O failure is OMR_INTERNAL with the errno text in omr_last_error.  It does not
+ * attach the file.
+ */
+omr_status omr_pixel_buffer_build_pyramid(omr_ctx* ctx, const omr_pixel_buffer* pb, int32_t rule,
+                                          int32_t n_levels, const char* sidecar_path);
+/* Attach a sidecar (host only: no context, no GPU): magic, version, pixel type, the five
+ * dimensions, the n_levels bounds and the file length are validated.  OMR_NOT_FOUND for a missing
+ * file, OMR_INVALID_ARGUMENT for anything else; a second attach replaces the first.  Not to be
+ * called while another thread uses pb (views taken before stay valid). */
+omr_status omr_pixel_buffer_attach_pyramid(omr_pixel_buffer* pb, const char* sidecar_path);
+/* getResolutionLevels: n_levels of the attached pyramid, 1 without one (0 for NULL). */
+int32_t    omr_pixel_buffer_resolution_levels(const omr_pixel_buffer* pb);
+/* getResolutionDescriptions: up to cap_pairs (w, h) pairs, largest first; returns the level count
+ * (negative -OMR_INVALID_ARGUMENT for a NULL argument). */
+int32_t    omr_pixel_buffer_resolution_descriptions(const omr_pixel_buffer* pb, int32_t* sizes_out,
+                                                    int32_t cap_pairs);
+/*
+ * A resolution level as a pixel buffer of its own.  resolution is the request's index (0 = full
+ * size), i.e. the index into the descriptions (omr_resolution_level gives the omeis number).  The
+ * view has the level's size_x / size_y, the parent's z, c, t and pixel type and its own identity
+ * for the batcher's caches, works with every call that takes an omr_pixel_buffer (get_tile,
+ * plane_offset, omr_render_pixel_buffer_tiles, histogram, batcher and pool jobs, projections) and
+ * is closed with omr_pixel_buffer_close; views and parent share the file mappings by reference
+ * count, so the closing order does not matter.  A view itself reports one level.
+ * OMR_INVALID_ARGUMENT for a resolution outside 0..n_levels-1.
+ */
+omr_status omr_pixel_buffer_level(const omr_pixel_buffer* pb, int32_t resolution, omr_pixel_buffer** view);
 
 /* ---- request batching ------------------------------ */
 /*

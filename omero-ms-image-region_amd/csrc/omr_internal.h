@@ -274,6 +274,9 @@ omr_status render_scaled(Ctx* ctx, const omr_quantum_def* qdef, const omr_channe
                          int32_t n, int64_t row_stride, int32_t pt, int32_t be, int32_t W, int32_t H, int32_t fh,
                          int32_t fv, uint32_t* d_out, int32_t* d_status, int32_t tw, int32_t th, const ScaledAux* aux);
 
+// K11 (omr_pyramid.hip): 1 <= n_levels <= min(OMR_PYRAMID_MAX_LEVELS, 1 + floor(log2(min(w, h)))).
+bool pyramid_levels_valid(int64_t w, int64_t h, int64_t n_levels);
+
 #define OMR_HIP(ctx, expr)                                         \
     do {                                                            \
         hipError_t _e = (expr);                                     \

@@ -12,6 +12,10 @@
 // threads copy each group of tiles into a pinned slot that is then sent in one copy.  K1+K2
 // render on the context's stream and the ARGB comes back (or stays in HBM for a JPEG batch);
 // two slots are in flight so reads, PCIe copies and kernels overlap.
+//
+// Resolution levels: omr_pixel_buffer_build_pyramid streams the planes through the same staging
+// into K11 (omr_pyramid.hip) and writes levels 1.. to a sidecar file; once attached, each level is
+// served as a pixel buffer of its own (omr_pixel_buffer_level) by everything above.
 #include "omr_internal.h"
 
 #include <fcntl.h>
@@ -25,24 +29,50 @@
 #include <cerrno>
 #include <condition_variable>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <thread>
 
-struct omr_pixel_buffer {
+// One open file and its read-only mapping, shared by reference count between a pixel buffer and
+// the level views taken from it (omr_pixel_buffer_level), so their closing order does not matter.
+struct PixFile {
     int fd = -1;
-    int32_t sx = 0, sy = 0, sz = 0, sc = 0, st = 0, pt = 0, bpp = 0;
-    int64_t row_bytes = 0, plane_bytes = 0, total = 0;
+    int64_t len = 0;     // bytes mapped
     // Read-only shared mapping of the file, only for files up to kMaxRegisterBytes: once
     // registered with HIP (hipHostRegister, first pipelined render) the copy engines read tile
-    // rows straight from it — no CPU copy at all.  Registration pins every page of the mapping
-    // while the buffer is open, hence the cap; larger files (and getTile) use pread, which turns a
+    // rows straight from it -- no CPU copy at all.  Registration pins every page of the mapping
+    // while the file is open, hence the cap; larger files (and getTile) use pread, which turns a
     // file truncated underneath us into an I/O error (the reference's IOException) rather than
     // a SIGBUS from a mapped read.  Requirement: a registered file is not truncated while open
     // (its pages stay pinned; the DMA then reads the old contents).
     const uint8_t* map = nullptr;
     std::mutex reg_m;
     int reg_state = 0;   // 0 untried, 1 registered, -1 not registrable (pread/memcpy path)
+    ~PixFile() {
+        if (map) {
+            if (reg_state == 1) (void)hipHostUnregister(const_cast<uint8_t*>(map));
+            ::munmap(const_cast<uint8_t*>(map), (size_t)len);
+        }
+        if (fd >= 0) ::close(fd);
+    }
+};
+
+// An attached pyramid sidecar (omr.h): levels 1..n_levels-1, each a ROMIO-layout run of planes.
+struct PixPyramid {
+    std::shared_ptr<PixFile> f;
+    int32_t n_levels = 1, rule = 0;
+    std::vector<int64_t> off;   // [n_levels]: file offset of level k (k >= 1)
+};
+
+struct omr_pixel_buffer {
+    std::shared_ptr<PixFile> f;
+    int fd = -1;                    // f->fd
+    const uint8_t* map = nullptr;   // f->map
+    int64_t base = 0;               // file offset of plane (0, 0, 0): 0, or a level's offset in the sidecar
+    int32_t sx = 0, sy = 0, sz = 0, sc = 0, st = 0, pt = 0, bpp = 0;
+    int64_t row_bytes = 0, plane_bytes = 0, total = 0;
     uint64_t serial = 0; // process-unique id (a closed buffer's address may be reused by the next open)
+    std::shared_ptr<const PixPyramid> pyr;   // omr_pixel_buffer_attach_pyramid
 };
 
 static std::atomic<uint64_t> g_pixbuf_serial{0};
@@ -241,13 +271,13 @@ static bool tile_in_bounds(const omr_pixel_buffer* pb, int32_t z, int32_t c, int
 }
 
 static int64_t plane_offset(const omr_pixel_buffer* pb, int32_t z, int32_t c, int32_t t) {
-    return (((int64_t)t * pb->sc + c) * pb->sz + z) * pb->plane_bytes;
+    return pb->base + (((int64_t)t * pb->sc + c) * pb->sz + z) * pb->plane_bytes;
 }
 
-// Files above this size are never mapped or registered (see omr_pixel_buffer::map).
+// Files above this size are never mapped or registered (see PixFile::map).
 constexpr int64_t kMaxRegisterBytes = (int64_t)1 << 30;
 
-// Rows y..y+h of the plane, columns x..x+w, packed into dst (pread: see omr_pixel_buffer::map).
+// Rows y..y+h of the plane, columns x..x+w, packed into dst (pread: see PixFile::map).
 static bool read_tile(const omr_pixel_buffer* pb, int32_t z, int32_t c, int32_t t, int32_t x, int32_t y, int32_t w,
                       int32_t h, uint8_t* dst) {
     const int64_t base = plane_offset(pb, z, c, t) + (int64_t)y * pb->row_bytes + (int64_t)x * pb->bpp;
@@ -261,15 +291,59 @@ static bool read_tile(const omr_pixel_buffer* pb, int32_t z, int32_t c, int32_t 
 // Register the file mapping with HIP once (portable, read-only): from then on tile rows are
 // DMA'd from the page cache.  Returns false when the driver refuses (the pread path stays).
 static bool ensure_registered(omr_pixel_buffer* pb) {
-    if (!pb->map) return false;
-    std::lock_guard<std::mutex> g(pb->reg_m);
-    if (pb->reg_state == 0) {
-        const hipError_t e = hipHostRegister(const_cast<uint8_t*>(pb->map), (size_t)pb->total,
+    PixFile* f = pb->f.get();
+    if (!f->map) return false;
+    std::lock_guard<std::mutex> g(f->reg_m);
+    if (f->reg_state == 0) {
+        const hipError_t e = hipHostRegister(const_cast<uint8_t*>(f->map), (size_t)f->len,
                                              hipHostRegisterPortable | hipHostRegisterReadOnly);
-        pb->reg_state = e == hipSuccess ? 1 : -1;
+        f->reg_state = e == hipSuccess ? 1 : -1;
         if (e != hipSuccess) (void)hipGetLastError();
     }
-    return pb->reg_state == 1;
+    return f->reg_state == 1;
+}
+
+// Map the first `len` bytes of an open file read-only (small files only, see PixFile::map).
+static void map_file(PixFile* f, int64_t len) {
+    if (len <= 0 || len > kMaxRegisterBytes) return;
+    void* m = ::mmap(nullptr, (size_t)len, PROT_READ, MAP_SHARED, f->fd, 0);
+    if (m != MAP_FAILED) {
+        f->map = static_cast<const uint8_t*>(m);
+        f->len = len;
+    }
+}
+
+// pwrite until done.
+static bool write_full(int fd, const void* src, size_t n, int64_t off) {
+    const uint8_t* s = static_cast<const uint8_t*>(src);
+    while (n) {
+        const ssize_t r = ::pwrite(fd, s, n, (off_t)off);
+        if (r < 0) {
+            if (errno == EINTR) continue;
+            return false;
+        }
+        s += r;
+        n -= (size_t)r;
+        off += r;
+    }
+    return true;
+}
+
+// The pyramid sidecar (omr.h): 64-byte header, then levels 1.. on 4096-byte boundaries.
+constexpr size_t kPyrHeaderBytes = 64;
+constexpr int64_t kPyrLevelAlign = 4096;
+constexpr uint32_t kPyrVersion = 1;
+static const char kPyrMagic[8] = {'O', 'M', 'R', 'P', 'Y', 'R', '1', '\0'};
+
+// off[k]: file offset of level k >= 1 of pb's sidecar with n_levels levels; len: the file's length.
+static void pyramid_layout(const omr_pixel_buffer* pb, int32_t n_levels, std::vector<int64_t>& off, int64_t& len) {
+    off.assign((size_t)n_levels, 0);
+    len = (int64_t)kPyrHeaderBytes;
+    const int64_t planes = (int64_t)pb->sz * pb->sc * pb->st;
+    for (int32_t k = 1; k < n_levels; ++k) {
+        off[k] = (len + kPyrLevelAlign - 1) / kPyrLevelAlign * kPyrLevelAlign;
+        len = off[k] + (int64_t)(pb->sx >> k) * (pb->sy >> k) * pb->bpp * planes;
+    }
 }
 
 }  // namespace omr
@@ -294,7 +368,8 @@ omr_status omr_pixel_buffer_open(const char* path, int32_t size_x, int32_t size_
     if (fd < 0) return OMR_NOT_FOUND;
     auto* pb = new omr_pixel_buffer;
     pb->serial = ++g_pixbuf_serial;
-    pb->fd = fd;
+    pb->f = std::make_shared<PixFile>();
+    pb->f->fd = pb->fd = fd;
     pb->sx = size_x; pb->sy = size_y; pb->sz = size_z; pb->sc = size_c; pb->st = size_t_;
     pb->pt = pixel_type;
     pb->bpp = bpp;
@@ -303,31 +378,22 @@ omr_status omr_pixel_buffer_open(const char* path, int32_t size_x, int32_t size_
     pb->total = total;
     struct stat sb;
     if (::fstat(fd, &sb) != 0 || (int64_t)sb.st_size < pb->total) {   // RomioPixelBuffer size check
-        ::close(fd);
-        delete pb;
+        delete pb;                                                     // (closes the file)
         return OMR_INVALID_ARGUMENT;
     }
-    if (pb->total <= kMaxRegisterBytes) {
-        void* m = ::mmap(nullptr, (size_t)pb->total, PROT_READ, MAP_SHARED, fd, 0);
-        if (m != MAP_FAILED) pb->map = static_cast<const uint8_t*>(m);
-    }
+    map_file(pb->f.get(), pb->total);
+    pb->map = pb->f->map;
     *out = pb;
     return OMR_OK;
 }
 
 void omr_pixel_buffer_close(omr_pixel_buffer* pb) {
-    if (!pb) return;
-    if (pb->map) {
-        if (pb->reg_state == 1) (void)hipHostUnregister(const_cast<uint8_t*>(pb->map));
-        ::munmap(const_cast<uint8_t*>(pb->map), (size_t)pb->total);
-    }
-    if (pb->fd >= 0) ::close(pb->fd);
-    delete pb;
+    delete pb;   // the files close with their last user (PixFile)
 }
 
 int64_t omr_pixel_buffer_plane_offset(const omr_pixel_buffer* pb, int32_t z, int32_t c, int32_t t) {
     if (!pb || !tile_in_bounds(pb, z, c, t, 0, 0, 0, 0)) return -1;
-    return plane_offset(pb, z, c, t);
+    return plane_offset(pb, z, c, t) - pb->base;
 }
 
 omr_status omr_pixel_buffer_get_tile(const omr_pixel_buffer* pb, int32_t z, int32_t c, int32_t t, int32_t x,
@@ -377,6 +443,218 @@ omr_status omr_pixel_buffer_histogram(omr_ctx* ctx, const omr_pixel_buffer* pb, 
 omr_status omr_ctx_set_pixel_buffer_dma(omr_ctx* ctx, int32_t enable) {
     if (!ctx) return OMR_INVALID_ARGUMENT;
     ctx->pixbuf_direct = enable != 0;
+    return OMR_OK;
+}
+
+// ---- resolution pyramids: the sidecar file (layout: omr.h) and level views -----------------------
+
+int32_t omr_pixel_buffer_resolution_levels(const omr_pixel_buffer* pb) {
+    return !pb ? 0 : pb->pyr ? pb->pyr->n_levels : 1;
+}
+
+int32_t omr_pixel_buffer_resolution_descriptions(const omr_pixel_buffer* pb, int32_t* sizes_out, int32_t cap_pairs) {
+    if (!pb || (!sizes_out && cap_pairs > 0)) return -(int32_t)OMR_INVALID_ARGUMENT;
+    const int32_t n = omr_pixel_buffer_resolution_levels(pb);
+    for (int32_t k = 0; k < n && k < cap_pairs; ++k) {
+        sizes_out[2 * k] = pb->sx >> k;
+        sizes_out[2 * k + 1] = pb->sy >> k;
+    }
+    return n;
+}
+
+omr_status omr_pixel_buffer_attach_pyramid(omr_pixel_buffer* pb, const char* sidecar_path) {
+    if (!pb || !sidecar_path) return OMR_INVALID_ARGUMENT;
+    const int fd = ::open(sidecar_path, O_RDONLY | O_CLOEXEC);
+    if (fd < 0) return errno == ENOENT ? OMR_NOT_FOUND : OMR_INVALID_ARGUMENT;
+    auto pyr = std::make_shared<PixPyramid>();
+    pyr->f = std::make_shared<PixFile>();
+    pyr->f->fd = fd;                                      // closed with pyr on every return below
+    uint8_t hdr[kPyrHeaderBytes];
+    struct stat sb;
+    if (::fstat(fd, &sb) != 0 || (int64_t)sb.st_size < (int64_t)sizeof(hdr) || !read_full(fd, hdr, sizeof(hdr), 0))
+        return OMR_INVALID_ARGUMENT;
+    uint32_t u[4];
+    int32_t d[5];
+    std::memcpy(u, hdr + 8, sizeof(u));                   // little-endian fields on a little-endian host
+    std::memcpy(d, hdr + 24, sizeof(d));
+    if (std::memcmp(hdr, kPyrMagic, 8) != 0 || u[0] != kPyrVersion) return OMR_INVALID_ARGUMENT;
+    if (u[1] != OMR_PYRAMID_SUBSAMPLE && u[1] != OMR_PYRAMID_MEAN) return OMR_INVALID_ARGUMENT;
+    if ((int64_t)u[2] != pb->pt || d[0] != pb->sx || d[1] != pb->sy || d[2] != pb->sz || d[3] != pb->sc || d[4] != pb->st)
+        return OMR_INVALID_ARGUMENT;
+    if (pb->base != 0 || !pyramid_levels_valid(pb->sx, pb->sy, (int64_t)u[3])) return OMR_INVALID_ARGUMENT;
+    pyr->n_levels = (int32_t)u[3];
+    pyr->rule = (int32_t)u[1];
+    int64_t len = 0;
+    pyramid_layout(pb, pyr->n_levels, pyr->off, len);
+    if ((int64_t)sb.st_size != len) return OMR_INVALID_ARGUMENT;
+    map_file(pyr->f.get(), len);
+    pb->pyr = std::move(pyr);
+    return OMR_OK;
+}
+
+omr_status omr_pixel_buffer_level(const omr_pixel_buffer* pb, int32_t resolution, omr_pixel_buffer** view) {
+    if (!view) return OMR_INVALID_ARGUMENT;
+    *view = nullptr;
+    if (!pb || resolution < 0 || resolution >= omr_pixel_buffer_resolution_levels(pb)) return OMR_INVALID_ARGUMENT;
+    auto* v = new omr_pixel_buffer;
+    v->serial = ++g_pixbuf_serial;
+    v->f = resolution == 0 ? pb->f : pb->pyr->f;
+    v->fd = v->f->fd;
+    v->map = v->f->map;
+    v->base = resolution == 0 ? pb->base : pb->pyr->off[resolution];
+    v->sx = pb->sx >> resolution; v->sy = pb->sy >> resolution;
+    v->sz = pb->sz; v->sc = pb->sc; v->st = pb->st;
+    v->pt = pb->pt;
+    v->bpp = pb->bpp;
+    v->row_bytes = (int64_t)v->sx * v->bpp;
+    v->plane_bytes = v->row_bytes * v->sy;
+    v->total = v->plane_bytes * v->sz * v->sc * v->st;
+    *view = v;
+    return OMR_OK;
+}
+
+// Levels of groups of planes through K11 (omr_pyramid.hip): group g's planes are read into pinned
+// slot g & 1 and copied on the copy stream while group g-1's kernel runs; the levels come back
+// behind the kernel on the context's stream and are written to the file at their places while the
+// next group is in flight.
+omr_status omr_pixel_buffer_build_pyramid(omr_ctx* ctx, const omr_pixel_buffer* pb, int32_t rule, int32_t n_levels,
+                                          const char* sidecar_path) {
+    if (!ctx) return OMR_INVALID_ARGUMENT;
+    if (!pb || !sidecar_path) return fail(ctx, OMR_INVALID_ARGUMENT, "null argument");
+    if (rule != OMR_PYRAMID_SUBSAMPLE && rule != OMR_PYRAMID_MEAN)
+        return fail(ctx, OMR_INVALID_ARGUMENT, "pyramid: unknown rule");
+    if (n_levels <= 0) n_levels = omr_pyramid_level_count(pb->sx, pb->sy, OMR_PYRAMID_DEFAULT_MIN_SIDE);
+    if (!pyramid_levels_valid(pb->sx, pb->sy, n_levels))
+        return fail(ctx, OMR_INVALID_ARGUMENT, "pyramid: n_levels outside 1..min(16, 1 + floor(log2(min(size_x, size_y))))");
+    if ((int64_t)pb->sx * pb->sy >= ((int64_t)1 << 31))
+        return fail(ctx, OMR_INVALID_ARGUMENT, "pyramid: plane of 2^31 pixels or more");
+    const int64_t n_planes = (int64_t)pb->sz * pb->sc * pb->st;
+    std::vector<int64_t> off;
+    int64_t file_len = 0;
+    pyramid_layout(pb, n_levels, off, file_len);
+
+    OMR_HIP(ctx, hipSetDevice(ctx->device));
+    PixPipe* P = nullptr;
+    omr_status st = get_pipe(ctx, P);
+    if (st) return st;
+    // a slot: up to 32 planes within the staging budget; its levels, each 256-byte aligned
+    const size_t plane_al = align_up((size_t)pb->plane_bytes, 256);
+    const int G = (int)std::max<int64_t>(1, std::min<int64_t>({n_planes, 32, (int64_t)(P->group_bytes / plane_al)}));
+    std::vector<size_t> loff(n_levels, 0), lplane(n_levels, 0);
+    size_t out_bytes = 0;
+    for (int k = 1; k < n_levels; ++k) {
+        lplane[k] = (size_t)(pb->sx >> k) * (size_t)(pb->sy >> k) * pb->bpp;
+        loff[k] = out_bytes;
+        out_bytes += align_up(lplane[k] * G, 256);
+    }
+    if (n_levels > 1) {
+        st = grow(ctx, P, plane_al * G, out_bytes, true);
+        if (st) return st;
+    }
+
+    const std::string tmp = std::string(sidecar_path) + ".tmp";
+    const int fd = ::open(tmp.c_str(), O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0644);
+    if (fd < 0) return fail(ctx, OMR_INTERNAL, "pyramid: cannot create " + tmp + ": " + std::strerror(errno));
+    auto io_fail = [&](const char* what) {
+        const std::string msg = std::string("pyramid: ") + what + " " + tmp + ": " + std::strerror(errno);
+        ::close(fd);
+        ::unlink(tmp.c_str());
+        return fail(ctx, OMR_INTERNAL, msg);
+    };
+    auto dev_fail = [&](omr_status s) {   // a failed device call: wait for what is in flight, drop the file
+        (void)hipStreamSynchronize(P->copy);
+        (void)hipStreamSynchronize(ctx->stream);
+        ::close(fd);
+        ::unlink(tmp.c_str());
+        return s;
+    };
+#define OMR_PYR_HIP(expr)                                                       \
+    do {                                                                         \
+        const hipError_t _e = (expr);                                            \
+        if (_e != hipSuccess) return dev_fail(::omr::hip_fail(ctx, _e, #expr)); \
+    } while (0)
+    uint8_t hdr[kPyrHeaderBytes] = {};
+    std::memcpy(hdr, kPyrMagic, 8);
+    const uint32_t u[4] = {kPyrVersion, (uint32_t)rule, (uint32_t)pb->pt, (uint32_t)n_levels};
+    const int32_t d[5] = {pb->sx, pb->sy, pb->sz, pb->sc, pb->st};
+    std::memcpy(hdr + 8, u, sizeof(u));
+    std::memcpy(hdr + 24, d, sizeof(d));
+    // the file's length first: the gaps between levels are zeros (and the result never depends
+    // on the order the groups land in)
+    if (::ftruncate(fd, (off_t)file_len) != 0) return io_fail("cannot size");
+    if (!write_full(fd, hdr, sizeof(hdr), 0)) return io_fail("cannot write");
+
+    const int ngroups = n_levels > 1 ? (int)((n_planes + G - 1) / G) : 0;
+    auto finish = [&](int g) -> int {      // levels of group g: pinned slot -> file; 0 ok, 1 device, 2 I/O
+        const int s = g & 1;
+        const int64_t p0 = (int64_t)g * G, cnt = std::min<int64_t>(G, n_planes - p0);
+        if (hipEventSynchronize(P->d2h[s]) != hipSuccess) return 1;
+        const uint8_t* src = static_cast<const uint8_t*>(P->pin_out[s]);
+        for (int k = 1; k < n_levels; ++k)
+            if (!write_full(fd, src + loff[k], lplane[k] * (size_t)cnt, off[k] + (int64_t)lplane[k] * p0)) return 2;
+        return 0;
+    };
+    auto finish_status = [&](int r) {
+        if (r == 1) return dev_fail(hip_fail(ctx, hipGetLastError(), "pyramid: levels device -> host"));
+        (void)hipStreamSynchronize(P->copy);
+        (void)hipStreamSynchronize(ctx->stream);
+        return io_fail("cannot write");
+    };
+    std::atomic<bool> io_error{false};
+    for (int g = 0; g < ngroups; ++g) {
+        const int s = g & 1;
+        const int64_t p0 = (int64_t)g * G, cnt = std::min<int64_t>(G, n_planes - p0);
+        OMR_PYR_HIP(hipEventSynchronize(P->h2d[s]));                 // pinned slot s is free
+        uint8_t* hin = static_cast<uint8_t*>(P->pin_in[s]);
+        uint8_t* din = static_cast<uint8_t*>(P->d_in[s]);
+        P->pool.run((int)cnt, [&](int i) {                           // planes are consecutive in XYZCT order
+            if (!read_full(pb->fd, hin + plane_al * (size_t)i, (size_t)pb->plane_bytes,
+                           pb->base + pb->plane_bytes * (p0 + i)))
+                io_error = true;
+        });
+        if (io_error) {
+            errno = EIO;
+            (void)hipStreamSynchronize(P->copy);
+            (void)hipStreamSynchronize(ctx->stream);
+            ::close(fd);
+            ::unlink(tmp.c_str());
+            return fail(ctx, OMR_INTERNAL, "pixel buffer read failed");
+        }
+        OMR_PYR_HIP(hipStreamWaitEvent(P->copy, P->rend[s], 0));     // device slot s is free
+        OMR_PYR_HIP(hipMemcpyAsync(din, hin, plane_al * (size_t)cnt, hipMemcpyHostToDevice, P->copy));
+        OMR_PYR_HIP(hipEventRecord(P->h2d[s], P->copy));
+        OMR_PYR_HIP(hipStreamWaitEvent(ctx->stream, P->h2d[s], 0));
+        const void* planes[32];
+        void* levels[OMR_PYRAMID_MAX_LEVELS];
+        uint8_t* dout = static_cast<uint8_t*>(P->d_out[s]);
+        for (int64_t i = 0; i < cnt; ++i) planes[i] = din + plane_al * (size_t)i;
+        for (int k = 1; k < n_levels; ++k) levels[k - 1] = dout + loff[k];
+        st = omr_pyramid_build_device(ctx, planes, (int32_t)cnt, pb->pt, 1, pb->sx, pb->sy, 0, rule, n_levels, levels);
+        if (st) return dev_fail(st);
+        OMR_PYR_HIP(hipEventRecord(P->rend[s], ctx->stream));
+        // (the file write of group g-2 below has already emptied pinned slot s)
+        OMR_PYR_HIP(hipMemcpyAsync(P->pin_out[s], dout, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        OMR_PYR_HIP(hipEventRecord(P->d2h[s], ctx->stream));
+        if (g >= 1) {
+            const int r = finish(g - 1);
+            if (r) return finish_status(r);
+        }
+    }
+    if (ngroups) {
+        const int r = finish(ngroups - 1);
+        if (r) return finish_status(r);
+    }
+#undef OMR_PYR_HIP
+    if (::close(fd) != 0) {
+        const std::string msg = "pyramid: cannot write " + tmp + ": " + std::strerror(errno);
+        ::unlink(tmp.c_str());
+        return fail(ctx, OMR_INTERNAL, msg);
+    }
+    if (::rename(tmp.c_str(), sidecar_path) != 0) {
+        const std::string msg = std::string("pyramid: cannot rename to ") + sidecar_path + ": " + std::strerror(errno);
+        ::unlink(tmp.c_str());
+        return fail(ctx, OMR_INTERNAL, msg);
+    }
     return OMR_OK;
 }
 

@@ -12,8 +12,8 @@ Layers:
 """
 from . import _lib
 from ._lib import OmrError
-from .context import Context, thumbnail_size
-from .pixbuf import PixelBuffer, write_romio
+from .context import Context, pyramid_level_count, pyramid_level_sizes, thumbnail_size
+from .pixbuf import PixelBuffer, write_pyramid, write_romio
 from .batcher import Batcher, Pool
 from .renderer import (ChannelSettings, Renderer, ReverseIntensityContext, create_rendering_def,
                        flip, split_html_color)
@@ -45,4 +45,4 @@ def histogram_json(ctx, pixbuf, z, c, t, bins=256, use_pixels_type_range=True, l
 __all__ = ["_lib", "OmrError", "Context", "Renderer", "histogram_bin_of", "histogram_json", "thumbnail_size", "ChannelSettings", "ReverseIntensityContext",
            "create_rendering_def", "flip", "split_html_color", "ImageRegionCtx",
            "ImageRegionRequestHandler", "InMemoryPixelBuffer", "LutProvider", "RequestError",
-           "ShapeMaskCtx", "ShapeMaskRequestHandler", "PixelBuffer", "write_romio", "Batcher", "Pool"]
+           "ShapeMaskCtx", "ShapeMaskRequestHandler", "PixelBuffer", "write_romio", "write_pyramid", "Batcher", "Pool"]

@@ -109,6 +109,8 @@ class HistogramInfo(ctypes.Structure):
 
 HIST_RANGE_TYPE, HIST_RANGE_PLANE, HIST_RANGE_EXPLICIT = 0, 1, 2
 HIST_MAX_BINS = 4096
+PYRAMID_SUBSAMPLE, PYRAMID_MEAN = 0, 1
+PYRAMID_MAX_LEVELS = 16
 
 _NCH = 64
 
@@ -173,6 +175,14 @@ _SIGS = {
                              _vp, _vp, _vp]),
     "omr_pixel_buffer_histogram": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _i32, ctypes.c_double, ctypes.c_double,
                                           _i32, _vp, _vp, _vp]),
+    "omr_pyramid_level_count": (_i32, [_i32, _i32, _i32]),
+    "omr_pyramid_level_sizes": (_i32, [_i32, _i32, _i32, ctypes.POINTER(_i32)]),
+    "omr_pyramid_build_device": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i64, _i32, _i32, _vp]),
+    "omr_pixel_buffer_build_pyramid": (_i32, [_vp, _vp, _i32, _i32, ctypes.c_char_p]),
+    "omr_pixel_buffer_attach_pyramid": (_i32, [_vp, ctypes.c_char_p]),
+    "omr_pixel_buffer_resolution_levels": (_i32, [_vp]),
+    "omr_pixel_buffer_resolution_descriptions": (_i32, [_vp, ctypes.POINTER(_i32), _i32]),
+    "omr_pixel_buffer_level": (_i32, [_vp, _i32, ctypes.POINTER(_vp)]),
     "omr_batcher_create": (_i32, [_i32, _i32, _i32, ctypes.POINTER(_vp)]),
     "omr_batcher_destroy": (None, [_vp]),
     "omr_batcher_submit": (_i32, [_vp, _vp, ctypes.POINTER(ctypes.c_uint64)]),

@@ -80,6 +80,21 @@ def thumbnail_size(size_x, size_y, longest_side=96):
     return w.value, h.value
 
 
+def pyramid_level_count(size_x, size_y, min_side=256):
+    """Levels (level 0 included) until the longer side is <= min_side (omr_pyramid_level_count)."""
+    n = lib.omr_pyramid_level_count(int(size_x), int(size_y), int(min_side))
+    if n < 1:
+        raise _lib.OmrError(-n, f"pyramid_level_count({size_x}, {size_y}, {min_side})")
+    return n
+
+
+def pyramid_level_sizes(size_x, size_y, n_levels):
+    """[[w, h]] of levels 0..n_levels-1, largest first (omr_pyramid_level_sizes)."""
+    out = (ctypes.c_int32 * (2 * max(int(n_levels), 1)))()
+    check(lib.omr_pyramid_level_sizes(int(size_x), int(size_y), int(n_levels), out))
+    return [[out[2 * k], out[2 * k + 1]] for k in range(n_levels)]
+
+
 class Context:
     """One omr_ctx.  Its launches run on the context's own non-blocking HIP stream.
 
@@ -162,7 +177,8 @@ class Context:
 
     def kernel_timings(self, cap=1 << 16):
         """[(ms, kind)] of the timed hot-kernel launches since the last call (kind 2 render,
-        3 projection, 4 jpeg, 10 fused scaled render, 11 ARGB scaler); synchronises the stream."""
+        3 projection, 4 jpeg, 10 fused scaled render, 11 ARGB scaler, 12 pyramid levels); synchronises
+        the stream."""
         ms = np.zeros(cap, np.float32)
         kind = np.zeros(cap, np.int32)
         n = lib.omr_ctx_kernel_timings(self.h, ms.ctypes.data, kind.ctypes.data, cap)
@@ -222,6 +238,23 @@ class Context:
         return out
 
     # ---- scaled render: thumbnails, bird's-eye views (K10) ---------------------------------
+    pyramid_level_count = staticmethod(pyramid_level_count)
+    pyramid_level_sizes = staticmethod(pyramid_level_sizes)
+
+    def pyramid_build_device(self, planes, pixel_type, width, height, levels_out, n_levels, rule=_lib.PYRAMID_MEAN,
+                             big_endian=True, row_stride=0):
+        """K11 (omr_pyramid_build_device): levels 1..n_levels-1 of the device planes (tensors or
+        addresses) into levels_out[k-1], one device buffer per level holding the planes' level-k
+        images back to back ([n_planes][h_k][w_k], packed)."""
+        ptrs = (ctypes.c_void_p * max(len(planes), 1))(*[_ptr(p) for p in planes])
+        outs = (ctypes.c_void_p * max(len(levels_out), 1))(*[_ptr(p) for p in levels_out])
+        if len(levels_out) < int(n_levels) - 1:
+            raise _lib.OmrError(_lib.INVALID_ARGUMENT, "levels_out shorter than n_levels - 1")
+        check(lib.omr_pyramid_build_device(self.h, ptrs if planes else None, len(planes), int(pixel_type),
+                                           int(big_endian), int(width), int(height), int(row_stride), int(rule),
+                                           int(n_levels), outs if levels_out else None), self.h)
+        return levels_out
+
     def scale_argb_device(self, src, n, src_w, src_h, dst, dst_w, dst_h, row_stride=0, image_stride=0):
         """The scaling rule (exact area-weighted mean, rounded half up; omr.h) on n device ARGB
         images [n][src_h][row_stride] -> dst [n][dst_h][dst_w]."""

@@ -23,13 +23,40 @@ def write_romio(path, pixels, pixel_type):
     a.tofile(path)
 
 
+PYRAMID_MAGIC = b"OMRPYR1\0"
+PYRAMID_HEADER_BYTES = 64
+PYRAMID_LEVEL_ALIGN = 4096
+
+
+def write_pyramid(path, levels, pixel_type, rule=_lib.PYRAMID_MEAN, size=None):
+    """Write the pyramid sidecar of an image (layout: include/omr/omr.h).  levels[k-1] is level k
+    as a [t][c][z][y][x] array, k = 1..n_levels-1; size = (size_x, size_y) of level 0 (default:
+    taken from level 1 when there is one, which fits an even-sized image only, so pass it)."""
+    levels = [np.ascontiguousarray(np.asarray(lv).astype(_BE_DTYPES[pixel_type])) for lv in levels]
+    for lv in levels:
+        assert lv.ndim == 5, "levels must be [t][c][z][y][x]"
+    if size is None:
+        size = (levels[0].shape[4] * 2, levels[0].shape[3] * 2)
+    st, sc, sz = levels[0].shape[:3] if levels else (1, 1, 1)
+    hdr = PYRAMID_MAGIC + np.array([1, rule, pixel_type, len(levels) + 1], "<u4").tobytes() + \
+        np.array([size[0], size[1], sz, sc, st], "<i4").tobytes()
+    with open(path, "wb") as f:
+        f.write(hdr.ljust(PYRAMID_HEADER_BYTES, b"\0"))
+        for lv in levels:
+            f.write(b"\0" * (-f.tell() % PYRAMID_LEVEL_ALIGN))
+            f.write(lv.tobytes())
+
+
 class PixelBuffer:
-    def __init__(self, path, size_x, size_y, size_z, size_c, size_t, pixel_type):
+    def __init__(self, path, size_x, size_y, size_z, size_c, size_t, pixel_type, _handle=None):
         h = ctypes.c_void_p()
-        st = lib.omr_pixel_buffer_open(str(path).encode(), size_x, size_y, size_z, size_c, size_t, pixel_type,
-                                       ctypes.byref(h))
-        if st != _lib.OK:
-            raise _lib.OmrError(st, f"cannot open pixel buffer {path}")
+        if _handle is not None:           # a level view (PixelBuffer.level)
+            h = _handle
+        else:
+            st = lib.omr_pixel_buffer_open(str(path).encode(), size_x, size_y, size_z, size_c, size_t, pixel_type,
+                                           ctypes.byref(h))
+            if st != _lib.OK:
+                raise _lib.OmrError(st, f"cannot open pixel buffer {path}")
         self.h = h
         self.size_x, self.size_y, self.size_z, self.size_c, self.size_t = size_x, size_y, size_z, size_c, size_t
         self.pixel_type = pixel_type
@@ -52,14 +79,41 @@ class PixelBuffer:
         self.close()
 
     # PixelBuffer interface the handler uses (ImageRegionRequestHandler.java:446-454): a ROMIO
-    # buffer has one resolution level.
+    # buffer has one resolution level until a pyramid sidecar is attached.
     big_endian = True
 
     def getResolutionLevels(self):
-        return 1
+        return int(lib.omr_pixel_buffer_resolution_levels(self.h))
 
     def getResolutionDescriptions(self):
-        return [[self.size_x, self.size_y]]
+        out = (ctypes.c_int32 * (2 * _lib.PYRAMID_MAX_LEVELS))()
+        n = lib.omr_pixel_buffer_resolution_descriptions(self.h, out, _lib.PYRAMID_MAX_LEVELS)
+        if n < 1:
+            raise _lib.OmrError(_lib.INVALID_ARGUMENT, "closed pixel buffer")
+        return [[out[2 * k], out[2 * k + 1]] for k in range(n)]
+
+    def build_pyramid(self, ctx, path, rule=_lib.PYRAMID_MEAN, n_levels=0):
+        """Build this image's levels on ctx's GPU (K11) and write the sidecar file `path`
+        (omr_pixel_buffer_build_pyramid; n_levels <= 0: down to a longest side of 256).  It does
+        not attach the file."""
+        _lib.check(lib.omr_pixel_buffer_build_pyramid(ctx.h, self.h, int(rule), int(n_levels), str(path).encode()),
+                   ctx.h)
+
+    def attach_pyramid(self, path):
+        """Serve resolution levels from the sidecar file `path` (omr_pixel_buffer_attach_pyramid)."""
+        st = lib.omr_pixel_buffer_attach_pyramid(self.h, str(path).encode())
+        if st != _lib.OK:
+            raise _lib.OmrError(st, f"cannot attach pyramid {path}")
+
+    def level(self, resolution):
+        """Resolution level `resolution` (0 = full size, the index into getResolutionDescriptions)
+        as a PixelBuffer of its own; close it like any other, in any order with this one."""
+        h = ctypes.c_void_p()
+        st = lib.omr_pixel_buffer_level(self.h, int(resolution), ctypes.byref(h))
+        if st != _lib.OK:
+            raise _lib.OmrError(st, f"no resolution level {resolution}")
+        return PixelBuffer(None, self.size_x >> resolution, self.size_y >> resolution, self.size_z, self.size_c,
+                           self.size_t, self.pixel_type, _handle=h)
 
     def getTileSize(self):
         return (min(self.size_x, 256), min(self.size_y, 256))

@@ -303,13 +303,19 @@ class ImageRegionRequestHandler:
                 int(irc.flipVertical), out.data_ptr()), self.ctx.h)
             pb.close()
         elif hasattr(pb, "stack_to_device"):
-            # ROMIO file: getTile reads straight into pinned staging, then K1+K2 (omr_pixbuf.cpp)
+            # ROMIO file: getTile reads straight into pinned staging, then K1+K2 (omr_pixbuf.cpp);
+            # with a pyramid attached the tile is read from the requested level's planes
             w, h = rd.width, rd.height
             out = out_argb if out_argb is not None else torch.empty((h, w), dtype=torch.int32, device=dev)
             req = _lib.TileRequest(irc.z, irc.t, rd.x, rd.y)
-            _lib.check(lib.omr_render_pixel_buffer_tiles(
-                self.ctx.h, pb.h, ctypes.byref(qdef), bindings, pb.size_c, ctypes.byref(req), 1, w, h,
-                int(irc.flipHorizontal), int(irc.flipVertical), out.data_ptr(), 1), self.ctx.h)
+            src = pb.level(level_index) if len(levels) > 1 else pb
+            try:
+                _lib.check(lib.omr_render_pixel_buffer_tiles(
+                    self.ctx.h, src.h, ctypes.byref(qdef), bindings, pb.size_c, ctypes.byref(req), 1, w, h,
+                    int(irc.flipHorizontal), int(irc.flipVertical), out.data_ptr(), 1), self.ctx.h)
+            finally:
+                if src is not pb:
+                    src.close()
             pb.close()
         else:
             w, h = rd.width, rd.height
