@@ -123,7 +123,8 @@ void*       omr_ctx_get_stream(omr_ctx* ctx);
  * per-launch durations in ms (launch order) and clears the record; returns the count.
  * kind_out (optional) receives 2 = render, 3 = projection, 4 = jpeg per entry (10 = fused scaled
  * render, 11 = ARGB scaler: omr_render_scaled_batch_device; 12 = pyramid levels:
- * omr_pyramid_build_device).
+ * omr_pyramid_build_device; 20..26 = the batched PNG stages and 27 = the grey wave filter:
+ * omr_encode_png_gray_batch_device).
  */
 omr_status  omr_ctx_enable_kernel_timing(omr_ctx* ctx, int32_t enable);
 int32_t     omr_ctx_kernel_timings(omr_ctx* ctx, float* ms_out, int32_t* kind_out, int32_t cap);
@@ -760,6 +761,64 @@ omr_status omr_encode_png_batch_device(omr_ctx* ctx, const uint32_t* d_argb, int
  * tiles, 1: masks), 16-byte slots included. */
 size_t omr_png_batch_max_bytes(int32_t width, int32_t height, int32_t channels, int32_t n);
 
+/* ---- raw pixel tiles (K12) ---------------------------------------------------- */
+/*
+ * The pixel values themselves, not a rendering: the /tile/<image>/<z>/<c>/<t>?x=&y=&w=&h=&
+ * resolution=&format=png|tif request of the OMERO pixel-buffer microservice.  The rules are this
+ * library's own:
+ *  - PNG: greyscale (colour type 0), bit depth 8 for OMR_PIXELS_INT8 / UINT8 and 16 for INT16 /
+ *    UINT16, samples big-endian as PNG demands (a native-order plane is swapped on the device).
+ *    Signed types keep their bit patterns: the file of an int16 plane holds the same bytes as the
+ *    file of the uint16 plane with those bits, which is what a Java TYPE_USHORT_GRAY raster of the
+ *    same bytes holds; a client that knows the pixel type reinterprets them.  PNG has no 32-bit
+ *    integer, float or double sample: those types are OMR_INVALID_ARGUMENT here, TIFF carries them.
+ *  - The encoder is the batched PNG pipeline (same filter heuristic, deflate and file layout as
+ *    omr_encode_png_batch_device); the filter stage reads the region's rows in place from the
+ *    plane with the plane's pitch, so a row band or a level view needs no repacking.
+ *  - Two calls with the same input return identical bytes.
+ *
+ * omr_encode_png_gray_batch_device: tile i is the width x height region at (x, y) of the device
+ * plane d_plane (its first pixel; rows pitch_px pixels apart, pitch_px >= x + width; a 16-bit
+ * plane at an even address).  n files packed in d_out as omr_encode_png_batch_device packs them
+ * (16-byte slots in tile order, d_offsets / d_lengths / d_status optional, OMR_BUFFER_TOO_SMALL
+ * and length 0 for a file that did not fit).  Asynchronous on the context stream, no host sync.
+ * OMR_INVALID_ARGUMENT (nothing launched): a pixel type PNG cannot hold, width / height outside
+ * 1..4096, n < 0, a null table or plane, pitch_px < x + width, a negative x or y, an odd 16-bit
+ * plane address.  n == 0 is OMR_OK and launches nothing.
+ * A context created with OMR_PNG_GRAY_WAVE=0 in the environment filters every batch with the
+ * workgroup kernel (the reference route of the tests); by default a uniform batch of whole-dword
+ * rows of at most 4096 bytes that all start on 16-byte boundaries takes the wave kernel, which
+ * omr_ctx_kernel_timings reports as kind 27 (the other PNG stages: 20 filter, 21 parse, 22 tables,
+ * 23 encode, 24 meta + offsets, 25 emit, 26 CRC).  Both give the same bytes.
+ */
+typedef struct omr_raw_tile {
+    const void* d_plane;
+    int64_t pitch_px;
+    int32_t x, y;
+} omr_raw_tile;
+/* Output capacity that always holds n grey PNG files of width x height (stored blocks, chunks and
+ * the 16-byte slots included); 0 for n <= 0 or a size / sample width no file has. */
+size_t omr_png_gray_batch_max_bytes(int32_t width, int32_t height, int32_t bytes_per_sample, int32_t n);
+omr_status omr_encode_png_gray_batch_device(omr_ctx* ctx, const omr_raw_tile* tiles, int32_t n,
+                                            int32_t pixel_type, int32_t big_endian, int32_t width,
+                                            int32_t height, uint8_t* d_out, size_t out_cap,
+                                            uint64_t* d_offsets, uint32_t* d_lengths, int32_t* d_status);
+/*
+ * Host-fed: n tiles (z, c, t, x, y) of one pixel buffer or level view, all width x height, read
+ * through the pixel-buffer staging (the registered mapping's DMA, or pinned slots) and encoded in
+ * one batch.  Host out, synchronous: file i at out + offsets[i], lengths[i] bytes, status[i].  A
+ * tile outside the image (the omr_pixel_buffer_get_tile rule) fails alone with
+ * OMR_INVALID_ARGUMENT in status[i] and length 0; the call still returns OMR_OK.
+ * n * omr_png_gray_batch_max_bytes(width, height, bytes per sample, 1) always suffices.
+ */
+typedef struct omr_raw_tile_request {
+    int32_t z, c, t, x, y;
+} omr_raw_tile_request;
+omr_status omr_pixel_buffer_tiles_png(omr_ctx* ctx, const omr_pixel_buffer* pb,
+                                      const omr_raw_tile_request* reqs, int32_t n, int32_t width,
+                                      int32_t height, uint8_t* out, size_t cap, uint64_t* offsets,
+                                      uint32_t* lengths, int32_t* status);
+
 /*
  * TIFF of the 24-bit RGB view (TIFFImageWriter branch, ImageRegionRequestHandler.java:584-596):
  * baseline uncompressed big-endian RGB, 8-bit samples, >= 8 KiB strips.  Host writer.
@@ -769,6 +828,22 @@ omr_status omr_encode_tiff(omr_ctx* ctx, const uint32_t* argb, int32_t width, in
                            uint8_t* out, size_t cap, size_t* out_len);
 omr_status omr_encode_tiff_device(omr_ctx* ctx, const uint32_t* d_argb, int32_t width,
                                   int32_t height, uint8_t* out, size_t cap, size_t* out_len);
+/*
+ * Raw TIFF (K12, host writer): the pixels of one plane region in their own type -- baseline,
+ * uncompressed, big-endian ("MM"), one sample per pixel, BitsPerSample 8 / 16 / 32 / 64,
+ * SampleFormat 1 (unsigned) / 2 (signed) / 3 (IEEE), PhotometricInterpretation BlackIsZero, whole
+ * rows per strip and every strip but the last at least 8 KiB.  All eight OMR_PIXELS_* types;
+ * native-order input (big_endian = 0) is swapped.  width, height <= 65535 and a file below 4 GiB,
+ * else OMR_INVALID_ARGUMENT (omr_tiff_raw_max_bytes: 0).  *out_len receives the file's length also
+ * with OMR_BUFFER_TOO_SMALL.  omr_pixel_buffer_tile_tiff reads the tile as
+ * omr_pixel_buffer_get_tile does (same bounds rule; w, h >= 1) and writes it.
+ */
+size_t omr_tiff_raw_max_bytes(int32_t width, int32_t height, int32_t pixel_type);
+omr_status omr_encode_tiff_raw(const void* pixels, int32_t pixel_type, int32_t big_endian,
+                               int32_t width, int32_t height, uint8_t* out, size_t cap, size_t* out_len);
+omr_status omr_pixel_buffer_tile_tiff(const omr_pixel_buffer* pb, int32_t z, int32_t c, int32_t t,
+                                      int32_t x, int32_t y, int32_t w, int32_t h, uint8_t* out,
+                                      size_t cap, size_t* out_len);
 
 /* ---- shape mask ------------------------------------------------------------- */
 /*

@@ -187,6 +187,7 @@ omr_status omr_ctx_create(int32_t device_ordinal, omr_ctx** out) {
     if (const char* v = std::getenv("OMR_F1_F32")) c->f1_f32 = std::atoi(v) != 0;
     if (const char* v = std::getenv("OMR_PLAN_CACHE")) c->plan_cache = std::atoi(v) != 0;
     if (const char* v = std::getenv("OMR_SCALE_FUSED")) c->scale_fused = std::atoi(v) != 0;
+    if (const char* v = std::getenv("OMR_PNG_GRAY_WAVE")) c->png_gray_wave = std::atoi(v) != 0;
     {
         const char* v = std::getenv("OMR_PLAN_CACHE_SLOTS");
         c->plan_slots.resize((size_t)plan_cache_slot_count(v ? std::atoll(v) : 0));

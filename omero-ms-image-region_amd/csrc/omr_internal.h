@@ -163,6 +163,9 @@ struct Ctx {
     // scaled renders through the fused kernel where it applies (omr_scale.hip, K10); env
     // OMR_SCALE_FUSED=0: always K2 into aux, then k_scale_argb (the A/B and test reference route)
     bool scale_fused = true;
+    // raw grey PNG tiles through the wave-form filter where it applies (omr_png.hip, K12); env
+    // OMR_PNG_GRAY_WAVE=0: always the workgroup form (the A/B and test reference route)
+    bool png_gray_wave = true;
     // kernel timing (omr_ctx_enable_kernel_timing)
     bool timing = false;
     struct Timed { hipEvent_t start, stop; int kind; };
@@ -273,6 +276,14 @@ omr_status render_scaled(Ctx* ctx, const omr_quantum_def* qdef, const omr_channe
                          const void* d_base, int64_t tile_stride, int64_t chan_stride, const void* const* d_ptrs,
                          int32_t n, int64_t row_stride, int32_t pt, int32_t be, int32_t W, int32_t H, int32_t fh,
                          int32_t fv, uint32_t* d_out, int32_t* d_status, int32_t tw, int32_t th, const ScaledAux* aux);
+
+// K12 (omr_png.hip): omr_encode_png_gray_batch_device after its argument check (scratch: the
+// workspace, which must hold neither the planes nor the outputs).
+omr_status encode_png_gray_batch(Ctx* ctx, const omr_raw_tile* tiles, int32_t n, int32_t pixel_type, int32_t big_endian,
+                                 int32_t width, int32_t height, uint8_t* d_out, size_t out_cap,
+                                 uint64_t* d_offsets, uint32_t* d_lengths, int32_t* d_status);
+// OMR_OK when a raw grey PNG batch of this type and size can be encoded (no launch).
+omr_status validate_png_gray(Ctx* ctx, int32_t pixel_type, int32_t width, int32_t height, int32_t n);
 
 // K11 (omr_pyramid.hip): 1 <= n_levels <= min(OMR_PYRAMID_MAX_LEVELS, 1 + floor(log2(min(w, h)))).
 bool pyramid_levels_valid(int64_t w, int64_t h, int64_t n_levels);

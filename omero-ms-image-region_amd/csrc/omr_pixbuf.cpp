@@ -440,6 +440,103 @@ omr_status omr_pixel_buffer_histogram(omr_ctx* ctx, const omr_pixel_buffer* pb, 
                                     counts_out, info_out, stats_out);
 }
 
+// Raw tiles as TIFF (K12): the tile read, then the host writer (ROMIO planes are big-endian).
+omr_status omr_pixel_buffer_tile_tiff(const omr_pixel_buffer* pb, int32_t z, int32_t c, int32_t t, int32_t x,
+                                      int32_t y, int32_t w, int32_t h, uint8_t* out, size_t cap, size_t* out_len) {
+    if (!pb) return OMR_INVALID_ARGUMENT;
+    if (w <= 0 || h <= 0 || !tile_in_bounds(pb, z, c, t, x, y, w, h)) return OMR_INVALID_ARGUMENT;
+    const size_t total = omr_tiff_raw_max_bytes(w, h, pb->pt);
+    if (!total) return OMR_INVALID_ARGUMENT;
+    if (out_len) *out_len = total;
+    if (!out || cap < total) return OMR_BUFFER_TOO_SMALL;
+    std::vector<uint8_t> px((size_t)w * h * pb->bpp);
+    if (!read_tile(pb, z, c, t, x, y, w, h, px.data())) return OMR_INTERNAL;
+    return omr_encode_tiff_raw(px.data(), pb->pt, 1, w, h, out, cap, out_len);
+}
+
+// Raw tiles as grey PNG (K12): the valid tiles' rows into the staging slot's device buffer -- by
+// DMA from the registered mapping, else by the reader threads through the pinned slot -- packed
+// at `width` pixels per row, then one grey PNG batch on the context's stream and the files back.
+omr_status omr_pixel_buffer_tiles_png(omr_ctx* ctx, const omr_pixel_buffer* pb, const omr_raw_tile_request* reqs,
+                                      int32_t n, int32_t width, int32_t height, uint8_t* out, size_t cap,
+                                      uint64_t* offsets, uint32_t* lengths, int32_t* status) {
+    if (!ctx) return OMR_INVALID_ARGUMENT;
+    if (!pb) return fail(ctx, OMR_INVALID_ARGUMENT, "null pixel buffer");
+    omr_status st = validate_png_gray(ctx, pb->pt, width, height, n);
+    if (st || n == 0) return st;
+    if (!reqs || !offsets || !lengths || !status || (!out && cap))
+        return fail(ctx, OMR_INVALID_ARGUMENT, "null raw tile table or output");
+    std::vector<int> idx;
+    for (int i = 0; i < n; ++i) {
+        const omr_raw_tile_request& r = reqs[i];
+        offsets[i] = 0;
+        lengths[i] = 0;
+        status[i] = tile_in_bounds(pb, r.z, r.c, r.t, r.x, r.y, width, height) ? OMR_OK : OMR_INVALID_ARGUMENT;
+        if (status[i] == OMR_OK) idx.push_back(i);
+    }
+    const int m = (int)idx.size();
+    if (!m) return OMR_OK;
+    OMR_HIP(ctx, hipSetDevice(ctx->device));
+    PixPipe* P = nullptr;
+    st = get_pipe(ctx, P);
+    if (st) return st;
+    const size_t seg = (size_t)width * pb->bpp, tile_al = align_up(seg * height, 256);
+    const size_t dcap = std::min((size_t)m * omr_png_gray_batch_max_bytes(width, height, pb->bpp, 1), cap & ~(size_t)15);
+    const size_t o_meta = align_up(dcap, 256);
+    st = grow(ctx, P, tile_al * m, o_meta + (size_t)m * 16, false);
+    if (st) return st;
+    uint8_t* din = static_cast<uint8_t*>(P->d_in[0]);
+    uint8_t* dout = static_cast<uint8_t*>(P->d_out[0]);
+    OMR_HIP(ctx, hipEventSynchronize(P->h2d[0]));                      // pinned slot 0 is free
+    OMR_HIP(ctx, hipEventRecord(P->rend[0], ctx->stream));             // earlier work is done with the slot
+    OMR_HIP(ctx, hipStreamWaitEvent(P->copy, P->rend[0], 0));
+    if (ctx->pixbuf_direct && ensure_registered(const_cast<omr_pixel_buffer*>(pb))) {
+        for (int k = 0; k < m; ++k) {
+            const omr_raw_tile_request& r = reqs[idx[k]];
+            const uint8_t* src = pb->map + plane_offset(pb, r.z, r.c, r.t) + (int64_t)r.y * pb->row_bytes +
+                                 (int64_t)r.x * pb->bpp;
+            OMR_HIP(ctx, hipMemcpy2DAsync(din + tile_al * k, seg, src, (size_t)pb->row_bytes, seg, (size_t)height,
+                                          hipMemcpyHostToDevice, P->copy));
+        }
+    } else {
+        uint8_t* hin = static_cast<uint8_t*>(P->pin_in[0]);
+        std::atomic<bool> io_error{false};
+        P->pool.run(m, [&](int k) {
+            const omr_raw_tile_request& r = reqs[idx[k]];
+            if (!read_tile(pb, r.z, r.c, r.t, r.x, r.y, width, height, hin + tile_al * k)) io_error = true;
+        });
+        if (io_error) return fail(ctx, OMR_INTERNAL, "pixel buffer read failed");
+        OMR_HIP(ctx, hipMemcpyAsync(din, hin, tile_al * m, hipMemcpyHostToDevice, P->copy));
+    }
+    OMR_HIP(ctx, hipEventRecord(P->h2d[0], P->copy));
+    OMR_HIP(ctx, hipStreamWaitEvent(ctx->stream, P->h2d[0], 0));
+    std::vector<omr_raw_tile> tiles((size_t)m);
+    for (int k = 0; k < m; ++k) tiles[k] = {din + tile_al * k, width, 0, 0};
+    uint64_t* d_off = reinterpret_cast<uint64_t*>(dout + o_meta);
+    uint32_t* d_len = reinterpret_cast<uint32_t*>(d_off + m);
+    int32_t* d_st = reinterpret_cast<int32_t*>(d_len + m);
+    st = encode_png_gray_batch(ctx, tiles.data(), m, pb->pt, 1, width, height, dout, dcap, d_off, d_len, d_st);
+    if (st) return st;
+    std::vector<uint8_t> meta((size_t)m * 16);
+    OMR_HIP(ctx, hipMemcpyAsync(meta.data(), d_off, meta.size(), hipMemcpyDeviceToHost, ctx->stream));
+    OMR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const uint64_t* h_off = reinterpret_cast<const uint64_t*>(meta.data());
+    const uint32_t* h_len = reinterpret_cast<const uint32_t*>(h_off + m);
+    const int32_t* h_st = reinterpret_cast<const int32_t*>(h_len + m);
+    size_t used = 0;
+    for (int k = 0; k < m; ++k) {
+        const int i = idx[k];
+        status[i] = h_st[k];
+        if (h_st[k] == OMR_OK) {
+            offsets[i] = h_off[k];
+            lengths[i] = h_len[k];
+            used = std::max<size_t>(used, h_off[k] + h_len[k]);
+        }
+    }
+    if (used) OMR_HIP(ctx, hipMemcpy(out, dout, used, hipMemcpyDeviceToHost));
+    return OMR_OK;
+}
+
 omr_status omr_ctx_set_pixel_buffer_dma(omr_ctx* ctx, int32_t enable) {
     if (!ctx) return OMR_INVALID_ARGUMENT;
     ctx->pixbuf_direct = enable != 0;

@@ -89,7 +89,9 @@ static uint32_t host_crc(const uint8_t* d, size_t n, uint32_t crc = 0) {
 }
 
 // Raw (filtered) scanline byte i of the image: filter 0 per row, then row bytes.
-enum PngKind : int32_t { kRgb = 0, kIdx1 = 1, kIdx8 = 2 };
+// kGray8 / kGray16 (K12): raw plane samples, one per pixel, read in place from the plane's rows.
+enum PngKind : int32_t { kRgb = 0, kIdx1 = 1, kIdx8 = 2, kGray8 = 3, kGray16 = 4 };
+__host__ __device__ constexpr bool png_gray(int kind) { return kind == kGray8 || kind == kGray16; }
 
 struct PngArgs {
     const uint32_t* argb;    // kRgb
@@ -97,6 +99,9 @@ struct PngArgs {
     uint8_t* chunk;          // IDAT chunk: [len 4][IDAT 4][zlib ...][adler 4][crc 4]
     unsigned long long* sums;  // adler partial sums (2)
     uint32_t* crc_out;
+    const uint8_t* gray;     // kGray*: the region's first byte in its plane
+    int64_t gpitch;          // kGray*: plane row pitch (bytes)
+    int32_t gswap, gpad;     // kGray16: 1 = little-endian plane (row byte i is plane byte i ^ 1)
     int32_t kind, W, H, flip_h, flip_v;
     int64_t rowlen;          // 1 + row bytes
     int64_t raw;             // rowlen * H
@@ -318,6 +323,7 @@ __device__ __forceinline__ uint32_t row_byte(const PngArgs& A, int y, int i) {
         const int px = i / 3, comp = i - px * 3;
         return (A.argb[(int64_t)y * A.W + px] >> (16 - 8 * comp)) & 0xFF;
     }
+    if (png_gray(A.kind)) return A.gray[(int64_t)y * A.gpitch + (i ^ A.gswap)];
     if (A.kind == kIdx8) return mask_bit(A, i, y);
     uint32_t b = 0;
     for (int k = 0; k < 8; ++k) b = (b << 1) | (i * 8 + k < A.W ? mask_bit(A, i * 8 + k, y) : 0u);
@@ -412,6 +418,17 @@ __device__ __forceinline__ void png_load_row(const PngArgs& A, int yy, int rb, u
             rw[3 * q + 2] = __builtin_amdgcn_perm(v.w, v.z, 0x04050600u);   // b2 r3 g3 b3
         }
         return;                                    // rb = 3 W: no tail
+    }
+    if (png_gray(A.kind) && ((reinterpret_cast<uintptr_t>(A.gray) | (uintptr_t)A.gpitch) & 3) == 0) {
+        // every row starts on a dword: whole dwords of the plane (a little-endian 16-bit pair
+        // swapped in the register), the ragged tail byte by byte
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(A.gray + (int64_t)yy * A.gpitch);
+        for (int j = threadIdx.x; j < (rb >> 2); j += 256) {
+            const uint32_t v = src[j];
+            rw[j] = A.gswap ? __builtin_amdgcn_perm(v, v, 0x02030001u) : v;
+        }
+        for (int i = (rb & ~3) + threadIdx.x; i < 4 * nw; i += 256) row[i] = i < rb ? (uint8_t)row_byte(A, yy, i) : 0;
+        return;
     }
     if (A.kind == kRgb) {
         for (int px = threadIdx.x; px < A.W; px += 256) {
@@ -1407,7 +1424,8 @@ struct PngPlan {
 
 static PngPlan png_plan(int kind, int W, int H) {
     PngPlan p;
-    const int64_t rowbytes = kind == kRgb ? 3ll * W : kind == kIdx8 ? W : (W + 7) / 8;
+    const int64_t rowbytes = kind == kRgb ? 3ll * W : kind == kIdx8 || kind == kGray8 ? W
+                             : kind == kGray16 ? 2ll * W : (W + 7) / 8;
     p.rowlen = 1 + rowbytes;
     p.raw = p.rowlen * H;
     p.nblk = (p.raw + kStored - 1) / kStored;
@@ -1650,6 +1668,11 @@ constexpr int kCrcPowLo = 4096, kCrcPowHi = 2048;
 struct PngImg {
     const uint32_t* argb;      // kRgb: pixels, row stride W
     const uint8_t* bits;       // kIdx1 / kIdx8: MSB-first mask bits
+    // kGray8 / kGray16: the raw-plane source, read in place: the region's pixel (c, r) is the
+    // plane's pixel (rx + c, ry + r), bps bytes each, rows pitch_px pixels apart
+    const uint8_t* plane;      // the plane's first pixel
+    int64_t pitch_px;
+    int32_t rx, ry, bps, be;   // region origin; bytes per sample (1 or 2); big-endian samples
     int32_t kind, W, H, flip_h, flip_v, bpp;
     int32_t row0, pblk0, grp0, pre_len;         // first global row / parse block / group; prefix bytes
     int32_t rblk0, pad2;                        // first D1 workgroup (kPngRowsPerWg rows each)
@@ -1734,6 +1757,11 @@ __device__ __forceinline__ PngArgs pngb_args(const PngImg& I) {
     PngArgs A{};
     A.argb = I.argb;
     A.bits = I.bits;
+    if (png_gray(I.kind)) {
+        A.gray = I.plane + ((int64_t)I.ry * I.pitch_px + I.rx) * I.bps;
+        A.gpitch = I.pitch_px * I.bps;
+        A.gswap = I.bps == 2 && !I.be;
+    }
     A.kind = I.kind;
     A.W = I.W;
     A.H = I.H;
@@ -1979,6 +2007,173 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OMR_PN
                 // bytes outside the whole out dwords: the row's first u, its last (rb - u) & 3
                 // (FULL: only dword 0 and the row's last dword can hold such bytes)
                 if ((!FULL || t == 0 || t == 3 * M - 1) && (4 * j < u || 4 * j + 3 >= u + 4 * jfull)) {
+                    for (int b = 0; b < 4; ++b) {
+                        const int tt = 4 * j + b;
+                        if (tt < u || tt >= u + 4 * jfull) flt[ypos + 1 + tt] = (uint8_t)byte_at(w, b);
+                    }
+                }
+            }
+        }
+        s1 += a1;                                              // sum (raw - pos) * byte over the row
+        s2 += rbase * a1 - 4ull * aj - ad;
+        if (lane == 0) {
+            flt[ypos] = (uint8_t)f;
+            s1 += (unsigned long long)f;
+            s2 += (unsigned long long)(raw - ypos) * (unsigned long long)f;
+        }
+        wave_lds_sync();                                       // every lane is done with `prev`
+        uint32_t* tmp = prev;
+        prev = cur;
+        cur = tmp;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        s1 += __shfl_xor(s1, o, 64);
+        s2 += __shfl_xor(s2, o, 64);
+    }
+    unsigned long long* rs = B.row_sums + 2 * ((int64_t)I.row0 + y0);
+    if (lane < 2 * (y1 - y0)) rs[lane] = lane == 0 ? s1 : lane == 1 ? s2 : 0ull;
+}
+
+// D1, wave form for grey rows (K12): k_pngb_filter_wave for kGray8 / kGray16 tiles of a uniform
+// batch whose rows are whole dwords, at most 4096 bytes, and start on 16-byte boundaries.  Lane l
+// holds the row's 16-byte units q = l + 64 m as they lie in the plane (one coalesced load each, a
+// little-endian 16-bit plane swapped to PNG's byte order by v_perm as it is staged): no ARGB
+// unpack.  The left neighbours sit BPS bytes back.  Same passes, filter choice and bytes as the
+// RGB form and as png_filter_rows.  (A kernel of its own: sharing the body would make the RGB
+// kernel's staging, row indexing and step count depend on which source it serves.)
+// LDS per wave: two rows of 4 * 64 * M dwords, each behind four dwords whose last is the zero left
+// of the row's first dword (so the staged units are aligned 16-byte stores).
+template <int M> __host__ __device__ constexpr int fg_row_dwords() { return 4 * 64 * M + 4; }
+template <int M> __host__ __device__ constexpr size_t fg_lds_bytes() { return (size_t)4 * 2 * fg_row_dwords<M>() * 4; }
+
+// FULL: the row is exactly 64 * M units (1024 uint16 pixels at M = 2, 1024 uint8 pixels at M = 1).
+// M = 4 holds 16 residual dwords and 4 loads in flight per lane: its 33 KiB of LDS per workgroup
+// allow 4 waves per SIMD anyway, so it takes their 128 VGPRs (5 waves' 96 spilled to scratch).
+template <int BPS, int M, bool FULL>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(M == 4 ? 4 : OMR_PNG_FW_WAVES)))
+k_pngb_filter_gray(PngBatch B) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_fg[];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int64_t wid = xcd_block(blockIdx.x, gridDim.x) * 4 + wv;   // (XCD order: the band above on the same L2)
+    const int i = (int)(wid / B.fw_bands);
+    if (i >= B.n) return;
+    const PngImg& I = B.img[i];
+    const int y0 = (int)(wid - (int64_t)i * B.fw_bands) * kFilterBandRows;
+    const int y1 = min(I.H, y0 + kFilterBandRows);
+    const int rb = I.W * BPS, nd = rb >> 2, nu = (rb + 15) >> 4;   // row bytes, dwords, 16-byte units
+    const int64_t pitch = I.pitch_px * BPS;
+    const uint8_t* __restrict__ src = I.plane + (int64_t)I.ry * pitch + (int64_t)I.rx * BPS;
+    const bool swap = BPS == 2 && !I.be;
+    uint8_t* __restrict__ flt = B.flt + I.flt;
+    const int64_t rowlen = I.rowlen, raw = I.raw;
+    constexpr int S = fg_row_dwords<M>(), T = 4 * M;
+    uint32_t* bufA = s_fg + wv * 2 * S;
+    uint32_t* bufB = bufA + S;
+    if (lane == 0) { bufA[3] = 0u; bufB[3] = 0u; }
+    auto load_raw = [&](int y, uint4 (&v)[M]) {
+#pragma unroll
+        for (int m = 0; m < M; ++m) {
+            const int q = lane + 64 * m;
+            v[m] = make_uint4(0, 0, 0, 0);
+            // (a last unit that the row only partly fills ends inside the plane's row: the region
+            // starts on a 16-byte boundary of a pitch that is a multiple of 16)
+            if (y >= 0 && (FULL || q < nu)) v[m] = reinterpret_cast<const uint4*>(src + (int64_t)y * pitch)[q];
+        }
+    };
+    auto put_row = [&](const uint4 (&v)[M], uint32_t* row) {   // the row's dword j at row[4 + j]
+#pragma unroll
+        for (int m = 0; m < M; ++m) {
+            const int q = lane + 64 * m;
+            if (FULL || q < nu) {
+                uint4 w = v[m];
+                if (swap) {
+                    w.x = __builtin_amdgcn_perm(w.x, w.x, 0x02030001u);
+                    w.y = __builtin_amdgcn_perm(w.y, w.y, 0x02030001u);
+                    w.z = __builtin_amdgcn_perm(w.z, w.z, 0x02030001u);
+                    w.w = __builtin_amdgcn_perm(w.w, w.w, 0x02030001u);
+                }
+                reinterpret_cast<uint4*>(row + 4)[q] = w;
+            }
+        }
+    };
+    uint4 nxt[M];
+    load_raw(y0 - 1, nxt);
+    uint32_t* prev = bufA;
+    uint32_t* cur = bufB;
+    put_row(nxt, prev);
+    load_raw(y0, nxt);
+    unsigned long long s1 = 0, s2 = 0;
+    for (int y = y0; y < y1; ++y) {
+        put_row(nxt, cur);
+        if (y + 1 < y1) load_raw(y + 1, nxt);                 // the next row's loads fly meanwhile
+        wave_lds_sync();
+        // pass 1: the five |residual| sums; lane l takes row dwords j = l + 64 t (conflict-free LDS)
+        uint32_t sm[5] = {0, 0, 0, 0, 0};
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+            const int j = lane + 64 * t;
+            if (FULL || j < nd) {
+                const uint32_t X = cur[4 + j], Bv = prev[4 + j];
+                const uint32_t Av = __builtin_amdgcn_alignbyte(X, cur[3 + j], 4 - BPS);
+                const uint32_t Cv = __builtin_amdgcn_alignbyte(Bv, prev[3 + j], 4 - BPS);
+                uint32_t r[5];
+                png_residuals(X, Av, Bv, Cv, r);
+#pragma unroll
+                for (int f = 0; f < 5; ++f) sm[f] = abs_sum8(r[f], sm[f]);
+            }
+            if (FULL) __builtin_amdgcn_sched_barrier(0);      // one dword's reads at a time (VGPRs)
+        }
+        int f = 0;                                             // scalar: sums by DPP, read out
+        uint32_t best = 0xFFFFFFFFu;
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            const uint32_t v = wave_sum_dpp(sm[k]);
+            if (v < best) { best = v; f = k; }                 // lowest filter on ties
+        }
+        // pass 2: the chosen residual row (one straight-line copy per filter, picked once per row)
+        uint32_t c[T];
+        auto pass2 = [&](auto F) {
+#pragma unroll
+            for (int t = 0; t < T; ++t) {
+                const int j = lane + 64 * t;
+                c[t] = 0u;
+                if (FULL || j < nd) {
+                    const uint32_t X = cur[4 + j], Bv = prev[4 + j];
+                    const uint32_t Av = __builtin_amdgcn_alignbyte(X, cur[3 + j], 4 - BPS);
+                    const uint32_t Cv = __builtin_amdgcn_alignbyte(Bv, prev[3 + j], 4 - BPS);
+                    c[t] = png_residual(decltype(F)::value, X, Av, Bv, Cv);
+                }
+            }
+        };
+        switch (f) {
+        case 0: pass2(FltIdx<0>{}); break;
+        case 1: pass2(FltIdx<1>{}); break;
+        case 2: pass2(FltIdx<2>{}); break;
+        case 3: pass2(FltIdx<3>{}); break;
+        default: pass2(FltIdx<4>{}); break;
+        }
+        const int64_t ypos = (int64_t)y * rowlen;              // the row's offset in the stream
+        const int64_t row0 = I.flt + ypos;                     // ... and in B.flt (16-aligned base)
+        const int u = (int)((-row0 - 1) & 3);                  // residual byte u sits at an aligned address
+        uint32_t* gw = reinterpret_cast<uint32_t*>(B.flt + row0 + u + 1);   // out dword J
+        const int jfull = (rb - u) >> 2;                       // out dwords J < jfull lie inside the row
+        const unsigned long long rbase = (unsigned long long)(raw - ypos - 1);
+        uint32_t a1 = 0, aj = 0, ad = 0;                      // this row's Adler partials in 32 bits
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+            const int j = lane + 64 * t;
+            const uint32_t hi = next_lane_dword(c[t], t + 1 < T ? c[t + 1] : 0u);   // residual dword j + 1
+            if (FULL || j < nd) {
+                const uint32_t w = c[t];
+                if ((FULL && t < T - 1) || j < jfull) gw[j] = __builtin_amdgcn_alignbyte(hi, w, u);
+                const uint32_t sv = __builtin_amdgcn_sad_u8(w, 0u, 0u);
+                a1 += sv;
+                aj += (uint32_t)j * sv;                        // <= 1023 * 16 * 1020 per lane and row
+                ad = __builtin_amdgcn_udot4(w, 0x03020100u, ad, false);
+                // bytes outside the whole out dwords: the row's first u, its last (rb - u) & 3
+                // (FULL: only dword 0 and the row's last dword can hold such bytes)
+                if ((!FULL || t == 0 || t == T - 1) && (4 * j < u || 4 * j + 3 >= u + 4 * jfull)) {
                     for (int b = 0; b < 4; ++b) {
                         const int tt = 4 * j + b;
                         if (tt < u || tt >= u + 4 * jfull) flt[ypos + 1 + tt] = (uint8_t)byte_at(w, b);
@@ -3272,6 +3467,9 @@ struct PngImgHost {
     const uint8_t* bits;
     int kind, W, H, flip_h, flip_v;
     uint8_t rgba[4];
+    const uint8_t* plane;          // kGray*: the raw-plane source (PngImg)
+    int64_t pitch_px;
+    int rx, ry, be;
 };
 
 static int png_prefix(int kind, int W, int H, const uint8_t* rgba, uint8_t* pre) {
@@ -3281,11 +3479,11 @@ static int png_prefix(int kind, int W, int H, const uint8_t* rgba, uint8_t* pre)
     uint8_t ihdr[13];
     ihdr[0] = W >> 24; ihdr[1] = W >> 16; ihdr[2] = W >> 8; ihdr[3] = W;
     ihdr[4] = H >> 24; ihdr[5] = H >> 16; ihdr[6] = H >> 8; ihdr[7] = H;
-    ihdr[8] = kind == kIdx1 ? 1 : 8;
-    ihdr[9] = kind == kRgb ? 2 : 3;   // truecolour / indexed
+    ihdr[8] = kind == kIdx1 ? 1 : kind == kGray16 ? 16 : 8;
+    ihdr[9] = kind == kRgb ? 2 : png_gray(kind) ? 0 : 3;   // truecolour / greyscale / indexed
     ihdr[10] = ihdr[11] = ihdr[12] = 0;
     put_chunk(v, "IHDR", ihdr, 13);
-    if (kind != kRgb) {
+    if (kind != kRgb && !png_gray(kind)) {
         const uint8_t plte[6] = {0, 0, 0, rgba[0], rgba[1], rgba[2]};
         put_chunk(v, "PLTE", plte, 6);
         const uint8_t trns[2] = {0, rgba[3]};
@@ -3328,7 +3526,12 @@ static omr_status plan_png_batch(Ctx* ctx, const PngImgHost* im, int n, PngBatch
         d.H = h.H;
         d.flip_h = h.flip_h;
         d.flip_v = h.flip_v;
-        d.bpp = h.kind == kRgb ? 3 : 1;
+        d.bpp = h.kind == kRgb ? 3 : h.kind == kGray16 ? 2 : 1;
+        d.pitch_px = h.pitch_px;
+        d.rx = h.rx;
+        d.ry = h.ry;
+        d.bps = h.kind == kGray16 ? 2 : 1;
+        d.be = h.be;
         d.rowlen = P.rowlen;
         d.raw = P.raw;
         d.nblk = P.nblk;
@@ -3390,6 +3593,22 @@ static omr_status plan_png_batch(Ctx* ctx, const PngImgHost* im, int n, PngBatch
     return OMR_OK;
 }
 
+constexpr int kKindPngGrayWave = 27;           // omr_ctx_kernel_timings: the grey wave filter (omr.h)
+
+template <int BPS>
+static void launch_filter_gray(int m, bool full, unsigned blocks, hipStream_t s, const PngBatch& Bt) {
+    switch (m * 2 + (full ? 1 : 0)) {
+    case 2: hipLaunchKernelGGL((k_pngb_filter_gray<BPS, 1, false>), dim3(blocks), dim3(256), fg_lds_bytes<1>(), s, Bt); break;
+    case 3: hipLaunchKernelGGL((k_pngb_filter_gray<BPS, 1, true>), dim3(blocks), dim3(256), fg_lds_bytes<1>(), s, Bt); break;
+    case 4: hipLaunchKernelGGL((k_pngb_filter_gray<BPS, 2, false>), dim3(blocks), dim3(256), fg_lds_bytes<2>(), s, Bt); break;
+    case 5: hipLaunchKernelGGL((k_pngb_filter_gray<BPS, 2, true>), dim3(blocks), dim3(256), fg_lds_bytes<2>(), s, Bt); break;
+    case 6: hipLaunchKernelGGL((k_pngb_filter_gray<BPS, 3, false>), dim3(blocks), dim3(256), fg_lds_bytes<3>(), s, Bt); break;
+    case 7: hipLaunchKernelGGL((k_pngb_filter_gray<BPS, 3, true>), dim3(blocks), dim3(256), fg_lds_bytes<3>(), s, Bt); break;
+    case 8: hipLaunchKernelGGL((k_pngb_filter_gray<BPS, 4, false>), dim3(blocks), dim3(256), fg_lds_bytes<4>(), s, Bt); break;
+    default: hipLaunchKernelGGL((k_pngb_filter_gray<BPS, 4, true>), dim3(blocks), dim3(256), fg_lds_bytes<4>(), s, Bt); break;
+    }
+}
+
 // Encode images[0..n) into d_out (asynchronous on the context stream).  Scratch: the workspace
 // from ws_off on, already sized to ws_off + L.scratch (it must not hold the inputs).
 static omr_status launch_png_batch(Ctx* ctx, PngBatchPlan& L, const PngImgHost* im, int n, size_t ws_off,
@@ -3401,6 +3620,7 @@ static omr_status launch_png_batch(Ctx* ctx, PngBatchPlan& L, const PngImgHost* 
     for (int i = 0; i < n; ++i) {
         L.I[i].argb = im[i].argb;
         L.I[i].bits = im[i].bits;
+        L.I[i].plane = im[i].plane;
     }
     std::vector<PngImg>& I = L.I;
     std::vector<int32_t>& firsts = L.firsts;
@@ -3470,10 +3690,19 @@ static omr_status launch_png_batch(Ctx* ctx, PngBatchPlan& L, const PngImgHost* 
     const bool wave_filter = !(fw_env && *fw_env == '0');
     const int W0 = im[0].W, H0 = im[0].H;
     const int fw_m = (W0 / 4 + 63) / 64;
+    // the grey wave form (K12; a context created with OMR_PNG_GRAY_WAVE=0: the workgroup form): a
+    // uniform batch of whole-dword rows up to 4096 bytes whose every row starts on a 16-byte boundary
+    const int gray_rb = W0 * (im[0].kind == kGray16 ? 2 : 1);
+    bool gray_wave = ctx->png_gray_wave && uniform && png_gray(im[0].kind) && gray_rb % 4 == 0 && gray_rb <= 4096;
+    for (int i = 0; gray_wave && i < n; ++i) {
+        const int64_t bps = gray_rb / W0;
+        gray_wave = reinterpret_cast<uintptr_t>(im[i].plane) % 16 == 0 && im[i].rx * bps % 16 == 0 &&
+                    im[i].pitch_px * bps % 16 == 0;
+    }
     // kernel timing (omr_ctx_enable_kernel_timing): kinds 20.. per stage, for bench.py's roofline
     // of the batched PNG pipeline
     {
-        KernelTimer t_filter(ctx, 20);
+        KernelTimer t_filter(ctx, gray_wave ? kKindPngGrayWave : 20);
         if (wave_filter && uniform && im[0].kind == kRgb && W0 % 4 == 0 && W0 <= 1024) {
             Bt.fw_bands = (H0 + kFilterBandRows - 1) / kFilterBandRows;
             const unsigned blocks = (unsigned)(((int64_t)n * Bt.fw_bands + 3) / 4);
@@ -3488,6 +3717,12 @@ static omr_status launch_png_batch(Ctx* ctx, PngBatchPlan& L, const PngImgHost* 
             case 8: hipLaunchKernelGGL((k_pngb_filter_wave<4, false>), dim3(blocks), dim3(256), fw_lds_bytes<4>(), s, Bt); break;
             default: hipLaunchKernelGGL((k_pngb_filter_wave<4, true>), dim3(blocks), dim3(256), fw_lds_bytes<4>(), s, Bt); break;
             }
+        } else if (gray_wave) {
+            Bt.fw_bands = (H0 + kFilterBandRows - 1) / kFilterBandRows;
+            const unsigned blocks = (unsigned)(((int64_t)n * Bt.fw_bands + 3) / 4);
+            const int gu = (gray_rb + 15) / 16, gm = (gu + 63) / 64;
+            if (gray_rb == W0) launch_filter_gray<1>(gm, gu == 64 * gm && gray_rb % 16 == 0, blocks, s, Bt);
+            else launch_filter_gray<2>(gm, gu == 64 * gm && gray_rb % 16 == 0, blocks, s, Bt);
         } else {
             hipLaunchKernelGGL(k_pngb_filter, dim3((unsigned)L.rblk), dim3(256), rows_lds, s, Bt);
         }
@@ -3611,6 +3846,32 @@ static omr_status png_single_batched(Ctx* ctx, PngImgHost im, PngBatchPlan& L, c
     return OMR_OK;
 }
 
+omr_status validate_png_gray(Ctx* ctx, int32_t pixel_type, int32_t width, int32_t height, int32_t n) {
+    const int bps = bytes_per_pixel(pixel_type);
+    if (bps != 1 && bps != 2)
+        return fail(ctx, OMR_INVALID_ARGUMENT, "PNG has no 32-bit integer, float or double sample (TIFF carries them)");
+    if (n < 0 || width <= 0 || height <= 0 || width > kPngbMaxSide || height > kPngbMaxSide)
+        return fail(ctx, OMR_INVALID_ARGUMENT, "bad grey PNG batch size (tiles up to 4096 x 4096)");
+    return OMR_OK;
+}
+
+omr_status encode_png_gray_batch(Ctx* ctx, const omr_raw_tile* tiles, int32_t n, int32_t pixel_type, int32_t big_endian,
+                                 int32_t width, int32_t height, uint8_t* d_out, size_t out_cap,
+                                 uint64_t* d_offsets, uint32_t* d_lengths, int32_t* d_status) {
+    const int kind = bytes_per_pixel(pixel_type) == 2 ? kGray16 : kGray8;
+    std::vector<PngImgHost> im(n);
+    for (int i = 0; i < n; ++i) {
+        im[i] = {nullptr, nullptr, kind, width, height, 0, 0, {0, 0, 0, 0}, static_cast<const uint8_t*>(tiles[i].d_plane),
+                 tiles[i].pitch_px, tiles[i].x, tiles[i].y, big_endian ? 1 : 0};
+    }
+    PngBatchPlan L;
+    omr_status st = plan_png_batch(ctx, im.data(), n, L);
+    if (st) return st;
+    st = ensure_workspace(ctx, L.scratch);
+    if (st) return st;
+    return launch_png_batch(ctx, L, im.data(), n, 0, d_out, out_cap, d_offsets, d_lengths, d_status);
+}
+
 }  // namespace omr
 
 using namespace omr;
@@ -3689,6 +3950,33 @@ omr_status omr_encode_png_batch_device(omr_ctx* ctx, const uint32_t* d_argb, int
 size_t omr_png_batch_max_bytes(int32_t width, int32_t height, int32_t channels, int32_t n) {
     if (n <= 0) return 0;
     return (size_t)n * align_up(omr_png_max_bytes(width, height, channels), 16);
+}
+
+size_t omr_png_gray_batch_max_bytes(int32_t width, int32_t height, int32_t bytes_per_sample, int32_t n) {
+    if (n <= 0 || width <= 0 || height <= 0 || (bytes_per_sample != 1 && bytes_per_sample != 2)) return 0;
+    const int kind = bytes_per_sample == 2 ? kGray16 : kGray8;
+    return (size_t)n * align_up(256 + (size_t)png_plan(kind, width, height).chunk_bytes, 16);
+}
+
+omr_status omr_encode_png_gray_batch_device(omr_ctx* ctx, const omr_raw_tile* tiles, int32_t n, int32_t pixel_type,
+                                            int32_t big_endian, int32_t width, int32_t height, uint8_t* d_out,
+                                            size_t out_cap, uint64_t* d_offsets, uint32_t* d_lengths,
+                                            int32_t* d_status) {
+    if (!ctx) return OMR_INVALID_ARGUMENT;
+    omr_status st = validate_png_gray(ctx, pixel_type, width, height, n);
+    if (st || n == 0) return st;
+    if (!tiles || !d_out) return fail(ctx, OMR_INVALID_ARGUMENT, "null grey PNG batch table or buffer");
+    const int bps = bytes_per_pixel(pixel_type);
+    for (int i = 0; i < n; ++i) {
+        const omr_raw_tile& t = tiles[i];
+        if (!t.d_plane || t.x < 0 || t.y < 0 || t.pitch_px < (int64_t)t.x + width)
+            return fail(ctx, OMR_INVALID_ARGUMENT, "grey PNG tile " + std::to_string(i) + ": null plane or pitch_px < x + width");
+        if (bps == 2 && (reinterpret_cast<uintptr_t>(t.d_plane) & 1))
+            return fail(ctx, OMR_INVALID_ARGUMENT, "grey PNG tile " + std::to_string(i) + ": 16-bit plane at an odd address");
+    }
+    OMR_HIP(ctx, hipSetDevice(ctx->device));
+    return encode_png_gray_batch(ctx, tiles, n, pixel_type, big_endian, width, height, d_out, out_cap, d_offsets,
+                                 d_lengths, d_status);
 }
 
 omr_status omr_render_shape_mask_png_batch(omr_ctx* ctx, const omr_mask_job* jobs, int32_t n, uint8_t* out,

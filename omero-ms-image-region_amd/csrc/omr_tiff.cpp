@@ -78,6 +78,63 @@ omr_status write_tiff(const uint32_t* argb, int W, int H, uint8_t* out, size_t c
     return OMR_OK;
 }
 
+// Raw tiles (K12): one sample per pixel in the plane's own type, big-endian, BlackIsZero.
+// Every strip but the last holds at least 8 KiB (whole rows).
+struct RawTiff {
+    int bps, fmt, rps, ns;          // bytes per sample, SampleFormat, rows per strip, strips
+    size_t row, head, total;        // row bytes, bytes before the pixels, file bytes (0: invalid)
+};
+constexpr int kRawTags = 11;
+
+RawTiff raw_tiff_plan(int W, int H, int pixel_type) {
+    RawTiff t{};
+    t.bps = omr::bytes_per_pixel(pixel_type);
+    if (!t.bps || W <= 0 || H <= 0 || W > 65535 || H > 65535) return t;
+    t.fmt = pixel_type == OMR_PIXELS_FLOAT || pixel_type == OMR_PIXELS_DOUBLE ? 3
+            : pixel_type == OMR_PIXELS_INT8 || pixel_type == OMR_PIXELS_INT16 || pixel_type == OMR_PIXELS_INT32 ? 2 : 1;
+    t.row = (size_t)W * t.bps;
+    t.rps = (int)std::min<size_t>((size_t)H, (8192 + t.row - 1) / t.row);
+    t.ns = (H + t.rps - 1) / t.rps;
+    // header 8 + IFD (2 + 12 n + 4) + strip offsets / counts (in the tags themselves for one strip)
+    t.head = 8 + 2 + 12 * kRawTags + 4 + (t.ns > 1 ? (size_t)t.ns * 8 : 0);
+    const size_t total = t.head + t.row * (size_t)H;
+    t.total = total > 0xFFFFFFFFull ? 0 : total;   // classic TIFF: 32-bit offsets
+    return t;
+}
+
+void write_tiff_raw_head(const RawTiff& t, int W, int H, uint8_t* out) {
+    std::vector<uint8_t> b;
+    b.reserve(t.head);
+    b.push_back('M'); b.push_back('M'); put16(b, 42); put32(b, 8);
+    const uint32_t offs_off = 8 + 2 + 12 * kRawTags + 4, cnts_off = offs_off + 4 * (uint32_t)t.ns;
+    const uint32_t pix_off = (uint32_t)t.head;
+    auto tag = [&](uint16_t id, uint16_t type, uint32_t count, uint32_t value) {
+        put16(b, id); put16(b, type); put32(b, count);
+        if (type == 3 && count == 1) { put16(b, value); put16(b, 0); }
+        else put32(b, value);
+    };
+    put16(b, kRawTags);
+    tag(256, 4, 1, (uint32_t)W);                  // ImageWidth
+    tag(257, 4, 1, (uint32_t)H);                  // ImageLength
+    tag(258, 3, 1, 8u * (uint32_t)t.bps);         // BitsPerSample
+    tag(259, 3, 1, 1);                            // Compression: none
+    tag(262, 3, 1, 1);                            // PhotometricInterpretation: BlackIsZero
+    if (t.ns == 1) tag(273, 4, 1, pix_off);       // StripOffsets
+    else tag(273, 4, (uint32_t)t.ns, offs_off);
+    tag(277, 3, 1, 1);                            // SamplesPerPixel
+    tag(278, 4, 1, (uint32_t)t.rps);              // RowsPerStrip
+    if (t.ns == 1) tag(279, 4, 1, (uint32_t)(t.row * H));   // StripByteCounts
+    else tag(279, 4, (uint32_t)t.ns, cnts_off);
+    tag(284, 3, 1, 1);                            // PlanarConfiguration: chunky
+    tag(339, 3, 1, (uint32_t)t.fmt);              // SampleFormat: 1 unsigned, 2 signed, 3 IEEE
+    put32(b, 0);                                  // no next IFD
+    if (t.ns > 1) {
+        for (int s = 0; s < t.ns; ++s) put32(b, pix_off + (uint32_t)((size_t)s * t.rps * t.row));
+        for (int s = 0; s < t.ns; ++s) put32(b, (uint32_t)((size_t)std::min(t.rps, H - s * t.rps) * t.row));
+    }
+    std::memcpy(out, b.data(), b.size());
+}
+
 }  // namespace
 
 using namespace omr;
@@ -111,6 +168,29 @@ omr_status omr_encode_tiff_device(omr_ctx* ctx, const uint32_t* d_argb, int32_t 
     OMR_HIP(ctx, hipMemcpyAsync(host.data(), d_argb, host.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
     OMR_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return omr_encode_tiff(ctx, host.data(), width, height, out, cap, out_len);
+}
+
+size_t omr_tiff_raw_max_bytes(int32_t width, int32_t height, int32_t pixel_type) {
+    return raw_tiff_plan(width, height, pixel_type).total;
+}
+
+omr_status omr_encode_tiff_raw(const void* pixels, int32_t pixel_type, int32_t big_endian, int32_t width,
+                               int32_t height, uint8_t* out, size_t cap, size_t* out_len) {
+    const RawTiff t = raw_tiff_plan(width, height, pixel_type);
+    if (!pixels || !t.total) return OMR_INVALID_ARGUMENT;
+    if (out_len) *out_len = t.total;
+    if (!out || cap < t.total) return OMR_BUFFER_TOO_SMALL;
+    write_tiff_raw_head(t, width, height, out);
+    const uint8_t* src = static_cast<const uint8_t*>(pixels);
+    uint8_t* px = out + t.head;
+    const size_t bytes = t.row * (size_t)height;
+    if (big_endian || t.bps == 1) {
+        std::memcpy(px, src, bytes);
+    } else {
+        for (size_t i = 0; i < bytes; i += t.bps)
+            for (int k = 0; k < t.bps; ++k) px[i + k] = src[i + t.bps - 1 - k];
+    }
+    return OMR_OK;
 }
 
 }  // extern "C"

@@ -28,6 +28,30 @@ def histogram_bin_of(v, lo, hi, bins):
     return int(_lib.lib.omr_histogram_bin_of(float(v), float(lo), float(hi), int(bins)))
 
 
+_NP_PIXEL_TYPES = {"int8": _lib.PIXELS_INT8, "uint8": _lib.PIXELS_UINT8, "int16": _lib.PIXELS_INT16,
+                   "uint16": _lib.PIXELS_UINT16, "int32": _lib.PIXELS_INT32, "uint32": _lib.PIXELS_UINT32,
+                   "float32": _lib.PIXELS_FLOAT, "float64": _lib.PIXELS_DOUBLE}
+
+
+def encode_tiff_raw(array):
+    """A [h][w] numpy array of one of the eight pixel types, in either byte order, as a baseline
+    big-endian one-sample TIFF in that type (omr_encode_tiff_raw; host writer, no GPU)."""
+    import ctypes
+    import numpy as np
+    a = np.ascontiguousarray(array)
+    if a.ndim != 2 or a.dtype.name not in _NP_PIXEL_TYPES:
+        raise OmrError(_lib.INVALID_ARGUMENT, f"not a [h][w] array of a pixel type: {a.dtype} {a.shape}")
+    pt = _NP_PIXEL_TYPES[a.dtype.name]
+    big = a.dtype.byteorder == ">" or (a.dtype.byteorder == "=" and not np.little_endian) or a.dtype.itemsize == 1
+    h, w = a.shape
+    cap = _lib.lib.omr_tiff_raw_max_bytes(w, h, pt)
+    out = np.empty(max(cap, 1), dtype=np.uint8)
+    n = ctypes.c_size_t(0)
+    _lib.check(_lib.lib.omr_encode_tiff_raw(a.ctypes.data if a.size else None, pt, int(big), w, h,
+                                            out.ctypes.data, cap, ctypes.byref(n)))
+    return out[:n.value].tobytes()
+
+
 def histogram_json(ctx, pixbuf, z, c, t, bins=256, use_pixels_type_range=True, lo=None, hi=None, region=None):
     """The body of webgateway/histogram_json for plane (z, c, t) of a pixel buffer, as plain Python
     numbers.  Range: an explicit (lo, hi) when both are given, else the pixel-type range
@@ -42,7 +66,7 @@ def histogram_json(ctx, pixbuf, z, c, t, bins=256, use_pixels_type_range=True, l
             "rightOutsideCount": int(info["above"])}
 
 
-__all__ = ["_lib", "OmrError", "Context", "Renderer", "histogram_bin_of", "histogram_json", "thumbnail_size", "ChannelSettings", "ReverseIntensityContext",
+__all__ = ["_lib", "OmrError", "Context", "Renderer", "histogram_bin_of", "histogram_json", "encode_tiff_raw", "thumbnail_size", "ChannelSettings", "ReverseIntensityContext",
            "create_rendering_def", "flip", "split_html_color", "ImageRegionCtx",
            "ImageRegionRequestHandler", "InMemoryPixelBuffer", "LutProvider", "RequestError",
            "ShapeMaskCtx", "ShapeMaskRequestHandler", "PixelBuffer", "write_romio", "write_pyramid", "Batcher", "Pool"]

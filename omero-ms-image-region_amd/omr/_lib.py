@@ -92,6 +92,16 @@ class MaskJob(ctypes.Structure):
                 ("flip_v", ctypes.c_int32)]
 
 
+class RawTile(ctypes.Structure):
+    _fields_ = [("d_plane", ctypes.c_void_p), ("pitch_px", ctypes.c_int64), ("x", ctypes.c_int32),
+                ("y", ctypes.c_int32)]
+
+
+class RawTileRequest(ctypes.Structure):
+    _fields_ = [("z", ctypes.c_int32), ("c", ctypes.c_int32), ("t", ctypes.c_int32), ("x", ctypes.c_int32),
+                ("y", ctypes.c_int32)]
+
+
 class Region(ctypes.Structure):
     _fields_ = [("x", ctypes.c_int32), ("y", ctypes.c_int32),
                 ("width", ctypes.c_int32), ("height", ctypes.c_int32)]
@@ -253,6 +263,13 @@ _SIGS = {
                                          _i32]),
     "omr_encode_png_batch_device": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _sz, _vp, _vp, _vp]),
     "omr_png_batch_max_bytes": (_sz, [_i32, _i32, _i32, _i32]),
+    "omr_png_gray_batch_max_bytes": (_sz, [_i32, _i32, _i32, _i32]),
+    "omr_encode_png_gray_batch_device": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _sz, _vp, _vp, _vp]),
+    "omr_pixel_buffer_tiles_png": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _sz, _vp, _vp, _vp]),
+    "omr_tiff_raw_max_bytes": (_sz, [_i32, _i32, _i32]),
+    "omr_encode_tiff_raw": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _sz, ctypes.POINTER(_sz)]),
+    "omr_pixel_buffer_tile_tiff": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _sz,
+                                          ctypes.POINTER(_sz)]),
     "omr_render_shape_mask_png_batch": (_i32, [_vp, ctypes.POINTER(MaskJob), _i32, _vp, _sz, _vp, _vp, _vp]),
     "omr_split_html_color": (_i32, [ctypes.c_char_p, ctypes.POINTER(_i32)]),
     "omr_shape_mask_fill_color": (_i32, [_i32, _i32, ctypes.c_char_p, _vp]),

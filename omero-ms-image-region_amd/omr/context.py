@@ -177,8 +177,8 @@ class Context:
 
     def kernel_timings(self, cap=1 << 16):
         """[(ms, kind)] of the timed hot-kernel launches since the last call (kind 2 render,
-        3 projection, 4 jpeg, 10 fused scaled render, 11 ARGB scaler, 12 pyramid levels); synchronises
-        the stream."""
+        3 projection, 4 jpeg, 10 fused scaled render, 11 ARGB scaler, 12 pyramid levels, 20..26 the
+        batched PNG stages, 27 the grey wave filter); synchronises the stream."""
         ms = np.zeros(cap, np.float32)
         kind = np.zeros(cap, np.int32)
         n = lib.omr_ctx_kernel_timings(self.h, ms.ctypes.data, kind.ctypes.data, cap)
@@ -502,6 +502,21 @@ class Context:
         check(lib.omr_encode_png_batch_device(self.h, _ptr(d_argb), tile_stride, n_tiles, width, height,
                                               _ptr(d_out), d_out.numel() * d_out.element_size(), _ptr(d_offsets),
                                               _ptr(d_lengths), _ptr(d_status)), self.h)
+
+    def encode_png_gray_batch_device(self, tiles, pixel_type, width, height, d_out, d_offsets=None, d_lengths=None,
+                                     d_status=None, big_endian=True):
+        """Batched greyscale PNG of raw plane regions (K12).  tiles: [(plane, pitch_px, x, y)] with
+        plane a device tensor (or address) of the plane's first pixel; every tile is the width x
+        height region at (x, y).  Files into d_out (device bytes) as encode_png_batch_device
+        packs them; asynchronous."""
+        n = len(tiles)
+        tab = (_lib.RawTile * max(n, 1))()
+        for i, (plane, pitch, x, y) in enumerate(tiles):
+            tab[i].d_plane, tab[i].pitch_px, tab[i].x, tab[i].y = _ptr(plane), int(pitch), int(x), int(y)
+        check(lib.omr_encode_png_gray_batch_device(self.h, ctypes.addressof(tab), n, int(pixel_type),
+                                                   int(bool(big_endian)), width, height, _ptr(d_out),
+                                                   d_out.numel() * d_out.element_size() if d_out is not None else 0,
+                                                   _ptr(d_offsets), _ptr(d_lengths), _ptr(d_status)), self.h)
 
     def render_shape_mask_png_batch(self, masks, cap=None):
         """masks: [(bits, width, height, rgba, flip_h, flip_v)] -> [(status, png bytes)] (host in/out)."""

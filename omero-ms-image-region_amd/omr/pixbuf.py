@@ -141,6 +141,43 @@ class PixelBuffer:
         return counts, _info_dict(info), {"min": stats.min, "max": stats.max, "count": int(stats.count),
                                           "nan_count": int(stats.nan_count)}
 
+    def tiles_png(self, ctx, reqs, w, h, cap=None):
+        """Raw tiles as greyscale PNG files (omr_pixel_buffer_tiles_png): reqs = [(z, c, t, x, y)],
+        every tile w x h; returns the files as a list of bytes.  When a tile failed (one outside
+        the image: INVALID_ARGUMENT) it raises OmrError with .statuses (per tile) and .files (the
+        other tiles' bytes, b"" for the failed ones)."""
+        n = len(reqs)
+        tab = (_lib.RawTileRequest * max(n, 1))()
+        for i, r in enumerate(reqs):
+            tab[i].z, tab[i].c, tab[i].t, tab[i].x, tab[i].y = [int(v) for v in r]
+        if cap is None:
+            cap = n * lib.omr_png_gray_batch_max_bytes(max(1, int(w)), max(1, int(h)),
+                                                       min(_lib.BYTES_PER_PIXEL[self.pixel_type], 2), 1)
+        out = np.empty(max(cap, 1), dtype=np.uint8)
+        offs = np.zeros(max(n, 1), np.uint64)
+        lens = np.zeros(max(n, 1), np.uint32)
+        stat = np.zeros(max(n, 1), np.int32)
+        _lib.check(lib.omr_pixel_buffer_tiles_png(ctx.h, self.h, ctypes.addressof(tab), n, int(w), int(h),
+                                                  out.ctypes.data, cap, offs.ctypes.data, lens.ctypes.data,
+                                                  stat.ctypes.data), ctx.h)
+        files = [out[int(offs[i]):int(offs[i]) + int(lens[i])].tobytes() if stat[i] == 0 else b"" for i in range(n)]
+        if n and stat[:n].any():
+            bad = [i for i in range(n) if stat[i]]
+            err = _lib.OmrError(int(stat[bad[0]]), f"raw tiles {bad} failed")
+            err.statuses, err.files = [int(s) for s in stat[:n]], files
+            raise err
+        return files
+
+    def tile_tiff(self, z, c, t, x, y, w, h):
+        """The raw tile as a baseline big-endian TIFF in the buffer's pixel type
+        (omr_pixel_buffer_tile_tiff)."""
+        cap = lib.omr_tiff_raw_max_bytes(int(w), int(h), self.pixel_type)
+        out = np.empty(max(cap, 1), dtype=np.uint8)
+        n = ctypes.c_size_t(0)
+        _lib.check(lib.omr_pixel_buffer_tile_tiff(self.h, z, c, t, x, y, int(w), int(h), out.ctypes.data, cap,
+                                                  ctypes.byref(n)))
+        return out[:n.value].tobytes()
+
     def plane_offset(self, z, c, t):
         return lib.omr_pixel_buffer_plane_offset(self.h, z, c, t)
 
