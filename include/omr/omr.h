@@ -124,7 +124,8 @@ void*       omr_ctx_get_stream(omr_ctx* ctx);
  * kind_out (optional) receives 2 = render, 3 = projection, 4 = jpeg per entry (10 = fused scaled
  * render, 11 = ARGB scaler: omr_render_scaled_batch_device; 12 = pyramid levels:
  * omr_pyramid_build_device; 20..26 = the batched PNG stages and 27 = the grey wave filter:
- * omr_encode_png_gray_batch_device).
+ * omr_encode_png_gray_batch_device; 30 = LZW decode and 31 = TIFF place:
+ * omr_tiff_image_read_regions_device).
  */
 omr_status  omr_ctx_enable_kernel_timing(omr_ctx* ctx, int32_t enable);
 int32_t     omr_ctx_kernel_timings(omr_ctx* ctx, float* ms_out, int32_t* kind_out, int32_t cap);
@@ -986,6 +987,95 @@ omr_status omr_create_rendering_def(int32_t pixel_type, int32_t size_c, omr_quan
 omr_status omr_update_settings(const omr_image_region_ctx* ctx, int32_t size_c, omr_quantum_def* qdef,
                                omr_channel_binding* channels, const omr_lut_provider* luts,
                                char* err, size_t err_cap);
+
+/* ---- tiled TIFF / OME-TIFF pixel data, LZW decoded on the device (K13) ------------------- */
+/*
+ * The second backend of PixelsService.getPixelBuffer: pyramidal OME-TIFF
+ * as raw2ometiff writes it -- one IFD per plane in the main chain, the lower resolutions in each
+ * IFD's SubIFDs (tag 330).  The TIFF image is a type of its own beside omr_pixel_buffer; what it
+ * reads feeds the device-level render and encode calls by composition.
+ *
+ * Supported: classic TIFF and BigTIFF in either byte order; one sample per pixel; BitsPerSample
+ * 8 / 16 / 32 / 64 with SampleFormat 1 / 2 / 3 (the eight OMR_PIXELS_* types); tiles or strips (a
+ * strip is a full-width segment); Compression 1 (none) and 5 (LZW); Predictor 1, and 2 for 8-, 16-
+ * and 32-bit samples; FillOrder 1; a segment with byte count 0 reads as zeros.  All planes have the
+ * same size, type, compression, segment geometry and level count.  OME-XML is not parsed: the
+ * caller gives Z, C, T and the dimension order (one of the six OME orders, "XYZCT" being the ROMIO
+ * order), and plane (z, c, t) is the main-chain IFD at the index the order gives.
+ *
+ * open: OMR_NOT_FOUND for a missing file; OMR_INVALID_ARGUMENT for anything unsupported (another
+ * compression, predictor 3, predictor 2 with 64-bit samples, several samples per pixel, FillOrder
+ * 2, fewer IFDs than Z*C*T, planes that disagree, a segment above 256 MiB decoded); OMR_INTERNAL
+ * for a corrupt file (an offset or count past the end of the file, an IFD chain that loops, a
+ * count whose product overflows).  The file is read with pread, every offset bounds-checked.
+ * Read-only; safe to share between contexts and threads.
+ */
+typedef struct omr_tiff_image omr_tiff_image;
+typedef struct omr_tiff_info {
+    int32_t size_x, size_y, size_z, size_c, size_t_;   /* level 0 */
+    int32_t pixel_type;                                /* OMR_PIXELS_* */
+    int32_t big_endian;                                /* the file's byte order ("MM": 1) */
+    int32_t n_levels;                                  /* 1 + SubIFDs per plane */
+    int32_t compression, predictor;                    /* TIFF tag values: 1 / 5, 1 / 2 */
+    int32_t tiled;                                     /* level 0: 1 tiles, 0 strips */
+    int32_t segment_width, segment_height;             /* level 0: tile size, or size_x and RowsPerStrip */
+    int32_t big_tiff;
+} omr_tiff_info;
+omr_status omr_tiff_image_open(const char* path, int32_t size_z, int32_t size_c, int32_t size_t_,
+                               const char* dimension_order, omr_tiff_image** out);
+void       omr_tiff_image_close(omr_tiff_image* img);
+omr_status omr_tiff_image_info(const omr_tiff_image* img, omr_tiff_info* info);
+/* (width, height) per level as stored in the file (not size >> k): up to cap_pairs pairs into
+ * sizes_out; returns the level count, or -OMR_INVALID_ARGUMENT. */
+int32_t    omr_tiff_image_level_sizes(const omr_tiff_image* img, int32_t* sizes_out, int32_t cap_pairs);
+/*
+ * The host route (no GPU): the bounds rule and packed rows of omr_pixel_buffer_get_tile at
+ * resolution `level`, bytes in the file's byte order, decoded with a plain serial LZW decoder.
+ * The reference the device route is tested against, and the route of single reads.  TIFF LZW as
+ * libtiff reads it: MSB-first codes from 9 bits, 256 Clear, 257 EOI, first entry 258, early change
+ * (10 bits once the next free entry is 511, 11 at 1023, 12 at 2047).  Decoding ends at EOI or once
+ * the segment's size (tile_w * tile_h * bpp, or rows_in_strip * W * bpp) is produced; a string
+ * that overruns it is cut.  OMR_INTERNAL: fewer bytes than that, a code above the next free entry,
+ * an old-style LSB-first stream, an I/O error.
+ */
+omr_status omr_tiff_image_get_tile(const omr_tiff_image* img, int32_t level, int32_t z, int32_t c, int32_t t,
+                                   int32_t x, int32_t y, int32_t w, int32_t h, void* dst, size_t cap);
+/* The host decoder alone: one stream into exactly `expected` bytes (OMR_OK / OMR_INTERNAL). */
+omr_status omr_lzw_decode_host(const uint8_t* src, size_t length, uint8_t* dst, size_t expected);
+/*
+ * K13a alone: n independent TIFF LZW streams, stream i at d_src + d_offsets[i], d_lengths[i] bytes
+ * (below 512 MiB), decoded into d_dst + d_dst_offsets[i], at most d_expected[i] bytes (below 1 GiB;
+ * nothing is written behind them); d_status[i] = OMR_OK or OMR_INTERNAL (the cases of the host
+ * decoder), one segment's failure leaving the others alone.  All tables in device memory.
+ * Asynchronous on the context stream; omr_ctx_kernel_timings reports kind 30.
+ */
+omr_status omr_lzw_decode_batch_device(omr_ctx* ctx, const uint8_t* d_src, const uint64_t* d_offsets,
+                                       const uint32_t* d_lengths, const uint32_t* d_expected, int32_t n,
+                                       uint8_t* d_dst, const uint64_t* d_dst_offsets, int32_t* d_status);
+/*
+ * n regions of one level, all width x height: region i = reqs[i] (z, c, t, x, y; the get_tile
+ * bounds rule, else OMR_INVALID_ARGUMENT and nothing is read) lands at d_dst + i *
+ * region_stride_bytes (a multiple of the sample size, at least width * height * bpp; d_dst aligned
+ * to the sample size) as height rows of width pixels in the file's byte order.  The host lists the
+ * segments the regions touch -- one needed by several requests is read and decoded once -- preads
+ * their compressed bytes into pinned staging and sends them in one copy with the segment table;
+ * K13a decodes the LZW segments into scratch (kind 30), K13b undoes predictor 2, crops and stores
+ * (kind 31); uncompressed segments go through K13b from the uploaded bytes.  Large calls are
+ * worked off in groups.  Synchronous; OMR_INTERNAL when a segment is corrupt.
+ */
+omr_status omr_tiff_image_read_regions_device(omr_ctx* ctx, const omr_tiff_image* img, int32_t level,
+                                              const omr_raw_tile_request* reqs, int32_t n, int32_t width,
+                                              int32_t height, void* d_dst, int64_t region_stride_bytes);
+/*
+ * omr_render_pixel_buffer_tiles for a TIFF image level: the active channels' regions are read as
+ * [tile][channel][h][w] (16-byte aligned strides) and rendered by
+ * omr_render_batch_strided_device with the file's byte order.  size_c must be the image's.
+ */
+omr_status omr_render_tiff_tiles(omr_ctx* ctx, const omr_tiff_image* img, int32_t level,
+                                 const omr_quantum_def* qdef, const omr_channel_binding* channels,
+                                 int32_t size_c, const omr_tile_request* reqs, int32_t n, int32_t width,
+                                 int32_t height, int32_t flip_h, int32_t flip_v, uint32_t* argb_out,
+                                 int32_t out_on_device);
 
 #ifdef __cplusplus
 }

@@ -175,6 +175,9 @@ struct Ctx {
     void* pixbuf_state = nullptr;
     bool pixbuf_direct = true;   // DMA tile rows from a registered file mapping when possible
     void (*pixbuf_state_free)(void*) = nullptr;
+    // tiled TIFF reader (omr_tiffread.cpp): pinned and device staging, scratch for decoded segments
+    void* tiff_state = nullptr;
+    void (*tiff_state_free)(void*) = nullptr;
 };
 
 // Bracket one hot-kernel launch with events when timing is enabled.
@@ -287,6 +290,24 @@ omr_status validate_png_gray(Ctx* ctx, int32_t pixel_type, int32_t width, int32_
 
 // K11 (omr_pyramid.hip): 1 <= n_levels <= min(OMR_PYRAMID_MAX_LEVELS, 1 + floor(log2(min(w, h)))).
 bool pyramid_levels_valid(int64_t w, int64_t h, int64_t n_levels);
+
+// K13 (omr_tiffread.hip).  One placement: the rectangle [x0, x1) x [y0, y1) of a decoded (or stored)
+// segment whose rows are seg_w samples apart, into dst (the address of sample (x0, y0)) with rows
+// dst_pitch samples apart; src == nullptr reads as zeros (a segment with byte count 0).
+struct TiffPlace {
+    const uint8_t* src;
+    uint8_t* dst;
+    int32_t seg_w, dst_pitch;
+    int32_t x0, x1, y0, y1;
+};
+// K13a: n LZW streams (omr_lzw_decode_batch_device after its argument check).
+omr_status launch_lzw_decode(Ctx* ctx, const uint8_t* d_src, const uint64_t* d_offsets, const uint32_t* d_lengths,
+                             const uint32_t* d_expected, int32_t n, uint8_t* d_dst, const uint64_t* d_dst_offsets,
+                             int32_t* d_status);
+// K13b: n placements (a device table) of samples bps bytes wide, none taller than max_rows; swap:
+// the file's byte order is not the host's (it matters to predictor 2 only).
+omr_status launch_tiff_place(Ctx* ctx, const TiffPlace* d_places, int32_t n, int32_t max_rows, int32_t bps,
+                             int32_t predictor, bool swap);
 
 #define OMR_HIP(ctx, expr)                                         \
     do {                                                            \

@@ -1,0 +1,808 @@
+// omr_tiffread.cpp — K13, host half: tiled TIFF / OME-TIFF pixel data (include/omr/omr.h).
+//
+// The second backend of pixelsService.getPixelBuffer: pyramidal OME-TIFF
+// as raw2ometiff writes it, one IFD per plane and the lower resolutions in SubIFDs.  This file
+// holds the parser (pread, every offset bounds-checked: a file is user-uploaded data), the plain
+// serial LZW decoder of the host route (omr_tiff_image_get_tile: the reference of the tests and
+// the route of single reads) and the staging of the device route: the segments the requested
+// regions touch are listed once each, their compressed bytes go to pinned memory and in one copy
+// to the device with the segment table, K13a decodes them and K13b places them (omr_tiffread.hip).
+#include "omr_internal.h"
+
+#include <fcntl.h>
+#include <sys/stat.h>
+#include <unistd.h>
+
+#include <atomic>
+#include <cerrno>
+#include <memory>
+#include <thread>
+#include <unordered_map>
+#include <unordered_set>
+
+namespace {
+
+constexpr uint64_t kMaxSegmentBytes = (uint64_t)256 << 20;   // decoded size of one segment
+constexpr uint64_t kMaxStreamBytes = ((uint64_t)512 << 20) - 1;
+constexpr uint32_t kMaxIfds = 1u << 20;
+
+struct Level {
+    int32_t w = 0, h = 0;          // image size at this level
+    int32_t seg_w = 0, seg_h = 0;  // tile size, or (w, rows per strip)
+    int32_t across = 0, down = 0;
+    bool tiled = false;
+    bool operator==(const Level& o) const {
+        return w == o.w && h == o.h && seg_w == o.seg_w && seg_h == o.seg_h && tiled == o.tiled;
+    }
+};
+
+struct Segments {
+    std::vector<uint64_t> off, cnt;   // [down][across]
+};
+
+}  // namespace
+
+struct omr_tiff_image {
+    int fd = -1;
+    uint64_t file_len = 0;
+    bool big = false, bigtiff = false;
+    int32_t sz = 0, sc = 0, st = 0;
+    int64_t stride_z = 0, stride_c = 0, stride_t = 0;   // plane index = z*stride_z + c*stride_c + t*stride_t
+    int32_t pt = 0, bpp = 0, compression = 1, predictor = 1;
+    std::vector<Level> levels;
+    std::vector<std::vector<Segments>> segs;   // [plane][level]
+    ~omr_tiff_image() {
+        if (fd >= 0) ::close(fd);
+    }
+};
+
+namespace {
+
+// pread until done (short reads, EINTR).
+bool read_full(int fd, void* dst, size_t n, uint64_t off) {
+    uint8_t* d = static_cast<uint8_t*>(dst);
+    while (n) {
+        const ssize_t r = ::pread(fd, d, n, (off_t)off);
+        if (r < 0) {
+            if (errno == EINTR) continue;
+            return false;
+        }
+        if (r == 0) return false;
+        d += r;
+        n -= (size_t)r;
+        off += (uint64_t)r;
+    }
+    return true;
+}
+
+struct Ifd {
+    uint64_t w = 0, h = 0, bps = 1, comp = 1, fill = 1, spp = 1, rps = 0xFFFFFFFFull, pred = 1, tw = 0, th = 0, fmt = 1;
+    bool has_tw = false, has_th = false;
+    std::vector<uint64_t> strip_off, strip_cnt, tile_off, tile_cnt, sub;
+};
+
+struct Parser {
+    int fd;
+    uint64_t len;
+    bool big = false, bigtiff = false;
+
+    bool rd(uint64_t off, void* dst, uint64_t n) const {
+        if (off > len || n > len - off) return false;
+        return n == 0 || read_full(fd, dst, (size_t)n, off);
+    }
+    uint64_t u(const uint8_t* p, int n) const {
+        uint64_t v = 0;
+        for (int k = 0; k < n; ++k) v = v << 8 | p[big ? k : n - 1 - k];
+        return v;
+    }
+    // The values of one IFD entry (e: its 12 or 20 bytes).  OMR_INTERNAL: count or offset past the file.
+    omr_status values(const uint8_t* e, std::vector<uint64_t>& out) const {
+        const uint32_t type = (uint32_t)u(e + 2, 2);
+        const uint64_t count = bigtiff ? u(e + 4, 8) : u(e + 4, 4);
+        const uint8_t* field = e + (bigtiff ? 12 : 8);
+        const int field_bytes = bigtiff ? 8 : 4;
+        int ts;
+        switch (type) {
+        case 1: ts = 1; break;
+        case 3: ts = 2; break;
+        case 4: case 13: ts = 4; break;
+        case 16: case 18: ts = 8; break;
+        default: return OMR_INVALID_ARGUMENT;
+        }
+        if (count > len) return OMR_INTERNAL;           // count * ts <= 8 * len: no overflow below
+        const uint64_t bytes = count * (uint64_t)ts;
+        std::vector<uint8_t> buf;
+        const uint8_t* src = field;
+        if (bytes > (uint64_t)field_bytes) {
+            buf.resize((size_t)bytes);
+            if (!rd(u(field, field_bytes), buf.data(), bytes)) return OMR_INTERNAL;
+            src = buf.data();
+        }
+        out.resize((size_t)count);
+        for (uint64_t k = 0; k < count; ++k) out[(size_t)k] = u(src + k * ts, ts);
+        return OMR_OK;
+    }
+    omr_status scalar(const uint8_t* e, uint64_t& v) const {
+        std::vector<uint64_t> vals;
+        const omr_status st = values(e, vals);
+        if (st) return st;
+        if (vals.empty()) return OMR_INTERNAL;
+        v = vals[0];
+        return OMR_OK;
+    }
+    // Entry count and the offset of the next IFD; with `ifd`, the tags too.
+    omr_status read_ifd(uint64_t off, Ifd* ifd, uint64_t& next) const {
+        uint8_t head[8];
+        const int cb = bigtiff ? 8 : 2, es = bigtiff ? 20 : 12, nb = bigtiff ? 8 : 4;
+        if (!rd(off, head, (uint64_t)cb)) return OMR_INTERNAL;
+        const uint64_t n = u(head, cb);
+        if (n > len / (uint64_t)es) return OMR_INTERNAL;
+        const uint64_t body = n * (uint64_t)es;
+        uint8_t nx[8];
+        if (!rd(off + (uint64_t)cb + body, nx, (uint64_t)nb)) return OMR_INTERNAL;   // off + cb <= len (rd above)
+        next = u(nx, nb);
+        if (!ifd) return OMR_OK;
+        std::vector<uint8_t> ent((size_t)body);
+        if (!rd(off + (uint64_t)cb, ent.data(), body)) return OMR_INTERNAL;
+        for (uint64_t k = 0; k < n; ++k) {
+            const uint8_t* e = ent.data() + k * es;
+            omr_status st = OMR_OK;
+            switch ((uint32_t)u(e, 2)) {
+            case 256: st = scalar(e, ifd->w); break;
+            case 257: st = scalar(e, ifd->h); break;
+            case 258: st = scalar(e, ifd->bps); break;
+            case 259: st = scalar(e, ifd->comp); break;
+            case 266: st = scalar(e, ifd->fill); break;
+            case 273: st = values(e, ifd->strip_off); break;
+            case 277: st = scalar(e, ifd->spp); break;
+            case 278: st = scalar(e, ifd->rps); break;
+            case 279: st = values(e, ifd->strip_cnt); break;
+            case 317: st = scalar(e, ifd->pred); break;
+            case 322: st = scalar(e, ifd->tw); ifd->has_tw = true; break;
+            case 323: st = scalar(e, ifd->th); ifd->has_th = true; break;
+            case 324: st = values(e, ifd->tile_off); break;
+            case 325: st = values(e, ifd->tile_cnt); break;
+            case 330: st = values(e, ifd->sub); break;
+            case 339: st = scalar(e, ifd->fmt); break;
+            default: break;
+            }
+            if (st) return st;
+        }
+        return OMR_OK;
+    }
+};
+
+int pixel_type_of(uint64_t bps, uint64_t fmt) {
+    if (fmt == 1) return bps == 8 ? OMR_PIXELS_UINT8 : bps == 16 ? OMR_PIXELS_UINT16 : bps == 32 ? OMR_PIXELS_UINT32 : -1;
+    if (fmt == 2) return bps == 8 ? OMR_PIXELS_INT8 : bps == 16 ? OMR_PIXELS_INT16 : bps == 32 ? OMR_PIXELS_INT32 : -1;
+    if (fmt == 3) return bps == 32 ? OMR_PIXELS_FLOAT : bps == 64 ? OMR_PIXELS_DOUBLE : -1;
+    return -1;
+}
+
+// Rows of segment row sy (the last strip of an image is short; tiles are stored whole).
+inline int32_t rows_in_segment(const Level& L, int32_t sy) {
+    return L.tiled ? L.seg_h : std::min(L.seg_h, L.h - sy * L.seg_h);
+}
+
+// One IFD into the image: geometry, format and the segment table, all checked.
+omr_status take_ifd(const Parser& P, const Ifd& f, Level& L, Segments& S, int32_t& pt, int32_t& comp, int32_t& pred) {
+    if (f.spp != 1 || f.fill != 1) return OMR_INVALID_ARGUMENT;
+    if (f.comp != 1 && f.comp != 5) return OMR_INVALID_ARGUMENT;
+    if (f.pred != 1 && f.pred != 2) return OMR_INVALID_ARGUMENT;
+    pt = pixel_type_of(f.bps, f.fmt);
+    if (pt < 0) return OMR_INVALID_ARGUMENT;
+    if (f.pred == 2 && f.bps == 64) return OMR_INVALID_ARGUMENT;
+    if (f.w < 1 || f.h < 1 || f.w > 0x7FFFFFFFull || f.h > 0x7FFFFFFFull) return OMR_INVALID_ARGUMENT;
+    comp = (int32_t)f.comp;
+    pred = (int32_t)f.pred;
+    const uint64_t bpp = f.bps / 8;
+    L.w = (int32_t)f.w;
+    L.h = (int32_t)f.h;
+    const std::vector<uint64_t>*off, *cnt;
+    if (f.has_tw || f.has_th || !f.tile_off.empty()) {
+        if (f.tw < 1 || f.th < 1 || f.tw > 0x7FFFFFFFull || f.th > 0x7FFFFFFFull) return OMR_INTERNAL;
+        L.tiled = true;
+        L.seg_w = (int32_t)f.tw;
+        L.seg_h = (int32_t)f.th;
+        off = &f.tile_off;
+        cnt = &f.tile_cnt;
+    } else {
+        if (f.rps < 1) return OMR_INTERNAL;
+        L.tiled = false;
+        L.seg_w = L.w;
+        L.seg_h = (int32_t)std::min<uint64_t>(f.rps, f.h);
+        off = &f.strip_off;
+        cnt = &f.strip_cnt;
+    }
+    L.across = (int32_t)((f.w + (uint64_t)L.seg_w - 1) / (uint64_t)L.seg_w);
+    L.down = (int32_t)((f.h + (uint64_t)L.seg_h - 1) / (uint64_t)L.seg_h);
+    uint64_t n_seg, seg_bytes;
+    if (__builtin_mul_overflow((uint64_t)L.across, (uint64_t)L.down, &n_seg)) return OMR_INTERNAL;
+    if (__builtin_mul_overflow((uint64_t)L.seg_w, (uint64_t)L.seg_h, &seg_bytes) ||
+        __builtin_mul_overflow(seg_bytes, bpp, &seg_bytes))
+        return OMR_INTERNAL;
+    if (off->size() != n_seg || cnt->size() != n_seg) return OMR_INTERNAL;
+    if (seg_bytes > kMaxSegmentBytes) return OMR_INVALID_ARGUMENT;
+    for (uint64_t k = 0; k < n_seg; ++k) {
+        const uint64_t o = (*off)[(size_t)k], c = (*cnt)[(size_t)k];
+        if (c == 0) continue;                                        // reads as zeros
+        if (o > P.len || c > P.len - o) return OMR_INTERNAL;
+        if (comp == 1) {
+            const uint64_t need = (uint64_t)rows_in_segment(L, (int32_t)(k / (uint64_t)L.across)) * L.seg_w * bpp;
+            if (c < need) return OMR_INTERNAL;
+        } else if (c > kMaxStreamBytes) {
+            return OMR_INVALID_ARGUMENT;
+        }
+    }
+    S.off = *off;
+    S.cnt = *cnt;
+    return OMR_OK;
+}
+
+// TIFF LZW, serial (the rules: omr.h at omr_tiff_image_get_tile).  true: exactly `expected` bytes out.
+bool lzw_decode(const uint8_t* s, size_t len, uint8_t* d, size_t expected) {
+    if (len >= 2 && s[0] == 0 && (s[1] & 1)) return false;   // old-style LSB-first stream
+    uint16_t prefix[4096], length[4096];
+    uint8_t suffix[4096], first[4096];
+    const uint64_t nbits = (uint64_t)len * 8;
+    uint64_t bit = 0;
+    uint32_t next = 258, width = 9;
+    int32_t prev = -1;
+    size_t out = 0;
+    auto len_of = [&](uint32_t c) -> uint32_t { return c < 256 ? 1u : length[c]; };
+    auto first_of = [&](uint32_t c) -> uint8_t { return c < 256 ? (uint8_t)c : first[c]; };
+    while (out < expected) {
+        if (bit + width > nbits) return false;                // the stream ends early
+        const uint64_t b = bit >> 3;
+        uint32_t v = (uint32_t)s[b] << 16;
+        if (b + 1 < len) v |= (uint32_t)s[b + 1] << 8;
+        if (b + 2 < len) v |= (uint32_t)s[b + 2];
+        const uint32_t code = (v >> (24 - width - (uint32_t)(bit & 7))) & ((1u << width) - 1);
+        bit += width;
+        if (code == 256) {
+            next = 258;
+            width = 9;
+            prev = -1;
+            continue;
+        }
+        if (code == 257) return false;                        // EOI before the segment is full
+        uint32_t n;        // length of this code's string
+        uint8_t f;         // and its first byte
+        if (prev < 0) {
+            if (code > 255) return false;
+            n = 1;
+            f = (uint8_t)code;
+        } else if (code < next) {
+            n = len_of(code);
+            f = first_of(code);
+        } else if (code == next && next < 4096) {             // the string of prev + its own first byte
+            n = len_of((uint32_t)prev) + 1;
+            f = first_of((uint32_t)prev);
+        } else {
+            return false;                                     // a code above the next free entry
+        }
+        if (prev >= 0 && next < 4096) {
+            prefix[next] = (uint16_t)prev;
+            suffix[next] = f;
+            length[next] = (uint16_t)(len_of((uint32_t)prev) + 1);
+            first[next] = first_of((uint32_t)prev);
+            ++next;
+            width = next < 511 ? 9 : next < 1023 ? 10 : next < 2047 ? 11 : 12;
+        }
+        size_t p = out + n;                                   // backwards along the prefix chain
+        uint32_t c = code;
+        for (uint32_t k = n; k > 1; --k) {
+            --p;
+            if (p < expected) d[p] = suffix[c];
+            c = prefix[c];
+        }
+        --p;
+        if (p < expected) d[p] = (uint8_t)c;
+        out += n;
+        prev = (int32_t)code;
+    }
+    return true;
+}
+
+template <typename T>
+T swap_bytes(T v) {
+    if (sizeof(T) == 2) return (T)__builtin_bswap16((uint16_t)v);
+    if (sizeof(T) == 4) return (T)__builtin_bswap32((uint32_t)v);
+    return v;
+}
+
+// Undo predictor 2 on `rows` rows of `w` samples: running sums in the sample's own width.
+template <typename T>
+void unpredict(uint8_t* buf, int64_t rows, int64_t w, bool swap) {
+    for (int64_t r = 0; r < rows; ++r) {
+        uint8_t* row = buf + (size_t)(r * w) * sizeof(T);
+        T acc = 0;
+        for (int64_t x = 0; x < w; ++x) {
+            T v;
+            std::memcpy(&v, row + x * sizeof(T), sizeof(T));
+            if (swap) v = swap_bytes(v);
+            acc = (T)(acc + v);
+            v = swap ? swap_bytes(acc) : acc;
+            std::memcpy(row + x * sizeof(T), &v, sizeof(T));
+        }
+    }
+}
+
+bool host_little_endian() {
+    const uint16_t one = 1;
+    uint8_t b;
+    std::memcpy(&b, &one, 1);
+    return b == 1;
+}
+
+int64_t plane_index(const omr_tiff_image* im, int32_t z, int32_t c, int32_t t) {
+    return z * im->stride_z + c * im->stride_c + t * im->stride_t;
+}
+
+bool region_in_bounds(const omr_tiff_image* im, const Level& L, int32_t z, int32_t c, int32_t t, int32_t x, int32_t y,
+                      int32_t w, int32_t h) {
+    return z >= 0 && z < im->sz && c >= 0 && c < im->sc && t >= 0 && t < im->st && x >= 0 && y >= 0 && w >= 0 &&
+           h >= 0 && (int64_t)x + w <= L.w && (int64_t)y + h <= L.h;
+}
+
+// Segment (sx, sy) of a plane, decoded and with the predictor undone: rows * seg_w samples.
+omr_status load_segment(const omr_tiff_image* im, const Level& L, const Segments& S, int32_t sx, int32_t sy,
+                        std::vector<uint8_t>& comp, std::vector<uint8_t>& out) {
+    const size_t k = (size_t)sy * L.across + sx;
+    const int32_t rows = rows_in_segment(L, sy);
+    const size_t expected = (size_t)rows * L.seg_w * im->bpp;
+    out.assign(expected, 0);
+    const uint64_t cnt = S.cnt[k];
+    if (cnt == 0) return OMR_OK;
+    if (im->compression == 1) {
+        if (!read_full(im->fd, out.data(), expected, S.off[k])) return OMR_INTERNAL;
+    } else {
+        comp.resize((size_t)cnt);
+        if (!read_full(im->fd, comp.data(), (size_t)cnt, S.off[k])) return OMR_INTERNAL;
+        if (!lzw_decode(comp.data(), (size_t)cnt, out.data(), expected)) return OMR_INTERNAL;
+    }
+    if (im->predictor == 2) {
+        const bool swap = im->big == host_little_endian();
+        if (im->bpp == 1) unpredict<uint8_t>(out.data(), rows, L.seg_w, false);
+        else if (im->bpp == 2) unpredict<uint16_t>(out.data(), rows, L.seg_w, swap);
+        else if (im->bpp == 4) unpredict<uint32_t>(out.data(), rows, L.seg_w, swap);
+    }
+    return OMR_OK;
+}
+
+// ---- device route: staging of one context -------------------------------------------------------
+
+struct TiffPipe {
+    void* pin = nullptr;      // compressed bytes + tables (+ the statuses coming back)
+    void* d_in = nullptr;
+    size_t in_cap = 0;
+    void* d_scratch = nullptr;   // decoded segments, tile-packed
+    size_t scratch_cap = 0;
+    void* d_regions = nullptr;   // omr_render_tiff_tiles: [tile][channel][h][w]
+    size_t regions_cap = 0;
+    void* d_out = nullptr;       // and its ARGB when the caller's output is host memory
+    size_t out_cap = 0;
+    ~TiffPipe() {
+        if (pin) (void)hipHostFree(pin);
+        for (void* p : {d_in, d_scratch, d_regions, d_out})
+            if (p) (void)hipFree(p);
+    }
+};
+
+void free_tiff_pipe(void* p) { delete static_cast<TiffPipe*>(p); }
+
+TiffPipe* get_tiff_pipe(omr::Ctx* c) {
+    if (!c->tiff_state) {
+        c->tiff_state = new TiffPipe;
+        c->tiff_state_free = free_tiff_pipe;
+    }
+    return static_cast<TiffPipe*>(c->tiff_state);
+}
+
+omr_status grow_device(omr::Ctx* c, void*& p, size_t& cap, size_t bytes) {
+    if (bytes <= cap) return OMR_OK;
+    if (p) OMR_HIP(c, hipFree(p));
+    p = nullptr;
+    cap = 0;
+    OMR_HIP(c, hipMalloc(&p, bytes));
+    cap = bytes;
+    return OMR_OK;
+}
+
+// job(i) for i in [0, n) on up to 16 threads (the calling one included).
+template <typename F>
+void parallel_for(int n, bool threaded, const F& job) {
+    const unsigned hw = std::thread::hardware_concurrency();
+    const int extra = threaded ? std::min<int>(n, (int)std::min(hw ? hw : 4u, 16u)) - 1 : 0;
+    std::atomic<int> next{0};
+    auto work = [&] {
+        for (int i; (i = next.fetch_add(1)) < n;) job(i);
+    };
+    std::vector<std::thread> th;
+    for (int k = 0; k < extra; ++k) th.emplace_back(work);
+    work();
+    for (auto& t : th) t.join();
+}
+
+struct UniqueSeg {
+    uint64_t off, cnt;
+    uint32_t expected;
+    uint64_t in_off = 0, scratch_off = 0;
+};
+
+constexpr size_t kGroupInBytes = (size_t)128 << 20;        // compressed bytes per group
+constexpr size_t kGroupScratchBytes = (size_t)512 << 20;   // decoded bytes per group
+constexpr size_t kRenderGroupBytes = (size_t)256 << 20;    // region bytes per render group
+
+// One group of regions: reqs[r0, r1).
+omr_status read_group(omr::Ctx* ctx, const omr_tiff_image* im, int32_t level, const omr_raw_tile_request* reqs, int32_t r0,
+                      int32_t r1, int32_t width, int32_t height, uint8_t* d_dst, int64_t stride) {
+    using omr::align_up;
+    using omr::TiffPlace;
+    const Level& L = im->levels[(size_t)level];
+    const bool lzw = im->compression == 5;
+    std::unordered_map<uint64_t, int32_t> index;      // plane * segments + k -> unique segment
+    std::vector<UniqueSeg> segs;
+    std::vector<TiffPlace> places;
+    std::vector<int32_t> place_seg;
+    const uint64_t per_plane = (uint64_t)L.across * L.down;
+    size_t in_bytes = 0, scratch_bytes = 0;
+    int32_t max_rows = 0;
+    for (int32_t i = r0; i < r1; ++i) {
+        const omr_raw_tile_request& r = reqs[i];
+        const Segments& S = im->segs[(size_t)plane_index(im, r.z, r.c, r.t)][(size_t)level];
+        for (int32_t sy = r.y / L.seg_h; sy <= (r.y + height - 1) / L.seg_h; ++sy)
+            for (int32_t sx = r.x / L.seg_w; sx <= (r.x + width - 1) / L.seg_w; ++sx) {
+                const uint64_t k = (uint64_t)sy * L.across + sx;
+                const uint64_t key = (uint64_t)plane_index(im, r.z, r.c, r.t) * per_plane + k;
+                auto it = index.find(key);
+                if (it == index.end()) {
+                    UniqueSeg u;
+                    u.off = S.off[(size_t)k];
+                    u.cnt = S.cnt[(size_t)k];
+                    u.expected = (uint32_t)((size_t)rows_in_segment(L, sy) * L.seg_w * im->bpp);
+                    if (u.cnt) {
+                        if (!lzw) u.cnt = u.expected;                 // the stored bytes we need
+                        u.in_off = in_bytes;
+                        in_bytes += align_up((size_t)u.cnt, 16);
+                        if (lzw) {
+                            u.scratch_off = scratch_bytes;
+                            scratch_bytes += align_up((size_t)u.expected, 16);
+                        }
+                    }
+                    it = index.emplace(key, (int32_t)segs.size()).first;
+                    segs.push_back(u);
+                }
+                const int32_t ox = sx * L.seg_w, oy = sy * L.seg_h;
+                const int32_t X0 = std::max(r.x, ox), X1 = std::min(r.x + width, ox + L.seg_w);
+                const int32_t Y0 = std::max(r.y, oy), Y1 = std::min(r.y + height, oy + L.seg_h);
+                TiffPlace p;
+                p.src = nullptr;
+                p.dst = d_dst + (int64_t)i * stride + ((int64_t)(Y0 - r.y) * width + (X0 - r.x)) * im->bpp;
+                p.seg_w = L.seg_w;
+                p.dst_pitch = width;
+                p.x0 = X0 - ox; p.x1 = X1 - ox; p.y0 = Y0 - oy; p.y1 = Y1 - oy;
+                max_rows = std::max(max_rows, Y1 - Y0);
+                places.push_back(p);
+                place_seg.push_back(it->second);
+            }
+    }
+    if (places.empty()) return OMR_OK;
+    std::vector<int32_t> coded;                        // the segments K13a decodes
+    if (lzw)
+        for (size_t k = 0; k < segs.size(); ++k)
+            if (segs[k].cnt) coded.push_back((int32_t)k);
+    const size_t m = coded.size();
+    // staging: [bytes][offsets u64 m][dst offsets u64 m][lengths u32 m][expected u32 m][places] | [status i32 m]
+    const size_t o_off = align_up(in_bytes, 256), o_dst = o_off + 8 * m, o_len = o_dst + 8 * m, o_exp = o_len + 4 * m;
+    const size_t o_place = align_up(o_exp + 4 * m, 16), up_bytes = o_place + places.size() * sizeof(TiffPlace);
+    const size_t o_status = align_up(up_bytes, 256), total = o_status + 4 * m;
+    TiffPipe* T = get_tiff_pipe(ctx);
+    if (total > T->in_cap) {
+        if (T->pin) OMR_HIP(ctx, hipHostFree(T->pin));
+        T->pin = nullptr;
+        const size_t keep = T->in_cap;
+        T->in_cap = 0;
+        omr_status st = grow_device(ctx, T->d_in, T->in_cap, std::max(total, keep + keep / 2));
+        if (st) return st;
+        const hipError_t e = hipHostMalloc(&T->pin, T->in_cap, hipHostMallocDefault);
+        if (e != hipSuccess) {
+            T->in_cap = 0;                               // both are made again on the next call
+            return omr::hip_fail(ctx, e, "hipHostMalloc(tiff staging)");
+        }
+    }
+    omr_status st = grow_device(ctx, T->d_scratch, T->scratch_cap, scratch_bytes);
+    if (st) return st;
+    uint8_t* pin = static_cast<uint8_t*>(T->pin);
+    uint8_t* din = static_cast<uint8_t*>(T->d_in);
+    uint8_t* dscr = static_cast<uint8_t*>(T->d_scratch);
+    std::atomic<bool> io_error{false};
+    parallel_for((int)segs.size(), in_bytes > ((size_t)4 << 20), [&](int k) {
+        const UniqueSeg& u = segs[(size_t)k];
+        if (u.cnt && !read_full(im->fd, pin + u.in_off, (size_t)u.cnt, u.off)) io_error = true;
+    });
+    if (io_error) return omr::fail(ctx, OMR_INTERNAL, "tiff: segment read failed");
+    uint64_t* h_off = reinterpret_cast<uint64_t*>(pin + o_off);
+    uint64_t* h_dst = reinterpret_cast<uint64_t*>(pin + o_dst);
+    uint32_t* h_len = reinterpret_cast<uint32_t*>(pin + o_len);
+    uint32_t* h_exp = reinterpret_cast<uint32_t*>(pin + o_exp);
+    for (size_t j = 0; j < m; ++j) {
+        const UniqueSeg& u = segs[(size_t)coded[j]];
+        h_off[j] = u.in_off;
+        h_dst[j] = u.scratch_off;
+        h_len[j] = (uint32_t)u.cnt;
+        h_exp[j] = u.expected;
+    }
+    TiffPlace* h_place = reinterpret_cast<TiffPlace*>(pin + o_place);
+    for (size_t k = 0; k < places.size(); ++k) {
+        const UniqueSeg& u = segs[(size_t)place_seg[k]];
+        places[k].src = !u.cnt ? nullptr : lzw ? dscr + u.scratch_off : din + u.in_off;
+        h_place[k] = places[k];
+    }
+    OMR_HIP(ctx, hipMemcpyAsync(din, pin, up_bytes, hipMemcpyHostToDevice, ctx->stream));
+    st = omr::launch_lzw_decode(ctx, din, reinterpret_cast<const uint64_t*>(din + o_off),
+                                reinterpret_cast<const uint32_t*>(din + o_len),
+                                reinterpret_cast<const uint32_t*>(din + o_exp), (int32_t)m, dscr,
+                                reinterpret_cast<const uint64_t*>(din + o_dst), reinterpret_cast<int32_t*>(din + o_status));
+    if (st) return st;
+    st = omr::launch_tiff_place(ctx, reinterpret_cast<const TiffPlace*>(din + o_place), (int32_t)places.size(), max_rows,
+                                im->bpp, im->predictor, im->big == host_little_endian());
+    if (st) return st;
+    if (m) OMR_HIP(ctx, hipMemcpyAsync(pin + o_status, din + o_status, 4 * m, hipMemcpyDeviceToHost, ctx->stream));
+    OMR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const int32_t* h_status = reinterpret_cast<const int32_t*>(pin + o_status);
+    for (size_t j = 0; j < m; ++j)
+        if (h_status[j] != OMR_OK) return omr::fail(ctx, OMR_INTERNAL, "tiff: corrupt LZW segment");
+    return OMR_OK;
+}
+
+}  // namespace
+
+using namespace omr;
+
+extern "C" {
+
+omr_status omr_tiff_image_open(const char* path, int32_t size_z, int32_t size_c, int32_t size_t_,
+                               const char* dimension_order, omr_tiff_image** out) {
+    if (!out) return OMR_INVALID_ARGUMENT;
+    *out = nullptr;
+    if (!path || !dimension_order || size_z <= 0 || size_c <= 0 || size_t_ <= 0) return OMR_INVALID_ARGUMENT;
+    int64_t n_planes = size_z;
+    if (__builtin_mul_overflow(n_planes, (int64_t)size_c, &n_planes) ||
+        __builtin_mul_overflow(n_planes, (int64_t)size_t_, &n_planes) || n_planes > (int64_t)kMaxIfds)
+        return OMR_INVALID_ARGUMENT;
+    // "XY" and a permutation of Z, C, T: the first of the three varies fastest along the IFD chain
+    if (std::strlen(dimension_order) != 5 || dimension_order[0] != 'X' || dimension_order[1] != 'Y')
+        return OMR_INVALID_ARGUMENT;
+    std::unique_ptr<omr_tiff_image> im(new omr_tiff_image);
+    im->sz = size_z; im->sc = size_c; im->st = size_t_;
+    int64_t stride = 1;
+    for (int k = 2; k < 5; ++k) {
+        switch (dimension_order[k]) {
+        case 'Z': if (im->stride_z) return OMR_INVALID_ARGUMENT; im->stride_z = stride; stride *= size_z; break;
+        case 'C': if (im->stride_c) return OMR_INVALID_ARGUMENT; im->stride_c = stride; stride *= size_c; break;
+        case 'T': if (im->stride_t) return OMR_INVALID_ARGUMENT; im->stride_t = stride; stride *= size_t_; break;
+        default: return OMR_INVALID_ARGUMENT;
+        }
+    }
+    im->fd = ::open(path, O_RDONLY | O_CLOEXEC);
+    if (im->fd < 0) return errno == ENOENT ? OMR_NOT_FOUND : OMR_INVALID_ARGUMENT;
+    struct stat sb;
+    if (::fstat(im->fd, &sb) != 0 || !S_ISREG(sb.st_mode)) return OMR_INVALID_ARGUMENT;
+    Parser P{im->fd, (uint64_t)sb.st_size};
+    im->file_len = P.len;
+    uint8_t hdr[16];
+    if (!P.rd(0, hdr, 8)) return OMR_INTERNAL;
+    if (hdr[0] == 'I' && hdr[1] == 'I') P.big = false;
+    else if (hdr[0] == 'M' && hdr[1] == 'M') P.big = true;
+    else return OMR_INVALID_ARGUMENT;
+    const uint64_t magic = P.u(hdr + 2, 2);
+    uint64_t ifd_off;
+    if (magic == 42) {
+        ifd_off = P.u(hdr + 4, 4);
+    } else if (magic == 43) {
+        P.bigtiff = true;
+        if (!P.rd(0, hdr, 16)) return OMR_INTERNAL;
+        if (P.u(hdr + 4, 2) != 8 || P.u(hdr + 6, 2) != 0) return OMR_INVALID_ARGUMENT;
+        ifd_off = P.u(hdr + 8, 8);
+    } else {
+        return OMR_INVALID_ARGUMENT;
+    }
+    im->big = P.big;
+    im->bigtiff = P.bigtiff;
+
+    std::unordered_set<uint64_t> seen;
+    int64_t n_ifds = 0;
+    bool first = true;
+    while (ifd_off != 0) {
+        if (!seen.insert(ifd_off).second || seen.size() > kMaxIfds) return OMR_INTERNAL;   // the chain loops
+        uint64_t next = 0;
+        if (n_ifds >= n_planes) {                        // behind the planes: only walk the chain
+            const omr_status st = P.read_ifd(ifd_off, nullptr, next);
+            if (st) return st;
+            ++n_ifds;
+            ifd_off = next;
+            continue;
+        }
+        Ifd main;
+        omr_status st = P.read_ifd(ifd_off, &main, next);
+        if (st) return st;
+        std::vector<Level> lv(1 + main.sub.size());
+        std::vector<Segments> sg(1 + main.sub.size());
+        for (size_t k = 0; k < lv.size(); ++k) {
+            Ifd sub;
+            if (k > 0) {
+                uint64_t ignored = 0;
+                if (!seen.insert(main.sub[k - 1]).second || seen.size() > kMaxIfds) return OMR_INTERNAL;
+                st = P.read_ifd(main.sub[k - 1], &sub, ignored);
+                if (st) return st;
+            }
+            int32_t pt = 0, comp = 0, pred = 0;
+            st = take_ifd(P, k ? sub : main, lv[k], sg[k], pt, comp, pred);
+            if (st) return st;
+            if (first) {
+                im->pt = pt;
+                im->bpp = bytes_per_pixel(pt);
+                im->compression = comp;
+                im->predictor = pred;
+                first = false;
+            } else if (pt != im->pt || comp != im->compression || pred != im->predictor) {
+                return OMR_INVALID_ARGUMENT;             // planes or levels that disagree
+            }
+        }
+        if (n_ifds == 0) im->levels = lv;
+        else if (!(lv == im->levels)) return OMR_INVALID_ARGUMENT;
+        im->segs.push_back(std::move(sg));
+        ++n_ifds;
+        ifd_off = next;
+    }
+    if (n_ifds < n_planes) return OMR_INVALID_ARGUMENT;
+    *out = im.release();
+    return OMR_OK;
+}
+
+void omr_tiff_image_close(omr_tiff_image* img) { delete img; }
+
+omr_status omr_tiff_image_info(const omr_tiff_image* img, omr_tiff_info* info) {
+    if (!img || !info) return OMR_INVALID_ARGUMENT;
+    const Level& L = img->levels[0];
+    info->size_x = L.w; info->size_y = L.h;
+    info->size_z = img->sz; info->size_c = img->sc; info->size_t_ = img->st;
+    info->pixel_type = img->pt;
+    info->big_endian = img->big;
+    info->n_levels = (int32_t)img->levels.size();
+    info->compression = img->compression;
+    info->predictor = img->predictor;
+    info->tiled = L.tiled;
+    info->segment_width = L.seg_w;
+    info->segment_height = L.seg_h;
+    info->big_tiff = img->bigtiff;
+    return OMR_OK;
+}
+
+int32_t omr_tiff_image_level_sizes(const omr_tiff_image* img, int32_t* sizes_out, int32_t cap_pairs) {
+    if (!img || (!sizes_out && cap_pairs > 0)) return -(int32_t)OMR_INVALID_ARGUMENT;
+    const int32_t n = (int32_t)img->levels.size();
+    for (int32_t k = 0; k < n && k < cap_pairs; ++k) {
+        sizes_out[2 * k] = img->levels[(size_t)k].w;
+        sizes_out[2 * k + 1] = img->levels[(size_t)k].h;
+    }
+    return n;
+}
+
+omr_status omr_lzw_decode_host(const uint8_t* src, size_t length, uint8_t* dst, size_t expected) {
+    if ((!src && length) || (!dst && expected)) return OMR_INVALID_ARGUMENT;
+    return lzw_decode(src, length, dst, expected) ? OMR_OK : OMR_INTERNAL;
+}
+
+omr_status omr_tiff_image_get_tile(const omr_tiff_image* img, int32_t level, int32_t z, int32_t c, int32_t t,
+                                   int32_t x, int32_t y, int32_t w, int32_t h, void* dst, size_t cap) {
+    if (!img || !dst || level < 0 || level >= (int32_t)img->levels.size()) return OMR_INVALID_ARGUMENT;
+    const Level& L = img->levels[(size_t)level];
+    if (!region_in_bounds(img, L, z, c, t, x, y, w, h)) return OMR_INVALID_ARGUMENT;   // DimensionsOutOfBounds
+    if (cap < (size_t)w * h * img->bpp) return OMR_BUFFER_TOO_SMALL;
+    if (w == 0 || h == 0) return OMR_OK;
+    const Segments& S = img->segs[(size_t)plane_index(img, z, c, t)][(size_t)level];
+    std::vector<uint8_t> comp, seg;
+    uint8_t* out = static_cast<uint8_t*>(dst);
+    const size_t bpp = (size_t)img->bpp;
+    for (int32_t sy = y / L.seg_h; sy <= (y + h - 1) / L.seg_h; ++sy)
+        for (int32_t sx = x / L.seg_w; sx <= (x + w - 1) / L.seg_w; ++sx) {
+            const omr_status st = load_segment(img, L, S, sx, sy, comp, seg);
+            if (st) return st;
+            const int32_t ox = sx * L.seg_w, oy = sy * L.seg_h;
+            const int32_t X0 = std::max(x, ox), X1 = std::min(x + w, ox + L.seg_w);
+            const int32_t Y0 = std::max(y, oy), Y1 = std::min(y + h, oy + L.seg_h);
+            for (int32_t yy = Y0; yy < Y1; ++yy)
+                std::memcpy(out + ((size_t)(yy - y) * w + (X0 - x)) * bpp,
+                            seg.data() + ((size_t)(yy - oy) * L.seg_w + (X0 - ox)) * bpp, (size_t)(X1 - X0) * bpp);
+        }
+    return OMR_OK;
+}
+
+omr_status omr_tiff_image_read_regions_device(omr_ctx* ctx, const omr_tiff_image* img, int32_t level,
+                                              const omr_raw_tile_request* reqs, int32_t n, int32_t width,
+                                              int32_t height, void* d_dst, int64_t region_stride_bytes) {
+    if (!ctx) return OMR_INVALID_ARGUMENT;
+    if (!img || n < 0 || (n && (!reqs || !d_dst))) return fail(ctx, OMR_INVALID_ARGUMENT, "tiff: null argument");
+    if (level < 0 || level >= (int32_t)img->levels.size()) return fail(ctx, OMR_INVALID_ARGUMENT, "tiff: no such level");
+    if (width < 0 || height < 0) return fail(ctx, OMR_INVALID_ARGUMENT, "tiff: bad region size");
+    const Level& L = img->levels[(size_t)level];
+    const int64_t region_bytes = (int64_t)width * height * img->bpp;
+    if (region_stride_bytes < region_bytes || region_stride_bytes % img->bpp ||
+        reinterpret_cast<uintptr_t>(d_dst) % (uintptr_t)img->bpp)
+        return fail(ctx, OMR_INVALID_ARGUMENT, "tiff: region stride or destination not a multiple of the sample size");
+    for (int32_t i = 0; i < n; ++i)
+        if (!region_in_bounds(img, L, reqs[i].z, reqs[i].c, reqs[i].t, reqs[i].x, reqs[i].y, width, height))
+            return fail(ctx, OMR_INVALID_ARGUMENT, "tiff: region " + std::to_string(i) + " outside the image");
+    if (n == 0 || width == 0 || height == 0) return OMR_OK;
+    OMR_HIP(ctx, hipSetDevice(ctx->device));
+    // groups of requests within the staging budgets (a request's segments counted without sharing)
+    const size_t seg_dec = align_up((size_t)L.seg_w * L.seg_h * img->bpp, 16);
+    const size_t per_req = (size_t)((width - 1) / L.seg_w + 2) * (size_t)((height - 1) / L.seg_h + 2) * seg_dec;
+    const int32_t G = (int32_t)std::max<size_t>(1, std::min<size_t>((size_t)n, std::min(kGroupInBytes, kGroupScratchBytes) / per_req));
+    for (int32_t r0 = 0; r0 < n; r0 += G) {
+        const omr_status st = read_group(ctx, img, level, reqs, r0, std::min(n, r0 + G), width, height,
+                                         static_cast<uint8_t*>(d_dst), region_stride_bytes);
+        if (st) return st;
+    }
+    return OMR_OK;
+}
+
+omr_status omr_render_tiff_tiles(omr_ctx* ctx, const omr_tiff_image* img, int32_t level, const omr_quantum_def* qdef,
+                                 const omr_channel_binding* channels, int32_t size_c, const omr_tile_request* reqs,
+                                 int32_t n, int32_t width, int32_t height, int32_t flip_h, int32_t flip_v,
+                                 uint32_t* argb_out, int32_t out_on_device) {
+    if (!ctx) return OMR_INVALID_ARGUMENT;
+    if (!img || !qdef || !channels || !reqs || !argb_out || n < 0) return fail(ctx, OMR_INVALID_ARGUMENT, "null argument");
+    if (size_c != img->sc) return fail(ctx, OMR_INVALID_ARGUMENT, "channel bindings do not match the image's sizeC");
+    if (width <= 0 || height <= 0) return fail(ctx, OMR_INVALID_ARGUMENT, "bad tile size");
+    if (level < 0 || level >= (int32_t)img->levels.size()) return fail(ctx, OMR_INVALID_ARGUMENT, "tiff: no such level");
+    if (n == 0) return OMR_OK;
+    // the rendered channels, compacted: [tile][active channel][h][w] with their bindings in order
+    std::vector<int32_t> act;
+    std::vector<omr_channel_binding> bind;
+    for (int c = 0; c < size_c; ++c)
+        if (channels[c].active) {
+            if (qdef->model == OMR_MODEL_GREYSCALE && !act.empty()) break;   // first active only
+            act.push_back(c);
+            bind.push_back(channels[c]);
+        }
+    const int na = (int)act.size();
+    if (act.empty()) bind.assign(channels, channels + size_c);   // nothing to read: the render's own answer
+    OMR_HIP(ctx, hipSetDevice(ctx->device));
+    TiffPipe* T = get_tiff_pipe(ctx);
+    const size_t plane_al = align_up((size_t)width * height * img->bpp, 16);   // K2's vector path: 16-byte strides
+    const size_t tile_out = (size_t)width * height * 4;
+    const int32_t G = (int32_t)std::max<size_t>(1, std::min<size_t>((size_t)n, kRenderGroupBytes / (plane_al * std::max(na, 1))));
+    omr_status st = grow_device(ctx, T->d_regions, T->regions_cap, std::max<size_t>(16, plane_al * na * (size_t)G));
+    if (st) return st;
+    if (!out_on_device) {
+        st = grow_device(ctx, T->d_out, T->out_cap, tile_out * (size_t)G);
+        if (st) return st;
+    }
+    std::vector<omr_raw_tile_request> rr;
+    for (int32_t t0 = 0; t0 < n; t0 += G) {
+        const int32_t cnt = std::min(G, n - t0);
+        rr.clear();
+        for (int32_t i = 0; i < cnt; ++i)
+            for (int a = 0; a < na; ++a) rr.push_back({reqs[t0 + i].z, act[(size_t)a], reqs[t0 + i].t, reqs[t0 + i].x, reqs[t0 + i].y});
+        st = omr_tiff_image_read_regions_device(ctx, img, level, rr.data(), cnt * na, width, height, T->d_regions,
+                                                (int64_t)plane_al);
+        if (st) return st;
+        uint32_t* dout = out_on_device ? argb_out + (size_t)t0 * width * height : static_cast<uint32_t*>(T->d_out);
+        st = omr_render_batch_strided_device(ctx, qdef, bind.data(), (int32_t)bind.size(), T->d_regions, (int64_t)(plane_al * na),
+                                             (int64_t)plane_al, cnt, 0, img->pt, img->big, width, height, flip_h, flip_v,
+                                             dout, nullptr);
+        if (st) return st;
+        if (!out_on_device) {
+            st = omr_ctx_synchronize(ctx);
+            if (st) return st;
+            OMR_HIP(ctx, hipMemcpy(reinterpret_cast<uint8_t*>(argb_out) + (size_t)t0 * tile_out, dout,
+                                   tile_out * (size_t)cnt, hipMemcpyDeviceToHost));
+        }
+    }
+    return out_on_device ? omr_ctx_synchronize(ctx) : OMR_OK;
+}
+
+}  // extern "C"

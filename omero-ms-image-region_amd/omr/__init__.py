@@ -6,6 +6,7 @@ Layers:
   renderer  Renderer facade mirroring the omeis Renderer calls the reference makes
             (ImageRegionRequestHandler.java:436-440, :689-741, :559)
   pixbuf    PixelBuffer: ROMIO repository pixel files (getPixelBuffer, :302-309)
+  tiffimage TiffImage: tiled TIFF / OME-TIFF pixel files, LZW decoded on the GPU; write_tiled_tiff
   batcher   Batcher: concurrent requests coalesced into GPU batches; Pool: one batcher per GPU
   request   ImageRegionCtx / ShapeMaskCtx parsing and the handler glue
             (ImageRegionCtx.java, ImageRegionRequestHandler.java, ShapeMaskRequestHandler.java)
@@ -14,6 +15,7 @@ from . import _lib
 from ._lib import OmrError
 from .context import Context, pyramid_level_count, pyramid_level_sizes, thumbnail_size
 from .pixbuf import PixelBuffer, write_pyramid, write_romio
+from .tiffimage import TiffImage, lzw_decode_host, lzw_encode, write_tiled_tiff
 from .batcher import Batcher, Pool
 from .renderer import (ChannelSettings, Renderer, ReverseIntensityContext, create_rendering_def,
                        flip, split_html_color)
@@ -69,4 +71,5 @@ def histogram_json(ctx, pixbuf, z, c, t, bins=256, use_pixels_type_range=True, l
 __all__ = ["_lib", "OmrError", "Context", "Renderer", "histogram_bin_of", "histogram_json", "encode_tiff_raw", "thumbnail_size", "ChannelSettings", "ReverseIntensityContext",
            "create_rendering_def", "flip", "split_html_color", "ImageRegionCtx",
            "ImageRegionRequestHandler", "InMemoryPixelBuffer", "LutProvider", "RequestError",
-           "ShapeMaskCtx", "ShapeMaskRequestHandler", "PixelBuffer", "write_romio", "write_pyramid", "Batcher", "Pool"]
+           "ShapeMaskCtx", "ShapeMaskRequestHandler", "PixelBuffer", "write_romio", "write_pyramid", "Batcher", "Pool",
+           "TiffImage", "write_tiled_tiff", "lzw_encode", "lzw_decode_host"]

@@ -102,6 +102,12 @@ class RawTileRequest(ctypes.Structure):
                 ("y", ctypes.c_int32)]
 
 
+class TiffInfo(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in (
+        "size_x", "size_y", "size_z", "size_c", "size_t", "pixel_type", "big_endian", "n_levels", "compression",
+        "predictor", "tiled", "segment_width", "segment_height", "big_tiff")]
+
+
 class Region(ctypes.Structure):
     _fields_ = [("x", ctypes.c_int32), ("y", ctypes.c_int32),
                 ("width", ctypes.c_int32), ("height", ctypes.c_int32)]
@@ -270,6 +276,15 @@ _SIGS = {
     "omr_encode_tiff_raw": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _sz, ctypes.POINTER(_sz)]),
     "omr_pixel_buffer_tile_tiff": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _sz,
                                           ctypes.POINTER(_sz)]),
+    "omr_tiff_image_open": (_i32, [ctypes.c_char_p, _i32, _i32, _i32, ctypes.c_char_p, ctypes.POINTER(_vp)]),
+    "omr_tiff_image_close": (None, [_vp]),
+    "omr_tiff_image_info": (_i32, [_vp, ctypes.POINTER(TiffInfo)]),
+    "omr_tiff_image_level_sizes": (_i32, [_vp, ctypes.POINTER(_i32), _i32]),
+    "omr_tiff_image_get_tile": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _sz]),
+    "omr_lzw_decode_host": (_i32, [_vp, _sz, _vp, _sz]),
+    "omr_lzw_decode_batch_device": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "omr_tiff_image_read_regions_device": (_i32, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _i64]),
+    "omr_render_tiff_tiles": (_i32, [_vp, _vp, _i32, _QD, _CB, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32]),
     "omr_render_shape_mask_png_batch": (_i32, [_vp, ctypes.POINTER(MaskJob), _i32, _vp, _sz, _vp, _vp, _vp]),
     "omr_split_html_color": (_i32, [ctypes.c_char_p, ctypes.POINTER(_i32)]),
     "omr_shape_mask_fill_color": (_i32, [_i32, _i32, ctypes.c_char_p, _vp]),

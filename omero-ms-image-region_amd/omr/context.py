@@ -178,7 +178,7 @@ class Context:
     def kernel_timings(self, cap=1 << 16):
         """[(ms, kind)] of the timed hot-kernel launches since the last call (kind 2 render,
         3 projection, 4 jpeg, 10 fused scaled render, 11 ARGB scaler, 12 pyramid levels, 20..26 the
-        batched PNG stages, 27 the grey wave filter); synchronises the stream."""
+        batched PNG stages, 27 the grey wave filter, 30 LZW decode, 31 TIFF place); synchronises the stream."""
         ms = np.zeros(cap, np.float32)
         kind = np.zeros(cap, np.int32)
         n = lib.omr_ctx_kernel_timings(self.h, ms.ctypes.data, kind.ctypes.data, cap)

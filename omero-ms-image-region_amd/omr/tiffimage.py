@@ -1,0 +1,331 @@
+"""TiffImage: tiled TIFF / OME-TIFF pixel data (K13), and write_tiled_tiff, the small writer that
+makes the test and probe files.
+
+The second backend of pixelsService.getPixelBuffer beside the ROMIO file (pixbuf.PixelBuffer):
+pyramidal OME-TIFF as raw2ometiff writes it, one IFD per plane and the lower resolutions in
+SubIFDs.  Reads go through libomr.so: get_tile on the host (plain serial LZW decoder), read_regions
+and render_tiles with the LZW segments decoded on the GPU (omr_tiffread.hip).
+"""
+import ctypes
+import struct
+
+import numpy as np
+
+from . import _lib
+from ._lib import lib
+
+_NP_NAMES = {_lib.PIXELS_INT8: "i1", _lib.PIXELS_UINT8: "u1", _lib.PIXELS_INT16: "i2", _lib.PIXELS_UINT16: "u2",
+             _lib.PIXELS_INT32: "i4", _lib.PIXELS_UINT32: "u4", _lib.PIXELS_FLOAT: "f4", _lib.PIXELS_DOUBLE: "f8"}
+DIMENSION_ORDERS = ("XYZCT", "XYZTC", "XYCZT", "XYCTZ", "XYTZC", "XYTCZ")
+
+
+def lzw_encode(data, early_clear=0, eoi=True):
+    """TIFF LZW as libtiff writes it: MSB-first codes from 9 bits, Clear (256) first, EOI (257)
+    last; the writer widens when its own next entry reaches 512, 1024 and 2048 (the reader, one
+    entry behind, when its reaches 511, 1023, 2047: "early change") and clears at 4094.
+    early_clear = k > 0: a Clear after every k entries as well.  eoi = False: no EOI code."""
+    data = bytes(data)
+    out = bytearray()
+    acc = nbits = 0
+
+    def put(code, width):
+        nonlocal acc, nbits
+        acc = (acc << width) | code
+        nbits += width
+        while nbits >= 8:
+            nbits -= 8
+            out.append((acc >> nbits) & 0xFF)
+        acc &= (1 << nbits) - 1
+
+    width, nxt, table = 9, 258, {}
+    put(256, width)
+    if data:
+        w = data[0]
+        for c in data[1:]:
+            key = (w << 8) | c
+            hit = table.get(key)
+            if hit is not None:
+                w = hit
+                continue
+            put(w, width)
+            table[key] = nxt
+            nxt += 1
+            if nxt in (512, 1024, 2048):
+                width += 1
+            if nxt == 4094 or (early_clear and nxt - 258 >= early_clear):
+                put(256, width)
+                width, nxt, table = 9, 258, {}
+            w = c
+        put(w, width)
+        nxt += 1
+        if nxt == 4094:
+            put(256, width)
+            width = 9
+        elif nxt in (512, 1024, 2048):
+            width += 1
+    if eoi:
+        put(257, width)
+    if nbits:
+        out.append((acc << (8 - nbits)) & 0xFF)
+    return bytes(out)
+
+
+class _LzwJob:
+    """lzw_encode with its options, picklable for a process pool's map."""
+
+    def __init__(self, early_clear, eoi):
+        self.early_clear, self.eoi = early_clear, eoi
+
+    def __call__(self, raw):
+        return lzw_encode(raw, self.early_clear, self.eoi)
+
+
+def _predict(seg):
+    """Horizontal differencing (Predictor 2) of a [rows][cols] array, in the sample's own width."""
+    u = np.ascontiguousarray(seg.astype(seg.dtype.newbyteorder("="))).view("u%d" % seg.dtype.itemsize)
+    d = u.copy()
+    d[:, 1:] = u[:, 1:] - u[:, :-1]
+    return d
+
+
+def write_tiled_tiff(path, planes, levels=(), tile=(256, 256), rows_per_strip=None, byteorder="<", bigtiff=False,
+                     compression=1, predictor=1, early_clear=0, eoi=True, dimension_order="XYZCT",
+                     skip_zero_segments=False, tag_overrides=None, mapper=map):
+    """Write a [t][c][z][y][x] array as a TIFF with one IFD per plane (in `dimension_order`), and
+    `levels` (arrays of the same [t][c][z] with their own [y][x]) as SubIFDs of each plane.
+    tile = (w, h), or rows_per_strip = n for strips; byteorder "<" (II) or ">" (MM); compression 1
+    or 5 (LZW, lzw_encode with early_clear / eoi); predictor 1 or 2 (integer samples up to 32 bits);
+    skip_zero_segments: an all-zero segment is written with byte count 0; tag_overrides = {tag:
+    value} replaces the value written for a SHORT tag (to make files a reader must reject); mapper:
+    a map() that encodes the LZW segments of one image, e.g. a multiprocessing pool's for big files.
+    Returns {"ifds": [offset per plane], "subifds": [[offsets] per plane]}."""
+    planes = np.asarray(planes)
+    assert planes.ndim == 5, "planes must be [t][c][z][y][x]"
+    levels = [np.asarray(lv) for lv in levels]
+    st, sc, sz = planes.shape[:3]
+    for lv in levels:
+        assert lv.ndim == 5 and lv.shape[:3] == planes.shape[:3] and lv.dtype == planes.dtype
+    assert dimension_order in DIMENSION_ORDERS
+    dt = planes.dtype
+    kind = {"u": 1, "i": 2, "f": 3}[dt.kind]
+    bo = byteorder
+    fdt = dt.newbyteorder(bo) if dt.itemsize > 1 else dt
+    tag_overrides = dict(tag_overrides or {})
+    buf = bytearray(b"II" if bo == "<" else b"MM")
+    if bigtiff:
+        buf += struct.pack(bo + "HHHQ", 43, 8, 0, 0)
+    else:
+        buf += struct.pack(bo + "HI", 42, 0)
+    osz, ofmt = (8, "Q") if bigtiff else (4, "I")
+
+    def segments(img):
+        """(offsets, counts, geometry tags) of one image; the data goes into buf."""
+        h, w = img.shape
+        if rows_per_strip is None:
+            tw, th = tile
+            boxes = [(x, y, tw, th) for y in range(0, h, th) for x in range(0, w, tw)]
+        else:
+            boxes = [(0, y, w, min(rows_per_strip, h - y)) for y in range(0, h, rows_per_strip)]
+        raws = []
+        for (x, y, bw, bh) in boxes:
+            seg = np.zeros((bh, bw), dtype=fdt)
+            part = img[y:y + bh, x:x + bw]
+            seg[:part.shape[0], :part.shape[1]] = part
+            if skip_zero_segments and not part.any():
+                raws.append(None)
+                continue
+            if predictor == 2:
+                seg = _predict(seg).astype(np.dtype("u%d" % dt.itemsize).newbyteorder(bo) if dt.itemsize > 1 else "u1")
+            raws.append(seg.tobytes())
+        if compression == 5:
+            todo = [r for r in raws if r is not None]
+            done = iter(list(mapper(_LzwJob(early_clear, eoi), todo)))
+            raws = [None if r is None else next(done) for r in raws]
+        offs, cnts = [], []
+        for raw in raws:
+            if raw is None:
+                offs.append(0)
+                cnts.append(0)
+                continue
+            if len(buf) % 2:
+                buf.append(0)
+            offs.append(len(buf))
+            cnts.append(len(raw))
+            buf.extend(raw)
+        if rows_per_strip is None:
+            geom = [(322, "H", [tile[0]]), (323, "H", [tile[1]]), (324, ofmt, offs), (325, ofmt, cnts)]
+        else:
+            geom = [(273, ofmt, offs), (278, "I", [rows_per_strip]), (279, ofmt, cnts)]
+        return geom
+
+    def ifd_entries(img, n_sub):
+        h, w = img.shape
+        ent = [(256, "I", [w]), (257, "I", [h]), (258, "H", [8 * dt.itemsize]), (259, "H", [compression]),
+               (262, "H", [1]), (277, "H", [1]), (284, "H", [1]), (339, "H", [kind])]
+        if predictor != 1 or 317 in tag_overrides:
+            ent.append((317, "H", [predictor]))
+        if 266 in tag_overrides:
+            ent.append((266, "H", [1]))
+        ent += segments(img)
+        if n_sub:
+            ent.append((330, ofmt, [0] * n_sub))     # patched once the SubIFDs have their places
+        ent = [(t, f, [tag_overrides[t]] if t in tag_overrides else v) for (t, f, v) in ent]
+        return sorted(ent)
+
+    tsize = {"H": 2, "I": 4, "Q": 8}
+    tcode = {"H": 3, "I": 4, "Q": 16}
+
+    def emit_ifd(ent, next_at_end=True):
+        """Out-of-line values, then the IFD itself; returns (ifd offset, {tag: position of its values})."""
+        where = {}
+        fields = []
+        for (t, f, v) in ent:
+            raw = struct.pack(bo + f * len(v), *v)
+            if len(raw) <= osz:
+                fields.append(raw.ljust(osz, b"\0"))
+                where[t] = None
+            else:
+                if len(buf) % 2:
+                    buf.append(0)
+                where[t] = len(buf)
+                fields.append(struct.pack(bo + ofmt, len(buf)))
+                buf.extend(raw)
+        if len(buf) % 2:
+            buf.append(0)
+        at = len(buf)
+        buf.extend(struct.pack(bo + ("Q" if bigtiff else "H"), len(ent)))
+        for (t, f, v), field in zip(ent, fields):
+            if where[t] is None:
+                where[t] = len(buf) + (12 if bigtiff else 8)
+            buf.extend(struct.pack(bo + "HH" + ofmt, t, tcode[f], len(v)) + field)
+        buf.extend(struct.pack(bo + ofmt, 0))            # next IFD: patched by the caller
+        return at, where
+
+    # plane order along the chain: the first letter behind XY varies fastest
+    sizes = {"Z": sz, "C": sc, "T": st}
+    order = dimension_order[2:]
+    result = {"ifds": [], "subifds": []}
+    prev_next = 8 if bigtiff else 4                         # where the offset of the next main IFD goes
+    n_planes = sz * sc * st
+    for k in range(n_planes):
+        idx, r = {}, k
+        for letter in order:
+            idx[letter] = r % sizes[letter]
+            r //= sizes[letter]
+        t, c, z = idx["T"], idx["C"], idx["Z"]
+        subs = []
+        for lv in levels:
+            at, _ = emit_ifd(ifd_entries(lv[t, c, z], 0))
+            subs.append(at)
+        at, where = emit_ifd(ifd_entries(planes[t, c, z], len(subs)))
+        if subs:
+            struct.pack_into(bo + ofmt * len(subs), buf, where[330], *subs)
+        struct.pack_into(bo + ofmt, buf, prev_next, at)
+        n_ent = struct.unpack_from(bo + ("Q" if bigtiff else "H"), buf, at)[0]
+        prev_next = at + ((8 + 20 * n_ent) if bigtiff else (2 + 12 * n_ent))
+        result["ifds"].append(at)
+        result["subifds"].append(subs)
+    with open(path, "wb") as f:
+        f.write(buf)
+    return result
+
+
+class TiffImage:
+    """An open tiled TIFF / OME-TIFF (omr_tiff_image).  The caller gives Z, C, T and the dimension
+    order as for PixelBuffer; OME-XML is not parsed."""
+
+    def __init__(self, path, size_z=1, size_c=1, size_t=1, dimension_order="XYZCT"):
+        h = ctypes.c_void_p()
+        st = lib.omr_tiff_image_open(str(path).encode(), int(size_z), int(size_c), int(size_t),
+                                     str(dimension_order).encode(), ctypes.byref(h))
+        if st != _lib.OK:
+            raise _lib.OmrError(st, f"cannot open TIFF image {path}")
+        self.h = h
+        i = _lib.TiffInfo()
+        _lib.check(lib.omr_tiff_image_info(self.h, ctypes.byref(i)))
+        self.info = {n: int(getattr(i, n)) for n, _ in _lib.TiffInfo._fields_}
+        self.size_x, self.size_y = i.size_x, i.size_y
+        self.size_z, self.size_c, self.size_t = i.size_z, i.size_c, i.size_t
+        self.pixel_type = i.pixel_type
+        self.big_endian = bool(i.big_endian)
+        self.dtype = np.dtype((">" if self.big_endian else "<") + _NP_NAMES[self.pixel_type])
+        sizes = (ctypes.c_int32 * (2 * i.n_levels))()
+        n = lib.omr_tiff_image_level_sizes(self.h, sizes, i.n_levels)
+        self.level_sizes = [[sizes[2 * k], sizes[2 * k + 1]] for k in range(n)]
+
+    def close(self):
+        if self.h:
+            lib.omr_tiff_image_close(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def getResolutionLevels(self):
+        return len(self.level_sizes)
+
+    def getResolutionDescriptions(self):
+        return [list(s) for s in self.level_sizes]
+
+    def get_tile(self, level, z, c, t, x, y, w, h):
+        """The host route: [h][w] array in the file's byte order (omr_tiff_image_get_tile)."""
+        if w < 0 or h < 0:
+            raise _lib.OmrError(_lib.INVALID_ARGUMENT, f"tile {w}x{h} out of bounds")
+        out = np.empty((h, w), dtype=self.dtype)
+        _lib.check(lib.omr_tiff_image_get_tile(self.h, int(level), z, c, t, x, y, w, h, out.ctypes.data,
+                                               max(out.nbytes, 1)))
+        return out
+
+    def read_regions(self, ctx, level, reqs, w, h, out=None, region_stride=None):
+        """reqs = [(z, c, t, x, y)], every region w x h of `level`, read and decoded on ctx's GPU
+        (omr_tiff_image_read_regions_device).  Returns a device uint8 tensor [n][region_stride]
+        (allocated when out is None; region_stride defaults to the region's bytes rounded up to
+        16): region i is its first w*h*bytes_per_pixel bytes, rows packed, file byte order."""
+        import torch
+        n = len(reqs)
+        bpp = _lib.BYTES_PER_PIXEL[self.pixel_type]
+        if region_stride is None:
+            region_stride = (w * h * bpp + 15) // 16 * 16
+        if out is None:
+            out = torch.zeros((max(n, 1), max(region_stride, 1)), dtype=torch.uint8, device=f"cuda:{ctx.device}")
+            ctx.order_after_torch()
+        tab = (_lib.RawTileRequest * max(n, 1))()
+        for i, r in enumerate(reqs):
+            tab[i].z, tab[i].c, tab[i].t, tab[i].x, tab[i].y = [int(v) for v in r]
+        _lib.check(lib.omr_tiff_image_read_regions_device(ctx.h, self.h, int(level), ctypes.addressof(tab), n, int(w),
+                                                          int(h), out.data_ptr(), int(region_stride)), ctx.h)
+        return out[:n]
+
+    def render_tiles(self, ctx, qdef, channels, level, requests, width, height, out=None, flip_h=False,
+                     flip_v=False, bindings=None):
+        """Context.render_pixel_buffer_tiles for this image's `level` (omr_render_tiff_tiles):
+        requests = [(z, t, x, y)]; out: host numpy [n][h][w] uint32 (allocated when None) or a
+        device tensor (rendered in place)."""
+        from .context import _ptr, make_bindings
+        arr, keep = make_bindings(channels) if bindings is None else bindings
+        n = len(requests)
+        reqs = (_lib.TileRequest * max(n, 1))(*[_lib.TileRequest(*r) for r in requests])
+        on_device = out is not None and hasattr(out, "data_ptr")
+        if out is None:
+            out = np.empty((n, height, width), dtype=np.uint32)
+        _lib.check(lib.omr_render_tiff_tiles(ctx.h, self.h, int(level), ctypes.byref(qdef), arr, len(channels), reqs, n,
+                                             int(width), int(height), int(flip_h), int(flip_v), _ptr(out),
+                                             int(on_device)), ctx.h)
+        return out
+
+
+def lzw_decode_host(stream, expected):
+    """The host LZW decoder alone (omr_lzw_decode_host): `expected` bytes, or OmrError(INTERNAL)."""
+    src = np.frombuffer(bytes(stream), dtype=np.uint8)
+    out = np.zeros(max(int(expected), 1), dtype=np.uint8)
+    _lib.check(lib.omr_lzw_decode_host(src.ctypes.data if src.size else None, src.size, out.ctypes.data, int(expected)))
+    return out[:int(expected)].tobytes()

@@ -25,7 +25,8 @@ for s in $SRCS; do
 done
 for p in $pids; do wait $p || exit 1; done
 skip=$(for s in $SRCS; do basename $s .hip; done | paste -sd'|')
-objs="$T/*.o $(ls $P/build/*.o | grep -v -E "^$P/build/($skip)\.o$")"
+# (the in-tree kernels' objects are build/<name>.hip.o; omr_tiffread also has a .cpp, build/omr_tiffread.o)
+objs="$T/*.o $(ls $P/build/*.o | grep -v -E "^$P/build/($skip)\.hip\.o$")"
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $R/ab/libomr_$NAME.so $objs || exit 1
 rm -rf $T
 echo "ab/libomr_$NAME.so"

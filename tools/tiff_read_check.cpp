@@ -1,0 +1,307 @@
+// tiff_read_check.cpp — the TIFF reader's parser and host LZW decoder (omr_tiffread.cpp, K13) under
+// AddressSanitizer and UBSan, as a stand-alone CPU program: a small LZW-compressed tiled file is
+// built here, read back, then damaged in the ways a user-uploaded file can be -- truncated, an
+// offset or a count past the end, a looping IFD chain, an overflowing count, bad LZW codes, a
+// stream that ends early -- and after that byte by byte at random; every damaged file must be
+// answered with a status, never with a read or write out of bounds.  The decoder's output buffers
+// are exactly as large as the segment, so a byte written past one is caught.
+// Built and run by `make -C omero-ms-image-region_amd tiff-read-check`.
+#include <unistd.h>
+
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "omr_internal.h"
+
+// what omr_tiffread.cpp takes from the rest of the library (the device route is not run here)
+namespace omr {
+int bytes_per_pixel(int32_t t) {
+    switch (t) {
+    case OMR_PIXELS_INT8: case OMR_PIXELS_UINT8: return 1;
+    case OMR_PIXELS_INT16: case OMR_PIXELS_UINT16: return 2;
+    case OMR_PIXELS_INT32: case OMR_PIXELS_UINT32: case OMR_PIXELS_FLOAT: return 4;
+    case OMR_PIXELS_DOUBLE: return 8;
+    default: return 0;
+    }
+}
+omr_status fail(Ctx*, omr_status s, const std::string&) { return s; }
+omr_status hip_fail(Ctx*, hipError_t, const char*) { return OMR_DEVICE; }
+omr_status launch_lzw_decode(Ctx*, const uint8_t*, const uint64_t*, const uint32_t*, const uint32_t*, int32_t, uint8_t*,
+                             const uint64_t*, int32_t*) { return OMR_DEVICE; }
+omr_status launch_tiff_place(Ctx*, const TiffPlace*, int32_t, int32_t, int32_t, int32_t, bool) { return OMR_DEVICE; }
+}  // namespace omr
+extern "C" omr_status omr_ctx_synchronize(omr_ctx*) { return OMR_DEVICE; }
+extern "C" omr_status omr_render_batch_strided_device(omr_ctx*, const omr_quantum_def*, const omr_channel_binding*, int32_t,
+                                                      const void*, int64_t, int64_t, int32_t, int64_t, int32_t, int32_t,
+                                                      int32_t, int32_t, int32_t, int32_t, uint32_t*, int32_t*) {
+    return OMR_DEVICE;
+}
+
+static int g_fail = 0;
+#define CHECK(c) do { if (!(c)) { std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #c); ++g_fail; } } while (0)
+
+// TIFF LZW as libtiff writes it (the writer widens at 512 / 1024 / 2048 and clears at 4094).
+static std::vector<uint8_t> lzw_encode(const std::vector<uint8_t>& d, bool eoi = true) {
+    std::vector<uint8_t> out;
+    uint64_t acc = 0;
+    int nbits = 0;
+    auto put = [&](uint32_t code, int width) {
+        acc = acc << width | code;
+        nbits += width;
+        while (nbits >= 8) {
+            nbits -= 8;
+            out.push_back((uint8_t)(acc >> nbits));
+        }
+        acc &= (1ull << nbits) - 1;
+    };
+    int width = 9;
+    uint32_t next = 258;
+    std::map<uint32_t, uint32_t> table;
+    put(256, width);
+    if (!d.empty()) {
+        uint32_t w = d[0];
+        for (size_t i = 1; i < d.size(); ++i) {
+            const uint32_t key = w << 8 | d[i];
+            auto it = table.find(key);
+            if (it != table.end()) {
+                w = it->second;
+                continue;
+            }
+            put(w, width);
+            table[key] = next++;
+            if (next == 512 || next == 1024 || next == 2048) ++width;
+            if (next == 4094) {
+                put(256, width);
+                width = 9;
+                next = 258;
+                table.clear();
+            }
+            w = d[i];
+        }
+        put(w, width);
+        ++next;
+        if (next == 4094) {
+            put(256, width);
+            width = 9;
+        } else if (next == 512 || next == 1024 || next == 2048) {
+            ++width;
+        }
+    }
+    if (eoi) put(257, width);
+    if (nbits) out.push_back((uint8_t)(acc << (8 - nbits)));
+    return out;
+}
+
+static void le16(std::vector<uint8_t>& f, size_t at, uint32_t v) { f[at] = (uint8_t)v; f[at + 1] = (uint8_t)(v >> 8); }
+static void le32(std::vector<uint8_t>& f, size_t at, uint32_t v) { le16(f, at, v & 0xFFFF); le16(f, at + 2, v >> 16); }
+static uint32_t rd32(const std::vector<uint8_t>& f, size_t at) {
+    return f[at] | f[at + 1] << 8 | f[at + 2] << 16 | (uint32_t)f[at + 3] << 24;
+}
+
+constexpr int W = 50, H = 40, TW = 16, TH = 16, ACROSS = 4, DOWN = 3, NSEG = ACROSS * DOWN;
+
+struct Built {
+    std::vector<uint8_t> file;
+    std::vector<size_t> ifd;           // per plane
+    std::vector<std::vector<uint16_t>> px;
+};
+
+// Two uint16 planes, 16 x 16 tiles, LZW, little-endian, classic TIFF; entry k of an IFD at ifd + 2 + 12 k:
+// 0 width, 1 height, 2 bits, 3 compression, 4 samples, 5 tile width, 6 tile length, 7 offsets, 8 counts, 9 format.
+static Built build() {
+    Built b;
+    std::vector<uint8_t>& f = b.file;
+    f = {'I', 'I', 42, 0, 0, 0, 0, 0};
+    size_t link = 4;
+    for (int p = 0; p < 2; ++p) {
+        std::vector<uint16_t> px((size_t)W * H);
+        for (size_t i = 0; i < px.size(); ++i) px[i] = (uint16_t)((i * 7 + p * 1000) % 311 + (i % W) / 8 * 256);
+        b.px.push_back(px);
+        uint32_t off[NSEG], cnt[NSEG];
+        for (int s = 0; s < NSEG; ++s) {
+            std::vector<uint8_t> seg((size_t)TW * TH * 2, 0);
+            for (int y = 0; y < TH; ++y)
+                for (int x = 0; x < TW; ++x) {
+                    const int ix = s % ACROSS * TW + x, iy = s / ACROSS * TH + y;
+                    if (ix < W && iy < H) std::memcpy(&seg[((size_t)y * TW + x) * 2], &px[(size_t)iy * W + ix], 2);
+                }
+            const std::vector<uint8_t> z = lzw_encode(seg, s % 2 == 0);
+            off[s] = (uint32_t)f.size();
+            cnt[s] = (uint32_t)z.size();
+            f.insert(f.end(), z.begin(), z.end());
+        }
+        if (f.size() % 2) f.push_back(0);
+        const size_t offs_at = f.size();
+        f.resize(f.size() + 8 * NSEG);
+        for (int s = 0; s < NSEG; ++s) {
+            le32(f, offs_at + 4 * s, off[s]);
+            le32(f, offs_at + 4 * NSEG + 4 * s, cnt[s]);
+        }
+        const size_t ifd = f.size();
+        const uint32_t ent[10][4] = {{256, 4, 1, W}, {257, 4, 1, H}, {258, 3, 1, 16}, {259, 3, 1, 5}, {277, 3, 1, 1},
+                                     {322, 3, 1, TW}, {323, 3, 1, TH}, {324, 4, NSEG, (uint32_t)offs_at},
+                                     {325, 4, NSEG, (uint32_t)(offs_at + 4 * NSEG)}, {339, 3, 1, 1}};
+        f.resize(f.size() + 2 + 12 * 10 + 4);
+        le16(f, ifd, 10);
+        for (int k = 0; k < 10; ++k) {
+            le16(f, ifd + 2 + 12 * k, ent[k][0]);
+            le16(f, ifd + 4 + 12 * k, ent[k][1]);
+            le32(f, ifd + 6 + 12 * k, ent[k][2]);
+            le32(f, ifd + 10 + 12 * k, ent[k][3]);
+        }
+        le32(f, link, (uint32_t)ifd);
+        link = ifd + 2 + 12 * 10;
+        b.ifd.push_back(ifd);
+    }
+    return b;
+}
+
+static std::string g_path;
+
+static void put_file(const std::vector<uint8_t>& f) {
+    std::FILE* fp = std::fopen(g_path.c_str(), "wb");
+    if (!fp || std::fwrite(f.data(), 1, f.size(), fp) != f.size()) {
+        std::printf("cannot write %s\n", g_path.c_str());
+        std::exit(2);
+    }
+    std::fclose(fp);
+}
+
+// Open and, when that works, read both planes whole and in pieces; returns the first failing status.
+static omr_status run(const std::vector<uint8_t>& f, const Built* expect = nullptr) {
+    put_file(f);
+    omr_tiff_image* img = nullptr;
+    omr_status st = omr_tiff_image_open(g_path.c_str(), 1, 2, 1, "XYZCT", &img);
+    if (st) {
+        CHECK(img == nullptr);
+        return st;
+    }
+    omr_tiff_info info;
+    CHECK(omr_tiff_image_info(img, &info) == OMR_OK);
+    int32_t sizes[2] = {0, 0};
+    CHECK(omr_tiff_image_level_sizes(img, sizes, 1) >= 1);
+    omr_status first = OMR_OK;
+    if (sizes[0] <= 4096 && sizes[1] <= 4096 && info.segment_width <= 4096 && info.segment_height <= 4096) {
+        for (int c = 0; c < 2; ++c) {
+            std::vector<uint8_t> out((size_t)sizes[0] * sizes[1] * omr::bytes_per_pixel(info.pixel_type));   // exactly: ASan guards the rest
+            st = omr_tiff_image_get_tile(img, 0, 0, c, 0, 0, 0, sizes[0], sizes[1], out.data(), out.size());
+            if (st && !first) first = st;
+            if (!st && expect) CHECK(std::memcmp(out.data(), expect->px[(size_t)c].data(), out.size()) == 0);
+            std::vector<uint8_t> one(8);
+            st = omr_tiff_image_get_tile(img, 0, 0, c, 0, sizes[0] - 1, sizes[1] - 1, 1, 1, one.data(), one.size());
+            if (st && !first) first = st;
+        }
+    }
+    omr_tiff_image_close(img);
+    return first;
+}
+
+int main() {
+    char tmpl[] = "/tmp/tiff_read_check_XXXXXX";
+    const int fd = mkstemp(tmpl);
+    if (fd < 0) return 2;
+    ::close(fd);
+    g_path = tmpl;
+    const Built b = build();
+    const std::vector<uint8_t>& good = b.file;
+    CHECK(run(good, &b) == OMR_OK);
+
+    // the corrupt files of tests/test_tiff_read_host.py
+    const size_t e = b.ifd[0] + 2;                         // first entry of IFD 0
+    std::vector<uint8_t> f(good.begin(), good.begin() + good.size() / 2);
+    CHECK(run(f) == OMR_INTERNAL);                         // truncated
+    f.assign(good.begin(), good.begin() + b.ifd[1] + 20);
+    CHECK(run(f) == OMR_INTERNAL);
+    f.assign(good.begin(), good.begin() + 6);
+    CHECK(run(f) == OMR_INTERNAL);
+    f = good;
+    le32(f, rd32(f, e + 12 * 7 + 8) + 8, (uint32_t)good.size() - 3);
+    CHECK(run(f) == OMR_INTERNAL);                         // a segment past the end
+    f = good;
+    le32(f, e + 12 * 7 + 8, (uint32_t)good.size() + 1000);
+    CHECK(run(f) == OMR_INTERNAL);                         // the offsets array past the end
+    f = good;
+    le32(f, b.ifd[1] + 2 + 120, (uint32_t)b.ifd[0]);
+    CHECK(run(f) == OMR_INTERNAL);                         // the chain loops
+    f = good;
+    le32(f, e + 12 * 7 + 4, 0xFFFFFFFFu);
+    CHECK(run(f) == OMR_INTERNAL);                         // count * 4 overflows
+    f = good;
+    le32(f, e + 8, 0x7FFFFFFF);
+    le32(f, e + 12 + 8, 0x7FFFFFFF);
+    CHECK(run(f) == OMR_INTERNAL);                         // 2^54 tiles
+    f = good;
+    le16(f, e + 12 * 5 + 8, 0);
+    CHECK(run(f) == OMR_INTERNAL);                         // tile width 0
+    f = good;
+    le16(f, e + 12 * 3 + 8, 8);
+    CHECK(run(f) == OMR_INVALID_ARGUMENT);                 // Deflate
+    f = good;
+    le16(f, e + 12 * 5 + 8, 60000);
+    le16(f, e + 12 * 6 + 8, 60000);
+    CHECK(run(f) != OMR_OK);                               // a 7 GB tile
+
+    // streams: a code above the next free entry, one right behind a Clear, a stream that ends early
+    const size_t seg0 = rd32(good, rd32(good, e + 12 * 7 + 8)), cnt_at = rd32(good, e + 12 * 8 + 8);
+    f = good;
+    f[seg0 + 1] = f[seg0 + 2] = 0xFF;
+    CHECK(run(f) == OMR_INTERNAL);
+    f = good;
+    le32(f, cnt_at, rd32(good, cnt_at) / 2);
+    CHECK(run(f) == OMR_INTERNAL);
+    f = good;
+    le32(f, cnt_at, 1);
+    CHECK(run(f) == OMR_INTERNAL);
+    {
+        std::vector<uint8_t> data(5000), out(5000);
+        for (size_t i = 0; i < data.size(); ++i) data[i] = (uint8_t)(i * i % 9);
+        const std::vector<uint8_t> z = lzw_encode(data), zn = lzw_encode(data, false);
+        CHECK(omr_lzw_decode_host(z.data(), z.size(), out.data(), out.size()) == OMR_OK && out == data);
+        CHECK(omr_lzw_decode_host(zn.data(), zn.size(), out.data(), out.size()) == OMR_OK && out == data);
+        std::vector<uint8_t> cut(777);                      // a string that overruns the size is cut
+        CHECK(omr_lzw_decode_host(z.data(), z.size(), cut.data(), cut.size()) == OMR_OK &&
+              std::memcmp(cut.data(), data.data(), cut.size()) == 0);
+        CHECK(omr_lzw_decode_host(z.data(), z.size() / 2, out.data(), out.size()) == OMR_INTERNAL);
+        CHECK(omr_lzw_decode_host(z.data(), 0, out.data(), out.size()) == OMR_INTERNAL);
+        const uint8_t bad[5] = {0x80, 0x01, 0x65, 0x90, 0x10};   // Clear, 5, 300, EOI
+        CHECK(omr_lzw_decode_host(bad, sizeof bad, out.data(), 64) == OMR_INTERNAL);
+        std::vector<uint8_t> old = z;
+        old[0] = 0;
+        old[1] = 1;
+        CHECK(omr_lzw_decode_host(old.data(), old.size(), out.data(), out.size()) == OMR_INTERNAL);
+        std::vector<uint8_t> run255(100000, 0xFF);          // every 12-bit code 4095, and other repeats
+        for (int v : {0xFF, 0x00, 0x80, 0x55}) {
+            std::fill(run255.begin(), run255.end(), (uint8_t)v);
+            std::vector<uint8_t> o(70000);
+            (void)omr_lzw_decode_host(run255.data(), run255.size(), o.data(), o.size());
+        }
+    }
+
+    // random damage: any status, no bad access (the sanitizers are the check)
+    uint64_t rng = 0x9E3779B97F4A7C15ull;
+    auto next = [&] {
+        rng ^= rng << 13; rng ^= rng >> 7; rng ^= rng << 17;
+        return rng;
+    };
+    int opened = 0;
+    for (int it = 0; it < 3000; ++it) {
+        f = good;
+        const int hits = 1 + (int)(next() % 4);
+        for (int k = 0; k < hits; ++k) {
+            // half of the damage goes to the IFDs and their arrays, where the parser looks
+            const size_t at = next() % 2 ? b.ifd[next() % 2] - 8 * NSEG + next() % (8 * NSEG + 126) : next() % f.size();
+            f[at] = next() % 3 ? (uint8_t)next() : (uint8_t)(next() % 2 ? 0xFF : 0x00);
+        }
+        if (it % 7 == 0) f.resize(next() % f.size());
+        opened += run(f) == OMR_OK;
+    }
+    std::printf("tiff_read_check: %d of 3000 damaged files still read\n", opened);
+    ::unlink(g_path.c_str());
+    std::printf(g_fail ? "tiff_read_check: %d check(s) failed\n" : "tiff_read_check: ok\n", g_fail);
+    return g_fail ? 1 : 0;
+}
