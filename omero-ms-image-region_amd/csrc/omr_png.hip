@@ -833,21 +833,6 @@ __device__ __forceinline__ uint32_t pngb_block_excl_scan(uint32_t v, uint32_t* s
     return off + x - v;
 }
 
-// Measurement build only (tools/ab_build.sh <name> -DOMR_PNG_T3_PROBE): block 0's shader-clock
-// stamps at the phases of the table build, read back by omr_png_t3_probe (tools/png_batch_probe.py).
-#ifdef OMR_PNG_T3_PROBE
-__device__ unsigned long long g_t3[32];
-#define T3MARK(i) do { if (blockIdx.x == 0 && threadIdx.x == 0) g_t3[i] = __builtin_amdgcn_s_memtime(); } while (0)
-// P4 phases of one workgroup in the middle of the grid, in g_t3[16 + i]
-#define T4MARK(i) do { if (blockIdx.x == gridDim.x / 2 && threadIdx.x == 0) g_t3[16 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
-extern "C" int omr_png_t3_probe(unsigned long long* out) {
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_t3), sizeof(g_t3)) == hipSuccess ? 0 : 1;
-}
-#else
-#define T3MARK(i) do {} while (0)
-#define T4MARK(i) do {} while (0)
-#endif
-
 // The table block D4/D5 read: codes, lengths and the block header bits.
 struct DflTables {
     uint16_t lcode[286];
@@ -884,7 +869,6 @@ __device__ void huff_lengths_dev(HuffWork& W, int n, int maxbits) {
     if (tid == 0) W.m = 0;
     if (tid < 17) W.bl[tid] = 0;
     __syncthreads();
-    if (n == 286) T3MARK(8);
     // rank among the used symbols in (frequency, symbol) order: with key = f << 9 | symbol (all
     // ones for an unused symbol) a rank is one 64-bit compare per symbol, two keys per broadcast
     // read (round 6: a third of the compares-and-selects of the (f, j < i) test)
@@ -925,7 +909,6 @@ __device__ void huff_lengths_dev(HuffWork& W, int n, int maxbits) {
     for (int k = tid; k < kHuffNodes + m + 1; k += nt)
         W.wt[k] = k < m ? W.f[W.ord[k]] : 0xFFFFFFFFu;
     __syncthreads();
-    if (n == 286) T3MARK(9);
     if (tid == 0) {                                 // two queues: sorted leaves, merged nodes
         // Serial: each merge reads the two queue heads as two adjacent pairs -- leaves past m and
         // nodes not yet merged read INF, so the reads are unconditional and go out together --
@@ -950,7 +933,6 @@ __device__ void huff_lengths_dev(HuffWork& W, int n, int maxbits) {
         }
     }
     __syncthreads();
-    if (n == 286) T3MARK(10);
     const int root = 2 * m - 2;
     for (int k = tid; k < m; k += nt) {             // leaf depth: walk up to the root
         int d = 0;
@@ -958,7 +940,6 @@ __device__ void huff_lengths_dev(HuffWork& W, int n, int maxbits) {
         atomicAdd(&W.bl[min(d, maxbits)], 1);
     }
     __syncthreads();
-    if (n == 286) T3MARK(11);
     if (tid == 0) {                                 // Kraft repair after the clamp (in registers)
         int bl[16];
 #pragma unroll
@@ -990,7 +971,6 @@ __device__ void huff_lengths_dev(HuffWork& W, int n, int maxbits) {
         W.len[W.ord[k]] = (uint8_t)b;
     }
     __syncthreads();
-    if (n == 286) T3MARK(12);
 }
 
 // Canonical codes of W.len (RFC 1951 3.2.2), bit-reversed for LSB-first packing; every thread
@@ -1038,18 +1018,14 @@ __device__ void png_build_tables(const uint32_t* __restrict__ hist, DflTables* _
     __shared__ uint8_t rs[286 + 30], rx[286 + 30];   // run-length symbols and their extra bits
     __shared__ int s_nr, s_hlit, s_hdist;
     const int tid = threadIdx.x;
-    T3MARK(0);
     for (int i = tid; i < 286; i += kHuffThreads) W.f[i] = hist[i] + (i == 256 ? 1u : 0u);   // + EOB
     huff_lengths_dev(W, 286, kMaxBits);
-    T3MARK(1);
     for (int i = tid; i < 286; i += kHuffThreads) t.llen[i] = W.len[i];
     huff_canon_dev(W, 286, t.lcode);
-    T3MARK(2);
     if (tid < 30) W.f[tid] = hist[286 + tid];
     huff_lengths_dev(W, 30, kMaxBits);
     if (tid < 30) t.dlen[tid] = W.len[tid];
     huff_canon_dev(W, 30, t.dcode);
-    T3MARK(3);
     // zlib trees.c scan_tree over the lengths, one thread per run of equal lengths (round 6; the
     // serial walk on lane 0 took ~107k cycles): runs found by a neighbour compare and compacted by
     // a scan, each run's entries counted, scanned and written at their positions -- the same
@@ -1106,13 +1082,11 @@ __device__ void png_build_tables(const uint32_t* __restrict__ hist, DflTables* _
     }
     if (tid < 19) W.f[tid] = 0;
     __syncthreads();
-    T3MARK(4);
     const int nr = s_nr;
     for (int i = tid; i < nr; i += kHuffThreads) atomicAdd(&W.f[rs[i]], 1u);
     huff_lengths_dev(W, 19, 7);
     __shared__ uint16_t ccode[19];
     huff_canon_dev(W, 19, ccode);
-    T3MARK(5);
     // The block header, LSB-first: BFINAL, BTYPE, HLIT, HDIST, HCLEN (17 bits), HCLEN 3-bit
     // code-length-code lengths, then every run-length entry's code + extra bits at its scanned bit
     // offset -- each field ORed into its (at most two) words in parallel.
@@ -1148,11 +1122,9 @@ __device__ void png_build_tables(const uint32_t* __restrict__ hist, DflTables* _
         t.hdr[95] = hbits + ebits;
     }
     __syncthreads();
-    T3MARK(6);
     const uint32_t* src = reinterpret_cast<const uint32_t*>(&t);
     uint32_t* dst = reinterpret_cast<uint32_t*>(T);
     for (int i = tid; i < (int)(sizeof(DflTables) / 4); i += kHuffThreads) dst[i] = src[i];
-    T3MARK(7);
 }
 
 __global__ void __launch_bounds__(kHuffThreads) k_png_tables(const uint32_t* __restrict__ hist, DflTables* __restrict__ T) {
@@ -1616,56 +1588,36 @@ static size_t png_scratch(int kind, int W, int H) { return png_layout(kind, W, H
 //   P3 k_pngb_tables   one workgroup per image: length-limited Huffman code + block header (D3
 //                      on the device: no host round trip; N workgroups run side by side)
 //   P3b k_pngb_block_offsets  one workgroup per image: every parse block's code bits from its
-//                      symbol counts x the code lengths, scanned into bit offsets
-//   P4 k_pngb_encode   one workgroup per 256 segments: the tokens again from the traces and the
-//                      stream bytes, each lane's codes into its LDS column, an in-group scan,
-//                      the columns shifted into the group's words, whole words stored, the
-//                      group's two partial words kept aside
-//   P5 k_pngb_fixup    one lane per group: the words groups share, ORed from the kept parts
+//                      symbol counts x the code lengths, scanned into bit offsets -- and with them
+//                      every stream's length
 //   P5b k_pngb_meta    one workgroup per image: stream length, stored vs dynamic, Adler-32 from
 //                      the row partials
 //   P6 k_pngb_offsets  one workgroup: files' offsets in the output (16-byte aligned), status
-//   P8 k_pngb_emit     16 output bytes per lane: prefix chunks, IDAT header, zlib stream (deflate
-//                      words funnel-shifted, or stored blocks of the filtered stream), Adler,
-//                      IEND — aligned 16-byte stores
-//   P8+P9 k_pngb_emit_crc  (round 6, the default) P8 with each wave's 4 KiB strip CRCed from the
-//                      registers it stores (16-byte braid over the lanes); P9b k_pngb_crc_combine
-//                      moves every strip's CRC to the range end by x^(8n) powers and XORs them
-//   P9 k_pngb_crc      (OMR_PNG_CRC_P9=1: after the plain P8) braided CRC-32 re-reading the file:
-//                      one wave per 16 KiB strip, coalesced dword loads, strips combined by powers
+//   P4 k_pngb_encode   one workgroup per 256 segments: the tokens again from the traces and the
+//                      stream bytes, each lane's codes into its LDS column, an in-group scan,
+//                      the columns shifted into the group's words -- the file's own dwords from
+//                      the stream's first byte on, so the stream is coded in place -- whole words
+//                      stored, the group's two partial words kept aside
+//   P5 k_pngb_fixup    one lane per group: the words groups share, ORed from the kept parts
+//   P8 k_pngb_emit_direct  the file's bytes around the coded stream (prefix chunks, IDAT header,
+//                      zlib header, Adler, IEND); a stored-blocks file whole, 16 bytes per lane
+//   P9 k_pngb_crc      braided CRC-32 over the file: one wave per 16 KiB strip, coalesced dword
+//                      loads, strips combined by x^(8n) powers
 //   P10 k_pngb_finish  one lane per image: the CRC bytes
+// This is the only emit and CRC form.  The forms it replaced in round 6 coded into a words buffer
+// that P8 copied into the files, with the CRC fused into P8 or in P9; they measured slower
+// (CHANGELOG.md K5b-r06 and its profile) and wrote the same bytes, which
+// tests/golden/png_batch_files.json still pins.
 // =====================================================================================
-constexpr int kPngbGroup = 256;                 // segments per P4/P7 group
-constexpr int kPngbEmitBytes = 16 * 256;        // output bytes per P8 workgroup (separate P9)
-// P8 with the IDAT CRC fused (round 6, the default): each wave emits one strip of the file and
-// CRCs the IDAT-range bytes of it from the registers it stored (k_pngb_emit_crc), P9b combines the
-// strips' CRCs (k_pngb_crc_combine), so the file is not read back from HBM by a separate CRC pass.
-// 4 KiB strips (round 6 A/B, profiles/r06/ab_png_crc_strip.txt): at 256 C2 tiles per call 4, 8 and
-// 16 KiB run alike (P8+P9b 0.343-0.348 ms); on the smaller batches of the probe's other cases 4 KiB
-// is 6 % faster (more waves, shorter CRC chains per lane).
-#ifndef OMR_PNG_CRC_STRIP_KIB
-#define OMR_PNG_CRC_STRIP_KIB 4
-#endif
-constexpr int kPngbEmitCrcStrip = OMR_PNG_CRC_STRIP_KIB * 1024;   // bytes a wave emits and CRCs (steps of 1 KiB)
-constexpr int kPngbEmitCrcBytes = 4 * kPngbEmitCrcStrip;   // file bytes per workgroup (4 waves)
-// Direct mode (round 6, the default; env OMR_PNG_DIRECT=0 for the forms below): P5b / P6 run before
-// P4, which codes into the files in place; P8 then stores only the bytes around the streams and
-// P9 CRCs the files (k_pngb_crc).
-static bool png_direct() {
-    static const bool v = [] { const char* e = std::getenv("OMR_PNG_DIRECT"); return !(e && std::atoi(e) == 0); }();
-    return v;
-}
-// env OMR_PNG_CRC_P9=1 (with OMR_PNG_DIRECT=0): the round-5 form (P8 4 KiB per workgroup, then
-// the separate P9 pass); otherwise P8 with the CRC fused (k_pngb_emit_crc)
-static bool png_crc_separate() {
-    static const bool v = [] { const char* e = std::getenv("OMR_PNG_CRC_P9"); return e && std::atoi(e) != 0; }();
-    return v;
-}
+constexpr int kPngbGroup = 256;                 // segments per P4 group
 constexpr int kPngbCrcBytes = 256 * 256;        // CRC range bytes per P9 workgroup
 constexpr int kPngbMaxSide = 4096;
 constexpr int kCrcPowLo = 4096, kCrcPowHi = 2048;
 
-struct PngImg {
+// One image's record, 256 bytes on a 64-byte boundary: every workgroup opens with scalar loads of
+// its image's fields (P4 starts 385 workgroups per 1024^2 tile).  With 232-byte records, which
+// straddle cache lines, P4 measured 0.4 % slower (CHANGELOG.md K5b-one-form).
+struct alignas(64) PngImg {
     const uint32_t* argb;      // kRgb: pixels, row stride W
     const uint8_t* bits;       // kIdx1 / kIdx8: MSB-first mask bits
     // kGray8 / kGray16: the raw-plane source, read in place: the region's pixel (c, r) is the
@@ -1678,11 +1630,11 @@ struct PngImg {
     int32_t rblk0, pad2;                        // first D1 workgroup (kPngRowsPerWg rows each)
     int32_t back, pad;                          // parse look-back (bytes, multiple of 16)
     int64_t rowlen, raw, nseg, nblk;            // row bytes + 1, filtered stream bytes, segments, stored blocks
-    int64_t flt, seg0, words;                   // filtered stream offset (bytes), first segment, first word
-    int64_t tok0;                               // first token slot (tok_at layout)
-    int64_t eblk0, cblk0;                       // first P8 / P9 workgroup
+    int64_t flt, seg0;                          // filtered stream offset (bytes), first segment
+    int64_t cblk0;                              // first P9 workgroup
     uint8_t pre[72];                            // signature, IHDR (+ PLTE, tRNS)
 };
+static_assert(sizeof(PngImg) == 256, "PngImg: whole cache lines");
 
 struct PngMeta {
     int64_t zlen, file_len, off;               // zlib stream bytes; file bytes; offset in the output (-1: none)
@@ -1693,12 +1645,11 @@ struct PngMeta {
 struct PngBatch {
     const PngImg* img;
     int32_t n, uniform;                         // uniform: every image has the same geometry
-    int32_t rblk_per, pblk_per, grp_per, eblk_per, cblk_per;   // per-image counts when uniform
+    int32_t rblk_per, pblk_per, grp_per, cblk_per;   // per-image counts when uniform
     int32_t total_grp, fw_bands;                // fw_bands: row bands per image of the wave-form D1
     const int32_t* rblk0;                       // [n] first D1 workgroup etc. (binary search when not uniform)
     const int32_t* pblk0;
     const int32_t* grp0;
-    const int32_t* eblk0;
     const int32_t* cblk0;
     uint8_t* flt;
     uint16_t* bh;                               // [parse blocks][316] symbol counts of each parse block
@@ -1715,15 +1666,12 @@ struct PngBatch {
     DflTables* tab;                             // [n]
     PngMeta* meta;                              // [n]
     unsigned long long* row_sums;               // [rows][2]
-    uint32_t* words;                            // deflate streams
     uint8_t* out;
     uint64_t out_cap;
     uint64_t* d_offsets;
     uint32_t* d_lengths;
     int32_t* d_status;
     const uint32_t* crc_pow;                    // [kCrcPowAll] (k_png_crc_pow)
-    uint32_t* strip_crc;                        // [P8 workgroups][4] raw CRC of each P8+P9 strip at its end
-    int32_t direct, pad4;                       // P4 codes straight into the files (png_direct())
 };
 
 // Image owning global item `x` of a stage whose per-image first items are `first` (sorted).
@@ -1737,17 +1685,13 @@ __device__ __forceinline__ int pngb_image(const PngBatch& B, const int32_t* firs
     return lo;
 }
 
-// Where P4 / P5 put image I's deflate words, and the bit offset of the stream in them: the words
-// buffer (bit 0), or -- direct mode (round 6) -- the file itself: the stream starts at file byte
-// pre_len + 10 (after the IDAT length and type and the zlib header), so the words are the file's
-// aligned dwords from a = (pre_len + 10) mod 4 bytes before it, and bit 8a is the stream's bit 0.
-// The file offsets (P5b, P6) are known before P4: they follow from P3b's stream lengths.
+// Where P4 / P5 put image I's deflate words, and the bit offset of the stream in them: the file
+// itself.  The stream starts at file byte pre_len + 10 (after the IDAT length and type and the
+// zlib header), so the words are the file's aligned dwords from a = (pre_len + 10) mod 4 bytes
+// before it, and bit 8a is the stream's bit 0.  The file offsets (P5b, P6) are known before P4:
+// they follow from P3b's stream lengths.
 __device__ __forceinline__ uint32_t* pngb_stream_words(const PngBatch& B, const PngImg& I, const PngMeta& M,
                                                        uint32_t& bo) {
-    if (!B.direct) {
-        bo = 0;
-        return B.words + I.words;
-    }
     const int a = (I.pre_len + 10) & 3;
     bo = 8u * (uint32_t)a;
     return reinterpret_cast<uint32_t*>(B.out + M.off + I.pre_len + 10 - a);
@@ -1773,39 +1717,14 @@ __device__ __forceinline__ PngArgs pngb_args(const PngImg& I) {
     return A;
 }
 
-// x^-1 mod P (zlib's reflected form: bit 31 is x^0): with P = x Q + 1, x Q = P + 1 = 1 mod P, so
-// x^-1 = Q = x^31 + x^25 + x^22 + x^21 + x^15 + x^11 + x^10 + x^9 + x^7 + x^6 + x^4 + x^3 + x + 1
-constexpr uint32_t kCrcXInv = (1u << 0) | (1u << 6) | (1u << 9) | (1u << 10) | (1u << 16) | (1u << 20) |
-                              (1u << 21) | (1u << 22) | (1u << 24) | (1u << 25) | (1u << 27) | (1u << 28) |
-                              (1u << 30) | (1u << 31);
-static_assert(multmodp_c(1u << 30, kCrcXInv) == 1u << 31, "x * x^-1 == 1 mod P");
-constexpr int kCrcPowR = kCrcPowLo + kCrcPowHi;   // x^(8 r), r < 256
-constexpr int kCrcInvR = kCrcPowR + 256;          // x^(-8 r), r < 256
-constexpr int kCrcInvA = kCrcInvR + 256;          // x^(-8 256 a), a < 64
-constexpr int kCrcPowAll = kCrcInvA + 64;
+constexpr int kCrcPowAll = kCrcPowLo + kCrcPowHi;
 
-// x^(8*256*j) mod P: [0, 4096) for j, [4096, 6144) for j * 4096; then x^(8 r) and x^(-8 r) for
-// r < 256 and x^(-8*256*a) for a < 64 (one lane per entry).
+// P9's powers, x^(8*256*j) mod P: [0, 4096) for j, [4096, 6144) for j * 4096 (one lane per entry).
 __global__ void __launch_bounds__(256) k_png_crc_pow(uint32_t* __restrict__ pw) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= kCrcPowAll) return;
-    if (i < kCrcPowR) {
-        const uint64_t j = i < kCrcPowLo ? (uint64_t)i : (uint64_t)(i - kCrcPowLo) * kCrcPowLo;
-        pw[i] = x2nmodp(j * 256, 3);
-        return;
-    }
-    const bool inv = i >= kCrcInvR;
-    const uint64_t e = i < kCrcInvR ? (uint64_t)(i - kCrcPowR) : i < kCrcInvA ? (uint64_t)(i - kCrcInvR)
-                                                                             : (uint64_t)(i - kCrcInvA) * 256;
-    if (!inv) { pw[i] = x2nmodp(e, 3); return; }
-    uint32_t xi8 = kCrcXInv;                      // x^-8 = (x^-1)^8
-    for (int k = 0; k < 3; ++k) xi8 = multmodp(xi8, xi8);
-    uint32_t p = 1u << 31, b = xi8;
-    for (uint64_t n = e; n; n >>= 1) {            // (x^-8)^e by squaring
-        if (n & 1) p = multmodp(b, p);
-        b = multmodp(b, b);
-    }
-    pw[i] = p;
+    const uint64_t j = i < kCrcPowLo ? (uint64_t)i : (uint64_t)(i - kCrcPowLo) * kCrcPowLo;
+    pw[i] = x2nmodp(j * 256, 3);
 }
 
 __global__ void __launch_bounds__(256) k_pngb_filter(PngBatch B) {
@@ -1819,12 +1738,9 @@ __global__ void __launch_bounds__(256) k_pngb_filter(PngBatch B) {
 
 // XCD-aware order of a grid's blocks (round 6): workgroup g runs on XCD g mod 8, so handing XCD x
 // the x-th contiguous eighth of the blocks puts a block and the one before it -- whose bytes its
-// look-back windows re-read -- on the same XCD, in the same L2.
-#ifndef OMR_PNG_XCD_ORDER
-#define OMR_PNG_XCD_ORDER 1
-#endif
+// look-back windows re-read -- on the same XCD, in the same L2: P2 reads 806 MB per 256 C2 tiles
+// instead of 1,435 in launch order (profiles/r06/ab_png_xcd_order.txt).
 __device__ __forceinline__ int64_t xcd_block(int64_t g, int64_t total) {
-    if (!OMR_PNG_XCD_ORDER) return g;
     constexpr int64_t X = 8;
     const int64_t q = total / X, r = total % X, x = g % X, k = g / X;
     return x < r ? x * (q + 1) + k : r * (q + 1) + (x - r) * q + k;
@@ -1887,14 +1803,15 @@ __device__ __forceinline__ void wave_lds_sync() {
 template <int M> __host__ __device__ constexpr int fw_row_dwords() { return 3 * 64 * M + 1; }
 template <int M> __host__ __device__ constexpr size_t fw_lds_bytes() { return (size_t)4 * 2 * fw_row_dwords<M>() * 4; }
 
-#ifndef OMR_PNG_FW_WAVES
-#define OMR_PNG_FW_WAVES 5
-#endif
+// Waves per SIMD the wave filters are compiled for: 5 (96 VGPRs), the setting the FULL form was
+// measured with (profiles/r06/ab_png_filter_full.txt); 6 spills and ran 36 % slower
+// (CHANGELOG.md K5b-r06).
+constexpr int kFilterWaves = 5;
 // FULL: W == 256 * M (the 1024-wide tiles at M = 4), so every lane's quads and dwords lie inside
 // the row: no per-dword guards, and the compiler keeps the sums in v_sad_u8's accumulator and
 // batches the LDS reads across dwords.
 template <int M, bool FULL>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OMR_PNG_FW_WAVES))) k_pngb_filter_wave(PngBatch B) {
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kFilterWaves))) k_pngb_filter_wave(PngBatch B) {
     extern __shared__ __attribute__((aligned(16))) uint32_t s_fw[];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int64_t wid = xcd_block(blockIdx.x, gridDim.x) * 4 + wv;   // (XCD order: the band above on the same L2)
@@ -2051,7 +1968,7 @@ template <int M> __host__ __device__ constexpr size_t fg_lds_bytes() { return (s
 // M = 4 holds 16 residual dwords and 4 loads in flight per lane: its 33 KiB of LDS per workgroup
 // allow 4 waves per SIMD anyway, so it takes their 128 VGPRs (5 waves' 96 spilled to scratch).
 template <int BPS, int M, bool FULL>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(M == 4 ? 4 : OMR_PNG_FW_WAVES)))
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(M == 4 ? 4 : kFilterWaves)))
 k_pngb_filter_gray(PngBatch B) {
     extern __shared__ __attribute__((aligned(16))) uint32_t s_fg[];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -2215,17 +2132,9 @@ k_pngb_filter_gray(PngBatch B) {
 // LDS -- [bin / 4][lane & 31]: a lane's adds hit its own bank, no conflicts; at most 4 lanes x 32
 // symbols share a counter, so u8 never wraps.
 // P2 match symbols from a per-workgroup (candidate, length) table instead of pack_match's four
-// table reads and the per-lane candidate distance select (round 6)
-#ifndef OMR_PNG_PARSE_PM
-#define OMR_PNG_PARSE_PM 1
-#endif
-constexpr int kPmLen = 33;
-#ifndef OMR_PNG_HIST_B128
-#define OMR_PNG_HIST_B128 1
-#endif                      // lengths 0..32 (tokens stay inside their segment)
-#ifndef OMR_PNG_LIT_FLAT
-#define OMR_PNG_LIT_FLAT 1
-#endif
+// table reads and the per-lane candidate distance select (round 6,
+// profiles/r06/ab_png_parse_hist.txt)
+constexpr int kPmLen = 33;                      // lengths 0..32 (tokens stay inside their segment)
 constexpr int kHistRows = 316 / 4 + 1;          // dwords of four u8 counters per copy
 
 __device__ __forceinline__ uint32_t eq_mask_q(const uint32_t (&x)[8], const uint32_t (&q)[9], int sh) {
@@ -2255,11 +2164,7 @@ __device__ __forceinline__ void lds_barrier() {
 
 __global__ void __launch_bounds__(kParseLanes) k_pngb_parse(PngBatch B) {
     __shared__ __attribute__((aligned(16))) uint32_t lh[kHistRows * 32];                 // u8 counters [bin / 4][copy]
-#if OMR_PNG_PARSE_PM
     __shared__ uint32_t pm[4 * kPmLen];     // (candidate, length) -> the match's two symbols
-#else
-    __shared__ DeflateTabs T;
-#endif
     const int64_t gblk = xcd_block(blockIdx.x, B.total_pblk);
     const int i = pngb_image(B, B.pblk0, B.pblk_per, gblk);
     const PngImg& I = B.img[i];
@@ -2289,7 +2194,6 @@ __global__ void __launch_bounds__(kParseLanes) k_pngb_parse(PngBatch B) {
         }
     }
     for (int k = threadIdx.x; k < kHistRows * 32; k += kParseLanes) lh[k] = 0;
-#if OMR_PNG_PARSE_PM
     {   // 257 + length symbol | (286 + distance symbol) << 16 of every (candidate, length <= 32)
         const uint32_t dl0[4] = {1u, I.bpp == 1 ? (uint32_t)rowlen : (uint32_t)I.bpp, (uint32_t)(2 * I.bpp),
                                  (uint32_t)rowlen};
@@ -2303,9 +2207,6 @@ __global__ void __launch_bounds__(kParseLanes) k_pngb_parse(PngBatch B) {
             pm[e] = v;
         }
     }
-#else
-    lz_load_tabs(T);
-#endif
     uint32_t* const hl = lh + (threadIdx.x & 31);
     auto count = [&](uint32_t t) {                          // one symbol into this lane's counters
         atomicAdd(hl + ((t >> 2) << 5), 1u << ((t << 3) & 31u));
@@ -2372,31 +2273,20 @@ __global__ void __launch_bounds__(kParseLanes) k_pngb_parse(PngBatch B) {
             M |= 1u << p;
             D |= (uint32_t)bk << (2 * nm++);
             cov |= (best >= 32 ? 0xFFFFFFFFu : ((1u << best) - 1u)) << p;
-#if OMR_PNG_PARSE_PM
             const uint32_t sy = pm[bk * kPmLen + best];     // one LDS read: both symbols
             count(sy & 0xFFFFu);
             count(sy >> 16);
-#else
-            const uint32_t t = pack_match(T, (uint32_t)best, dl[bk]);
-            count(257 + (t & 31));
-            count(286 + ((t >> 5) & 31));
-#endif
             p += best;
         }
         const uint32_t lit = nmask & ~cov;
         S |= lit;
-#if OMR_PNG_LIT_FLAT
         // every byte's add issued, a non-literal's with 0: no exec-mask branch per byte
+        // (profiles/r06/ab_png_crc_dpp_litflat.txt)
 #pragma unroll
         for (int q = 0; q < 32; ++q) {
             const uint32_t b = (x[q >> 2] >> (8 * (q & 3))) & 0xFFu;
             atomicAdd(hl + ((b >> 2) << 5), ((lit >> q) & 1u) << ((b << 3) & 31u));
         }
-#else
-#pragma unroll
-        for (int q = 0; q < 32; ++q)
-            if (lit & (1u << q)) count((x[q >> 2] >> (8 * (q & 3))) & 0xFFu);
-#endif
     }
     lds_barrier();
     // per-block counts: bins 4r..4r+3 summed over the 32 copies of row r (u16 pairs: <= 32 x 128);
@@ -2404,9 +2294,8 @@ __global__ void __launch_bounds__(kParseLanes) k_pngb_parse(PngBatch B) {
     uint16_t* bh = B.bh + (size_t)gblk * 316;               // <= 4096 symbols per block: u16
     for (int r = threadIdx.x; r < kHistRows; r += kParseLanes) {
         uint32_t ev = 0, od = 0;
-#if OMR_PNG_HIST_B128
         // four copies per 16-byte read (rotated by the row: 8 lanes cover the 32 banks); even bytes
-        // by a mask, odd ones by a v_perm, two dwords per v_add3
+        // by a mask, odd ones by a v_perm, two dwords per v_add3 (profiles/r06/ab_png_parse_hist.txt)
         const uint4* row4 = reinterpret_cast<const uint4*>(lh + r * 32);
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
@@ -2416,14 +2305,6 @@ __global__ void __launch_bounds__(kParseLanes) k_pngb_parse(PngBatch B) {
             od += __builtin_amdgcn_perm(0u, v.x, 0x0C030C01u) + __builtin_amdgcn_perm(0u, v.y, 0x0C030C01u);
             od += __builtin_amdgcn_perm(0u, v.z, 0x0C030C01u) + __builtin_amdgcn_perm(0u, v.w, 0x0C030C01u);
         }
-#else
-#pragma unroll 8
-        for (int c = 0; c < 32; ++c) {
-            const uint32_t v = lh[r * 32 + ((c + r) & 31)];  // rotated start: rows spread over banks
-            ev += v & 0x00FF00FFu;
-            od += (v >> 8) & 0x00FF00FFu;
-        }
-#endif
         const uint32_t cnt[4] = {ev & 0xFFFFu, od & 0xFFFFu, ev >> 16, od >> 16};
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -2461,14 +2342,10 @@ __global__ void __launch_bounds__(320) k_pngb_hist(PngBatch B) {
 // symbol counts times the code lengths (extra bits included), an exclusive scan over the image's
 // blocks from the header's end gives every block's first bit -- so P4 needs no inter-block
 // communication at all.
-#ifndef OMR_PNG_BOFF_WAVE
-#define OMR_PNG_BOFF_WAVE 1
-#endif
-#if OMR_PNG_BOFF_WAVE
 // (round 6) A wave per parse block: the lanes read the block's 632-byte count row together (three
 // coalesced loads instead of 158 row-strided ones per lane), multiply by the code lengths held in
 // registers and sum by DPP; four blocks' loads in flight per wave, 16 waves, chunks of 1024 blocks
-// scanned by the workgroup.
+// scanned by the workgroup (profiles/r06/ab_png_block_offsets.txt).
 constexpr int kBoffThreads = 1024, kBoffChunk = 1024;
 __global__ void __launch_bounds__(kBoffThreads) k_pngb_block_offsets(PngBatch B) {
     __shared__ uint32_t s_bits[kBoffChunk];
@@ -2528,70 +2405,29 @@ __global__ void __launch_bounds__(kBoffThreads) k_pngb_block_offsets(PngBatch B)
     }
     if (threadIdx.x == 0) B.img_bits[i] = s_carry + T->llen[256];   // + EOB
 }
-#else
-constexpr int kBoffThreads = 256;
-__global__ void __launch_bounds__(256) k_pngb_block_offsets(PngBatch B) {
-    __shared__ uint32_t cost[316];
-    __shared__ uint32_t s_wave[4];
-    __shared__ uint32_t s_carry;
-    const int i = blockIdx.x;
-    const PngImg& I = B.img[i];
-    const DflTables* T = B.tab + i;
-    for (int k = threadIdx.x; k < 316; k += 256) {
-        uint32_t c;
-        if (k < 257) c = T->llen[k];
-        else if (k < 286) c = T->llen[k] + len_xbits_of(k - 257);
-        else c = T->dlen[k - 286] + dist_xbits_of(k - 286);
-        cost[k] = c;
+
+// The codes of one packed token through put(value, bits), with the code tables packed as
+// code | length << 16: a literal is one put, a match two (its extra bits ride above each code).
+template <typename Put>
+__device__ __forceinline__ void put_token_packed(uint32_t t, const uint32_t* lc, const uint32_t* dc, Put& put) {
+    if (!(t & 0x80000000u)) {
+        const uint32_t e = lc[t];
+        put(e & 0xFFFFu, (int)(e >> 16));
+        return;
     }
-    const uint32_t hb = T->hdr[95];
-    if (threadIdx.x == 0) s_carry = hb;
-    __syncthreads();
-    const int64_t p0 = B.uniform ? (int64_t)i * B.pblk_per : I.pblk0;
-    const int npb = (int)((I.nseg + kParseLanes - 1) / kParseLanes);
-    for (int j0 = 0; j0 < npb; j0 += 256) {
-        const int j = j0 + threadIdx.x;
-        uint32_t bits = 0;
-        if (j < npb) {
-            const uint32_t* c2 = reinterpret_cast<const uint32_t*>(B.bh + (size_t)(p0 + j) * 316);   // 4-aligned
-            for (int k = 0; k < 158; ++k) {
-                const uint32_t v = c2[k];
-                bits += (v & 0xFFFFu) * cost[2 * k] + (v >> 16) * cost[2 * k + 1];
-            }
-        }
-        uint32_t tot;
-        const uint32_t ex = pngb_block_excl_scan(bits, s_wave, tot);
-        const uint32_t base = s_carry;
-        if (j < npb) B.poff[p0 + j] = base + ex;
-        __syncthreads();
-        if (threadIdx.x == 0) s_carry = base + tot;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) B.img_bits[i] = s_carry + T->llen[256];   // + EOB
+    const int ls = (int)(t & 31), ds = (int)((t >> 5) & 31);
+    const uint32_t le = lc[257 + ls], de = dc[ds];
+    const int ll = (int)(le >> 16), dn = (int)(de >> 16);
+    put((le & 0xFFFFu) | (((t >> 10) & 31u) << ll), ll + len_xbits_of(ls));          // <= 20 bits
+    put((de & 0xFFFFu) | (((t >> 15) & 0x1FFFu) << dn), dn + dist_xbits_of(ds));     // <= 28 bits
 }
 
-#endif
-
-// The tokens of a segment from its parse trace (P2): t as lz_seg_tokens produced them.
-template <typename Byte, typename Tok>
-__device__ __forceinline__ void trace_tokens(uint32_t S, uint32_t M, uint32_t D, int n, Byte&& seg,
-                                             const uint32_t (&dl)[4], const DeflateTabs& T, Tok&& tok) {
-    while (S) {
-        const int p = __builtin_ctz(S);
-        S &= S - 1;
-        const int q = S ? __builtin_ctz(S) : n;
-        if ((M >> p) & 1u) {
-            tok(pack_match(T, (uint32_t)(q - p), dl[D & 3u]));
-            D >>= 2;
-        } else {
-            tok(seg(p));
-        }
-    }
-}
-
-// The encoder's walk of a segment's parse trace: the tokens of trace_tokens, coded through
-// put(value, bits), two adjacent literals at a time (their codes, <= 15 bits each, joined into one
-// put): literal runs -- most of a photographic tile -- take half the iterations.
+// The walk of a segment's parse trace (P2) that P4's pass 2 codes a long lane with: the tokens as
+// lz_seg_tokens produced them -- a match where M marks a token start, its length the distance to
+// the next start, its candidate the next two bits of D -- coded through put(value, bits) of at
+// most 32 bits, two adjacent literals at a time (their codes, <= 15 bits each, joined into one
+// put).  Long lanes are rare, so this walk may branch (with the four-literal walk below in its
+// place P4 ran the same, CHANGELOG.md K5b-r06).
 template <typename Byte, typename Put>
 __device__ __forceinline__ void trace_codes(uint32_t S, uint32_t M, uint32_t D, int n, Byte&& seg,
                                             const uint32_t (&dl)[4], const DeflateTabs& T, const uint32_t* lc,
@@ -2617,41 +2453,19 @@ __device__ __forceinline__ void trace_codes(uint32_t S, uint32_t M, uint32_t D, 
     }
 }
 
-// P4's pass-1 walk without branches (round 6; OMR_PNG_ENC_FLAT=0 builds the trace_codes form):
-// every step takes one token -- a match, or one or two literals -- and puts its whole code at
-// once.  A match's code comes from one 8-byte table entry per (distance candidate, length) --
-// the four candidate distances are the image's, a length is <= 32 (tokens stay inside their
-// segment) -- holding the length code + extra bits, then the distance code + extra bits (<= 48
-// bits), and the bit count in bits 58-63.  The literal and match values are both formed and one
-// selected, so a wave with literals in some lanes and matches in others runs one path instead of
-// both under masks (the branchy walk ran ~140 instructions per step).
+// P4's pass-1 walk, without branches (round 6): every step takes one token -- a match, or up to
+// four literals in a row -- and puts its whole code at once.  A match's code comes from one
+// 8-byte table entry per (distance candidate, length) -- the four candidate distances are the
+// image's, a length is <= 32 (tokens stay inside their segment) -- holding the length code + extra
+// bits, then the distance code + extra bits (<= 48 bits), and the bit count in bits 58-63.  The
+// literal and match values are both formed and one selected, so a wave with literals in some lanes
+// and matches in others runs one path instead of both under masks (the branchy walk ran ~140
+// instructions per step).  The four bytes from p come out of the lane's stream column as one word
+// (two reads and an alignbyte), their four codes are read, and those past the run of literals get
+// length 0 -- a literal-heavy segment (most of a photographic tile) takes 8 steps instead of the
+// 16 of a walk by literal pairs (profiles/r06/ab_png_encode_quad.txt).  Codes of a step: up to
+// 4 x 15 bits, or a match's <= 48.
 constexpr int kMcLen = 33;                       // match table: [candidate][length 0..32]
-template <typename Byte, typename Put>
-__device__ __forceinline__ void trace_codes_flat(uint32_t S, uint32_t M, uint32_t D, int n, Byte&& seg,
-                                                 const uint64_t* mc, const uint32_t* lc, Put& put) {
-    while (S) {
-        const int p = __builtin_ctz(S);
-        S &= S - 1;
-        const int q = S ? __builtin_ctz(S) : n;
-        const bool ism = (M >> p) & 1u;
-        const uint64_t me = mc[(D & 3u) * kMcLen + (uint32_t)(q - p)];
-        const uint32_t e1 = lc[seg(p)];
-        // a literal followed by a literal (the next byte starts a token that is no match)
-        const bool pair = !ism && q < n && !((M >> q) & 1u);
-        const uint32_t e2 = lc[seg(pair ? q : p)];
-        const uint32_t n1 = e1 >> 16, n2 = pair ? e2 >> 16 : 0u;
-        const uint64_t lv = (e1 & 0xFFFFu) | (pair ? (e2 & 0xFFFFu) << n1 : 0u);
-        put(ism ? me & 0xFFFFFFFFFFFFull : lv, ism ? (uint32_t)(me >> 58) : n1 + n2);
-        S = pair ? S & (S - 1) : S;
-        D = ism ? D >> 2 : D;
-    }
-}
-
-// The same walk taking up to four literals in a row per step (OMR_PNG_ENC_FLAT=2, the default):
-// the four bytes from p come out of the lane's stream column as one word (two reads and an
-// alignbyte), their four codes are read, and those past the run of literals get length 0 -- a
-// literal-heavy segment (most of a photographic tile) takes 8 steps instead of 16.  Codes of a
-// step: up to 4 x 15 bits, or a match's <= 48.
 template <typename Word4, typename Put>
 __device__ __forceinline__ void trace_codes_quad(uint32_t S, uint32_t M, uint32_t D, int n, Word4&& seg4,
                                                  const uint64_t* mc, const uint32_t* lc, Put& put) {
@@ -2685,74 +2499,42 @@ __global__ void __launch_bounds__(kHuffThreads) k_pngb_tables(PngBatch B) {
 // LDS for 8 bits per stream byte + header; a group whose codes need more (<= 16 bits per byte:
 // high-entropy data) ORs its interior words straight into memory (the slow path).
 constexpr int kEncWords = kPngbGroup * kSeg * 8 / 32 + 96 + 4;
-#ifndef OMR_PNG_ENC_SCR
-#define OMR_PNG_ENC_SCR 10
-#endif
 // Words of codes a lane keeps in LDS: 10 (320 bits, 10 bits per stream byte; round 6).  A lane
 // past them codes its tokens again in pass 2 with a word-by-word atomic put, and its wave (and
 // the workgroup's barrier) waits for it: at 8 words (256 bits) enough C2 segments passed that P4
 // ran 1.03 ms per 256 tiles, at 10 or 12 words 0.73-0.75 (profiles/r06/ab_png_encode_scr.txt).
-constexpr int kEncScr = OMR_PNG_ENC_SCR;
-#ifndef OMR_PNG_ENC_LDS_T
-#define OMR_PNG_ENC_LDS_T 0
-#endif
-#ifndef OMR_PNG_ENC_FLAT
-#define OMR_PNG_ENC_FLAT 2
-#endif
+constexpr int kEncScr = 10;
 static_assert(kPngbGroup == 2 * kParseLanes, "P4 groups are two parse blocks");
-
-// The codes of one packed token through put(value, bits), with the code tables packed as
-// code | length << 16: a literal is one put, a match two (its extra bits ride above each code).
-template <typename Put>
-__device__ __forceinline__ void put_token_packed(uint32_t t, const uint32_t* lc, const uint32_t* dc, Put& put) {
-    if (!(t & 0x80000000u)) {
-        const uint32_t e = lc[t];
-        put(e & 0xFFFFu, (int)(e >> 16));
-        return;
-    }
-    const int ls = (int)(t & 31), ds = (int)((t >> 5) & 31);
-    const uint32_t le = lc[257 + ls], de = dc[ds];
-    const int ll = (int)(le >> 16), dn = (int)(de >> 16);
-    put((le & 0xFFFFu) | (((t >> 10) & 31u) << ll), ll + len_xbits_of(ls));          // <= 20 bits
-    put((de & 0xFFFFu) | (((t >> 15) & 0x1FFFu) << dn), dn + dist_xbits_of(ds));     // <= 28 bits
-}
 
 __global__ void __launch_bounds__(kPngbGroup) k_pngb_encode(PngBatch B) {
     // the group's stream bytes, [dword][lane] (pass 1: a lane reads only its own column, each
     // read on its own bank), then in the same LDS the group's code words (pass 2)
     __shared__ __attribute__((aligned(16))) uint32_t s_buf[kEncWords];
     static_assert(kEncWords * 4 >= kPngbGroup * kSeg, "stream bytes fit the word buffer");
-#if OMR_PNG_ENC_LDS_T
-    __shared__ DeflateTabs T;
-#else
     // (round 6) the deflate tables from constant memory: they serve only the (candidate, length)
-    // table build and the rare long-lane re-code, and their 1.2 KiB of LDS lets a seventh
-    // workgroup onto the CU
+    // table build and the rare long-lane re-code, and the 1.2 KiB of LDS a copy took lets a seventh
+    // workgroup onto the CU (profiles/r06/ab_png_encode_tables_const.txt)
     const DeflateTabs& T = c_dfl;
-#endif
     __shared__ uint32_t lc[286], dc[30];                        // code | length << 16
     __shared__ uint32_t scr[(kEncScr + 2) * kPngbGroup];        // [word][lane]: each lane's codes from bit 0
                                                                 // (+2 rows: pass 1's spill, see put)
     __shared__ uint32_t s_end[2];                               // slow path: the group's first / last word
     __shared__ uint32_t s_wave[kPngbGroup / 64];
-#if OMR_PNG_ENC_FLAT
-    __shared__ uint64_t mc[4 * kMcLen];                         // match codes (trace_codes_flat)
-#endif
+    __shared__ uint64_t mc[4 * kMcLen];                         // match codes (trace_codes_quad)
     const int i = pngb_image(B, B.grp0, B.grp_per, blockIdx.x);
     const PngImg& I = B.img[i];
     const int64_t gfirst = B.uniform ? (int64_t)i * B.grp_per : I.grp0;
     const int64_t blk = (int64_t)blockIdx.x - gfirst;
     const int64_t g = blockIdx.x;                               // this workgroup's group
     const DflTables* Tb = B.tab + i;
-    T4MARK(0);
     // the group's bit range from P3b: its first parse block's offset (the header opens group 0)
     // to the next group's (or the stream's end)
     const int64_t p0 = B.uniform ? (int64_t)i * B.pblk_per : I.pblk0;
     const int npb = (int)((I.nseg + kParseLanes - 1) / kParseLanes);
     // stored blocks win for this image (P5b decides the same from the same bits): nothing to code;
-    // direct mode: nor for a file without a slot in the output
+    // nor for a file without a slot in the output
     if (2 + ((int64_t)B.img_bits[i] + 7) / 8 + 4 >= 2 + 5 * I.nblk + I.raw + 4) return;
-    if (B.direct && B.meta[i].off < 0) return;
+    if (B.meta[i].off < 0) return;
     uint32_t bo;                                                // the stream's bit 0 in the words
     uint32_t* w = pngb_stream_words(B, I, B.meta[i], bo);
     // (group 0 owns the bits below bo too: zero here, the zlib header's bytes are stored by P8)
@@ -2777,9 +2559,6 @@ __global__ void __launch_bounds__(kPngbGroup) k_pngb_encode(PngBatch B) {
         else if (li == 0 || li == nwl) orw(li, v);
         else w[w0 + li] = v;
     };
-#if OMR_PNG_ENC_LDS_T
-    lz_load_tabs(T);
-#endif
     const int64_t s = blk * kPngbGroup + threadIdx.x;
     const bool live = s < I.nseg;
     uint32_t x[kSeg / 4] = {};                                  // the lane's 32 stream bytes
@@ -2797,14 +2576,11 @@ __global__ void __launch_bounds__(kPngbGroup) k_pngb_encode(PngBatch B) {
         for (int k = 0; k < kSeg / 4; ++k) s_buf[k * kPngbGroup + threadIdx.x] = x[k];
     }
     __syncthreads();
-    T4MARK(1);
     const bool last = s == I.nseg - 1;                          // the EOB code follows its tokens
     int n = 0;
     const uint32_t dl[4] = {1u, I.bpp == 1 ? (uint32_t)I.rowlen : (uint32_t)I.bpp, (uint32_t)(2 * I.bpp),
                             (uint32_t)I.rowlen};               // lz_seg_prepare's candidates
-    auto seg_byte = [&](int p) { return (s_buf[(p >> 2) * kPngbGroup + threadIdx.x] >> (8 * (p & 3))) & 0xFFu; };
     uint32_t nb = 0;
-#if OMR_PNG_ENC_FLAT
     if (threadIdx.x < 4 * kMcLen) {                             // (lc, dc, T are staged: barrier above)
         const int k = threadIdx.x / kMcLen, l = threadIdx.x % kMcLen;
         uint64_t e = 0;
@@ -2845,7 +2621,6 @@ __global__ void __launch_bounds__(kPngbGroup) k_pngb_encode(PngBatch B) {
             nw += wn;
             nacc = tot & 31u;
         };
-#if OMR_PNG_ENC_FLAT == 2
         auto seg4 = [&](int p) {                                // stream bytes p .. p + 3 of the lane
             const int d = p >> 2;
             const uint32_t lo = s_buf[d * kPngbGroup + threadIdx.x];
@@ -2853,38 +2628,10 @@ __global__ void __launch_bounds__(kPngbGroup) k_pngb_encode(PngBatch B) {
             return __builtin_amdgcn_alignbyte(hi, lo, (uint32_t)(p & 3));
         };
         trace_codes_quad(S, M, D, n, seg4, mc, lc, put);
-        (void)seg_byte;
-#else
-        trace_codes_flat(S, M, D, n, seg_byte, mc, lc, put);
-#endif
         if (last) put(lc[256] & 0xFFFFu, lc[256] >> 16);
         if (nacc > 0 && nw < (uint32_t)kEncScr) scr[nw * kPngbGroup + threadIdx.x] = (uint32_t)acc;
         nb = 32 * nw + nacc;
     }
-#else
-    // pass 1: the lane's codes from bit 0 into its scratch column (a lane whose codes pass
-    // kEncScr words only counts them and codes again in pass 2)
-    if (live) {
-        n = (int)min((int64_t)kSeg, I.raw - s * kSeg);
-        uint64_t acc = 0;
-        int nacc = 0;
-        uint32_t nw = 0;
-        auto put = [&](uint32_t v, int bits) {
-            acc |= (uint64_t)v << nacc;
-            nacc += bits;
-            if (nacc >= 32) {
-                if (nw < (uint32_t)kEncScr) scr[nw * kPngbGroup + threadIdx.x] = (uint32_t)acc;
-                ++nw;
-                acc >>= 32;
-                nacc -= 32;
-            }
-        };
-        trace_codes(S, M, D, n, seg_byte, dl, T, lc, dc, put);
-        if (last) put(lc[256] & 0xFFFFu, (int)(lc[256] >> 16));
-        if (nacc > 0 && nw < (uint32_t)kEncScr) scr[nw * kPngbGroup + threadIdx.x] = (uint32_t)acc;
-        nb = 32 * nw + (uint32_t)nacc;
-    }
-#endif
     // a lane whose codes passed its scratch column codes them again in pass 2, from its stream
     // bytes kept in that column (the stream buffer becomes the word buffer; the scan's barriers
     // order these copies before it is zeroed)
@@ -2892,7 +2639,6 @@ __global__ void __launch_bounds__(kPngbGroup) k_pngb_encode(PngBatch B) {
 #pragma unroll
         for (int k = 0; k < kSeg / 4; ++k) scr[k * kPngbGroup + threadIdx.x] = x[k];
     }
-    T4MARK(2);
     uint32_t total;
     const uint32_t ex = pngb_block_excl_scan(nb, s_wave, total);
     const uint32_t hb = Tb->hdr[95];
@@ -2907,7 +2653,6 @@ __global__ void __launch_bounds__(kPngbGroup) k_pngb_encode(PngBatch B) {
         __threadfence_block();                                  // the zeroed words before any OR
     }
     __syncthreads();
-    T4MARK(3);
     if (blk == 0 && threadIdx.x == 0) {                         // the block header, from bit bo
         const uint32_t nh = (hb + 31) / 32;
         uint32_t prev = 0;
@@ -2953,7 +2698,6 @@ __global__ void __launch_bounds__(kPngbGroup) k_pngb_encode(PngBatch B) {
         }
     }
     __syncthreads();
-    T4MARK(4);
     // whole words inside [b0, b1) go out; the first and last (shared with the neighbouring
     // blocks) are kept for P5
     const uint32_t cf = big ? s_end[0] : sw[0], cl = nwl ? (big ? s_end[1] : sw[nwl]) : 0u;
@@ -2970,7 +2714,6 @@ __global__ void __launch_bounds__(kPngbGroup) k_pngb_encode(PngBatch B) {
         B.blk_cf[g] = cf;
         B.blk_cl[g] = cl;
     }
-    T4MARK(5);
 }
 
 // P5: the words two or more blocks share.  Block g handles the partial word its stream ends in,
@@ -2985,7 +2728,7 @@ __global__ void __launch_bounds__(256) k_pngb_fixup(PngBatch B) {
     if (2 + ((int64_t)B.img_bits[i] + 7) / 8 + 4 >= 2 + 5 * I.nblk + I.raw + 4) return;   // stored: P4 skipped
     const uint32_t b0 = B.blk_b0[g], b1 = B.blk_b1[g], w0 = b0 >> 5, w1 = (b1 - 1) >> 5;
     if ((b1 & 31) == 0 || !(w1 > w0 || (b0 & 31) == 0)) return;
-    if (B.direct && B.meta[i].off < 0) return;
+    if (B.meta[i].off < 0) return;
     uint32_t v = w1 == w0 ? B.blk_cf[g] : B.blk_cl[g];
     for (int64_t j = g + 1; j < gend && B.blk_b0[j] < 32 * (w1 + 1); ++j) v |= B.blk_cf[j];
     uint32_t bo;
@@ -3078,7 +2821,8 @@ __global__ void __launch_bounds__(1024) k_pngb_offsets(PngBatch B) {
 
 __constant__ uint8_t c_iend[12] = {0, 0, 0, 0, 'I', 'E', 'N', 'D', 0xAE, 0x42, 0x60, 0x82};
 
-// Byte k of image I's file (P8's general path).
+// Byte k of image I's file, for P8: any byte of a stored-blocks file; of a dynamic one the bytes
+// around the stream (its interior is coded in place by P4 / P5 and never asked for here).
 __device__ uint32_t pngb_file_byte(const PngBatch& B, const PngImg& I, const PngMeta& M, int64_t k) {
     const int64_t P = I.pre_len;
     if (k < P) return I.pre[k];
@@ -3090,8 +2834,7 @@ __device__ uint32_t pngb_file_byte(const PngBatch& B, const PngImg& I, const Png
         if (k == 0) return 0x78;                       // CMF/FLG: deflate, 32K window, check bits
         if (k == 1) return 0x01;
         if (k >= M.zlen - 4) return (M.adler >> (8 * (M.zlen - 1 - k))) & 0xFF;
-        const int64_t d = k - 2;
-        if (!M.stored) return reinterpret_cast<const uint8_t*>(B.words + I.words)[d];
+        const int64_t d = k - 2;                       // byte of the stored blocks
         const int64_t b = d / (kStored + 5), o = d - b * (kStored + 5);
         if (o >= 5) return B.flt[I.flt + b * kStored + (o - 5)];
         const uint32_t len = (uint32_t)min((int64_t)kStored, I.raw - b * kStored);
@@ -3109,10 +2852,10 @@ __device__ uint32_t pngb_file_byte(const PngBatch& B, const PngImg& I, const Png
     return k < 12 ? c_iend[k] : 0u;
 }
 
-// The 16 bytes of image I's file at k0 outside the dynamic stream's interior (chunk headers,
-// zlib header and Adler, stored blocks, CRC and IEND), byte by byte: a rare path, kept out of line
-// so it does not inflate the callers' registers.
-__device__ __noinline__ uint4 pngb_file_chunk_bytes(const PngBatch& B, const PngImg& I, const PngMeta& M, int64_t k0) {
+// The 16 bytes of a stored-blocks file at k0 (chunk headers, zlib header and Adler, stored blocks,
+// CRC and IEND), byte by byte: a rare path (noise), kept out of line so it does not inflate P8's
+// registers.
+__device__ __noinline__ uint4 pngb_file_chunk(const PngBatch& B, const PngImg& I, const PngMeta& M, int64_t k0) {
     uint32_t o[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -3126,38 +2869,11 @@ __device__ __noinline__ uint4 pngb_file_chunk_bytes(const PngBatch& B, const Png
     return make_uint4(o[0], o[1], o[2], o[3]);
 }
 
-// The 16 bytes of image I's file at k0 (P8's body).
-__device__ __forceinline__ uint4 pngb_file_chunk(const PngBatch& B, const PngImg& I, const PngMeta& M, int64_t k0) {
-    const int64_t d0 = k0 - I.pre_len - 10;            // deflate byte of k0 (dynamic stream)
-    if (!M.stored && d0 >= 0 && k0 + 16 <= I.pre_len + 8 + M.zlen - 4) {
-        const uint32_t* w = B.words + I.words + (d0 >> 2);
-        const int sh = (int)(d0 & 3) * 8;
-        uint32_t x[5], o[4];
-#pragma unroll
-        for (int j = 0; j < 5; ++j) x[j] = w[j];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = sh ? (x[j] >> sh) | (x[j + 1] << (32 - sh)) : x[j];
-        return make_uint4(o[0], o[1], o[2], o[3]);
-    }
-    return pngb_file_chunk_bytes(B, I, M, k0);
-}
-
-// P8: 16 bytes of one file per lane, one aligned 16-byte store (the form with a separate P9).
-__global__ void __launch_bounds__(256) k_pngb_emit(PngBatch B) {
-    const int i = pngb_image(B, B.eblk0, B.eblk_per, blockIdx.x);
-    const PngImg& I = B.img[i];
-    const PngMeta& M = B.meta[i];
-    const int64_t lb = (int64_t)blockIdx.x - (B.uniform ? (int64_t)i * B.eblk_per : I.eblk0);
-    const int64_t k0 = (lb * 256 + threadIdx.x) * 16;
-    if (M.off < 0 || k0 >= M.file_len) return;
-    *reinterpret_cast<uint4*>(B.out + M.off + k0) = pngb_file_chunk(B, I, M, k0);
-}
-
-// P8 in direct mode: the file's bytes around the stream P4 / P5 already coded in place -- the prefix
-// chunks, IDAT length and type, zlib header, Adler-32, IEND (the CRC is P10's) -- by byte stores
-// from each image's first workgroup; a stored-blocks file whole, 16 bytes per lane, as k_pngb_emit,
-// over the image's kEmitDirectWgs workgroups (grid: images x kEmitDirectWgs -- a grid of every
-// file's 4 KiB pieces, nearly all idle here, cost 0.06 ms of dispatch per 256 tiles).
+// P8: the file's bytes around the stream P4 / P5 already coded in place -- the prefix chunks, IDAT
+// length and type, zlib header, Adler-32, IEND (the CRC is P10's) -- by byte stores from each
+// image's first workgroup; a stored-blocks file whole, 16 bytes per lane and aligned 16-byte
+// store, over the image's kEmitDirectWgs workgroups (grid: images x kEmitDirectWgs -- a grid of
+// every file's 4 KiB pieces, nearly all idle here, cost 0.06 ms of dispatch per 256 tiles).
 constexpr int kEmitDirectWgs = 16;
 __global__ void __launch_bounds__(256) k_pngb_emit_direct(PngBatch B) {
     const int i = blockIdx.x / kEmitDirectWgs, lb = blockIdx.x % kEmitDirectWgs;
@@ -3305,151 +3021,6 @@ __global__ void __launch_bounds__(256) k_pngb_crc(PngBatch B) {
     }
 }
 
-// P8+P9 tables: hop[b][v] = raw CRC of byte v at position b of a 4-byte word followed by 3 - b +
-// 1008 zero bytes (the state then sits at the same lane's next 16-byte chunk, 1 KiB on); lane16[k]
-// = x^(8 (1008 - 16 k)), the shift from the end of lane k's last chunk to the end of its strip.
-struct CrcHop {
-    uint32_t hop[4][256];
-    uint32_t lane16[64];
-};
-constexpr CrcHop make_crc_hop() {
-    CrcHop c{};
-    uint32_t t[256] = {}, t0[256] = {};
-    for (uint32_t n = 0; n < 256; ++n) {
-        uint32_t r = n;
-        for (int k = 0; k < 8; ++k) r = (r & 1) ? kCrcPoly ^ (r >> 1) : r >> 1;
-        t[n] = t0[n] = r;
-    }
-    for (int k = 0; k <= 1011; ++k) {          // t = CRC of byte n followed by k zero bytes
-        for (int b = 0; b < 4; ++b)
-            if (k == 1011 - b)
-                for (int n = 0; n < 256; ++n) c.hop[b][n] = t[n];
-        for (int n = 0; n < 256; ++n) t[n] = (t[n] >> 8) ^ t0[t[n] & 0xFF];
-    }
-    uint32_t x8 = 1u << 30;                    // x^1 -> x^8
-    for (int i = 0; i < 3; ++i) x8 = multmodp_c(x8, x8);
-    const uint32_t x32 = multmodp_c(multmodp_c(x8, x8), multmodp_c(x8, x8));
-    const uint32_t x128 = multmodp_c(multmodp_c(x32, x32), multmodp_c(x32, x32));          // x^(8*16)
-    uint32_t p = 1u << 31;                     // lane 63: x^0
-    for (int k = 63; k >= 0; --k) {
-        c.lane16[k] = p;
-        p = multmodp_c(x128, p);
-    }
-    return c;
-}
-__constant__ CrcHop c_hop = make_crc_hop();
-
-// P8 + P9 fused (round 6, the default): each wave emits a strip of the file (lane t, step
-// s: the 16 bytes at strip + 1 KiB s + 16 t -- one coalesced 1 KiB store per step) and CRCs it
-// from the same registers: lane t's 16 bytes are four words through slicing-by-4 tables, the
-// fourth with a table that also hops the state over the other lanes' 1008 bytes to its next chunk
-// (a 16-byte braid); no LDS staging, no barrier after the tables.  Bytes outside the IDAT range
-// ['IDAT', end of the zlib stream) read as 0.  The strip's raw CRC sits at the strip end E; it is
-// moved to the range end R1 (x^(8 (R1 - E)) from the power tables, or x^(-8 (E - R1)) for the
-// strip holding R1, whose trailing bytes read as 0) in P9b, which XORs it into the file's CRC; P10
-// stores it.  The file is not read back from HBM (P9 re-read it: 482 MB per 256 C2 tiles).
-__global__ void __launch_bounds__(256) k_pngb_emit_crc(PngBatch B) {
-    constexpr int kSteps = kPngbEmitCrcStrip / 1024;
-    __shared__ uint32_t sl[4][256], sh[4][256];
-    const int i = pngb_image(B, B.eblk0, B.eblk_per, blockIdx.x);
-    const PngImg& I = B.img[i];
-    const PngMeta& M = B.meta[i];
-    const int64_t lb = (int64_t)blockIdx.x - (B.uniform ? (int64_t)i * B.eblk_per : I.eblk0);
-    const int64_t F0 = lb * kPngbEmitCrcBytes;          // file offset of the workgroup's bytes
-    if (M.off < 0 || F0 >= M.file_len) return;          // workgroup-uniform
-    for (int k = threadIdx.x; k < 4 * 256; k += 256) {
-        sl[k >> 8][k & 255] = c_braid.last[k >> 8][k & 255];
-        sh[k >> 8][k & 255] = c_hop.hop[k >> 8][k & 255];
-    }
-    __syncthreads();                                    // the CRC tables
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int64_t S0 = F0 + (int64_t)wv * kPngbEmitCrcStrip, E = S0 + kPngbEmitCrcStrip;
-    if (S0 >= M.file_len) return;                       // wave-uniform (P9b skips the strip too)
-    const int64_t R0 = I.pre_len + 4, R1 = I.pre_len + 8 + M.zlen;   // CRC range: 'IDAT' + zlib stream
-    const bool any = !(E <= R0 || S0 >= R1);            // wave-uniform: the strip holds range bytes
-    // range limits relative to this lane's first byte of the strip (clamped: a strip is 16 KiB)
-    const int64_t p0 = S0 + 16 * lane;
-    const int32_t lo = (int32_t)max<int64_t>(min<int64_t>(R0 - p0, 1 << 20), -(1 << 20));
-    const int32_t hi = (int32_t)max<int64_t>(min<int64_t>(R1 - p0, 1 << 20), -(1 << 20));
-    auto T = [&](const uint32_t (*t)[256], uint32_t x) {
-        return t[0][x & 255] ^ t[1][(x >> 8) & 255] ^ t[2][(x >> 16) & 255] ^ t[3][x >> 24];
-    };
-    uint32_t q = 0;
-#pragma unroll 4
-    for (int st = 0; st < kSteps; ++st) {
-        const int64_t k0 = p0 + 1024 * st;
-        uint4 v = make_uint4(0, 0, 0, 0);
-        if (k0 < M.file_len) {
-            v = pngb_file_chunk(B, I, M, k0);
-            *reinterpret_cast<uint4*>(B.out + M.off + k0) = v;
-        }
-        if (any) {
-            uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int32_t r = 1024 * st + 4 * j;    // word offset from p0
-                if (r < lo) w[j] = r + 4 <= lo ? 0u : w[j] & (0xFFFFFFFFu << (8 * (lo - r)));     // before the range
-                if (r + 4 > hi) w[j] = r >= hi ? 0u : w[j] & (0xFFFFFFFFu >> (8 * (r + 4 - hi))); // after it
-                q = (j < 3 || st == kSteps - 1) ? T(sl, q ^ w[j]) : T(sh, q ^ w[j]);
-            }
-        }
-    }
-    uint32_t c = 0;
-    if (any) {
-        c = q ? multmodp(c_hop.lane16[lane], q) : 0u;
-        for (int o = 32; o > 0; o >>= 1) c ^= __shfl_xor(c, o, 64);
-    }
-    // the strip's raw CRC at its end; P9b moves it to the range end (one thread per strip, so the
-    // GF(2) products run on every lane instead of on lane 0 of each wave)
-    if (lane == 0) B.strip_crc[(int64_t)blockIdx.x * 4 + wv] = c;
-}
-
-// P9b: every strip's CRC moved to its file's range end R1 -- x^(8 (R1 - E)), or x^(-8 (E - R1))
-// for the strip holding R1 -- plus the init / final inversions once per file, XORed into the CRC.
-__global__ void __launch_bounds__(256) k_pngb_crc_combine(PngBatch B, int64_t n_strips) {
-    const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const bool live = g < n_strips;
-    const int64_t blk = live ? g >> 2 : (n_strips - 1) >> 2;
-    const int i = pngb_image(B, B.eblk0, B.eblk_per, blk);
-    const PngImg& I = B.img[i];
-    const PngMeta& M = B.meta[i];
-    const int64_t lb = blk - (B.uniform ? (int64_t)i * B.eblk_per : I.eblk0);
-    const int64_t S0 = lb * kPngbEmitCrcBytes + (g & 3) * (int64_t)kPngbEmitCrcStrip, E = S0 + kPngbEmitCrcStrip;
-    const int64_t R0 = I.pre_len + 4, R1 = I.pre_len + 8 + M.zlen;
-    // strips the emit skipped contribute 0 (no early return: the wave reduces below)
-    const bool used = live && !(M.off < 0 || S0 >= M.file_len || E <= R0 || S0 >= R1);
-    uint32_t c = used ? B.strip_crc[g] : 0u;
-    if (c) {
-        if (E <= R1) {                                  // x^(8 d), d = R1 - E = 256 jj + r
-            const uint64_t d = (uint64_t)(R1 - E), jj = d >> 8, r = d & 255;
-            if (r) c = multmodp(B.crc_pow[kCrcPowR + r], c);
-            if (jj & (kCrcPowLo - 1)) c = multmodp(B.crc_pow[jj & (kCrcPowLo - 1)], c);
-            if (jj >= kCrcPowLo) c = multmodp(B.crc_pow[kCrcPowLo + (jj / kCrcPowLo)], c);
-        } else {                                        // the strip holding R1: x^(-8 t), t < the strip
-            const uint64_t t = (uint64_t)(E - R1), a = t >> 8, r = t & 255;
-            if (r) c = multmodp(B.crc_pow[kCrcInvR + r], c);
-            if (a) c = multmodp(B.crc_pow[kCrcInvA + a], c);
-        }
-    }
-    if (used && E >= R1) {                              // the init / final inversions: x^(8 n) from the tables
-        const uint64_t n = (uint64_t)(R1 - R0), jj = n >> 8, r = n & 255;   // (x2nmodp's 21 dependent
-        uint32_t x = B.crc_pow[kCrcPowR + r];                                // constant loads cost 40 us)
-        if (jj & (kCrcPowLo - 1)) x = multmodp(B.crc_pow[jj & (kCrcPowLo - 1)], x);
-        if (jj >= kCrcPowLo) x = multmodp(B.crc_pow[kCrcPowLo + (jj / kCrcPowLo)], x);
-        c ^= ~multmodp(x, 0xFFFFFFFFu);
-    }
-    // one atomic per wave when its 64 strips are one file's (all but the waves at file seams):
-    // 256 files' CRC words otherwise take every strip's atomic in turn
-    const int i0 = __shfl(i, 0, 64);
-    if (__ballot(i != i0) == 0) {
-        for (int o = 32; o > 0; o >>= 1) c ^= __shfl_xor(c, o, 64);
-        if ((threadIdx.x & 63) == 0 && c) atomicXor(&B.meta[i].crc, c);
-    } else if (c) {
-        atomicXor(&B.meta[i].crc, c);
-    }
-}
-static_assert(kPngbEmitCrcStrip / 256 <= 64, "P8+P9: the inverse-power table covers a strip");
-
 // P10: the CRC bytes after the zlib stream.
 __global__ void __launch_bounds__(256) k_pngb_finish(PngBatch B) {
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -3507,16 +3078,16 @@ static omr_status ensure_crc_pow(Ctx* ctx) {
 struct PngBatchPlan {
     std::vector<PngImg> I;
     std::vector<int32_t> firsts;
-    int64_t rows = 0, rblk = 0, pblk = 0, grp = 0, eblk = 0, cblk = 0, segs = 0, toks = 0, flt = 0, words = 0;
+    int64_t rows = 0, rblk = 0, pblk = 0, grp = 0, cblk = 0, segs = 0, flt = 0;
     size_t rows_lds = 16, parse_lds = 16;
     bool uniform = true;
-    size_t o_img, o_first, o_flt, o_bh, o_poff, o_blk, o_trace, o_hist, o_tab, o_meta, o_rows, o_words, o_scrc;
+    size_t o_img, o_first, o_flt, o_bh, o_poff, o_blk, o_trace, o_hist, o_tab, o_meta, o_rows;
     size_t scratch = 0;
 };
 
 static omr_status plan_png_batch(Ctx* ctx, const PngImgHost* im, int n, PngBatchPlan& L) {
     L.I.assign(n, PngImg{});
-    L.firsts.assign(5 * (size_t)n, 0);
+    L.firsts.assign(4 * (size_t)n, 0);
     for (int i = 0; i < n; ++i) {
         const PngImgHost& h = im[i];
         const PngPlan P = png_plan(h.kind, h.W, h.H);
@@ -3539,45 +3110,35 @@ static omr_status plan_png_batch(Ctx* ctx, const PngImgHost* im, int n, PngBatch
         d.back = (int32_t)align_up((size_t)std::min<int64_t>(std::max<int64_t>(P.rowlen, 2 * d.bpp), kMaxBack), 16);
         d.pre_len = png_prefix(h.kind, h.W, h.H, h.rgba, d.pre);
         const int64_t npb = (d.nseg + kParseLanes - 1) / kParseLanes, ng = (d.nseg + kPngbGroup - 1) / kPngbGroup;
-        const int64_t max_file = d.pre_len + 8 + P.zlen + 4 + 12;
-        const int64_t eb = png_direct() || png_crc_separate() ? kPngbEmitBytes : kPngbEmitCrcBytes;
-        const int64_t ne = (max_file + eb - 1) / eb;
         const int64_t nc = (4 + P.zlen + kPngbCrcBytes - 1) / kPngbCrcBytes;
         if (L.rows + h.H > INT32_MAX || L.pblk + npb > INT32_MAX || L.grp + ng > INT32_MAX ||
-            L.eblk + ne > INT32_MAX || L.cblk + nc > INT32_MAX)
+            L.cblk + nc > INT32_MAX)
             return fail(ctx, OMR_INVALID_ARGUMENT, "PNG batch too large");
         d.row0 = (int32_t)L.rows;
         d.rblk0 = (int32_t)L.rblk;
         d.pblk0 = (int32_t)L.pblk;
         d.grp0 = (int32_t)L.grp;
-        d.eblk0 = L.eblk;
         d.cblk0 = L.cblk;
         d.seg0 = L.segs;
-        d.tok0 = L.toks;
         d.flt = L.flt;
-        d.words = L.words;
         L.firsts[i] = d.rblk0;
         L.firsts[n + i] = d.pblk0;
         L.firsts[2 * (size_t)n + i] = d.grp0;
-        L.firsts[3 * (size_t)n + i] = (int32_t)d.eblk0;
-        L.firsts[4 * (size_t)n + i] = (int32_t)d.cblk0;
+        L.firsts[3 * (size_t)n + i] = (int32_t)d.cblk0;
         L.rows += h.H;
         L.rblk += (h.H + kPngRowsPerWg - 1) / kPngRowsPerWg;
         L.pblk += npb;
         L.grp += ng;
-        L.eblk += ne;
         L.cblk += nc;
         L.segs += d.nseg;
-        L.toks += tok_slots(d.nseg);
         L.flt += (int64_t)align_up((size_t)P.raw, 16);
-        L.words += (int64_t)align_up((size_t)(P.raw / 2 + 128), 4);     // <= 16 bits per byte + header
         L.rows_lds = std::max(L.rows_lds, align_up((size_t)png_filter_lds(P.rowlen - 1) + 16, 16));
         if (i && (h.kind != im[0].kind || h.W != im[0].W || h.H != im[0].H)) L.uniform = false;
     }
     size_t o = 0;
     auto take = [&](size_t b) { const size_t r = o; o = align_up(o + b, 256); return r; };
     L.o_img = take(sizeof(PngImg) * n);
-    L.o_first = take(sizeof(int32_t) * 5 * n);
+    L.o_first = take(sizeof(int32_t) * 4 * n);
     L.o_flt = take((size_t)L.flt + 64);              // P2 reads up to 48 bytes past an image's stream
     L.o_bh = take((size_t)L.pblk * 316 * 2);
     L.o_poff = take((size_t)L.pblk * 4 + (size_t)n * 4);
@@ -3587,8 +3148,6 @@ static omr_status plan_png_batch(Ctx* ctx, const PngImgHost* im, int n, PngBatch
     L.o_tab = take(sizeof(DflTables) * n);
     L.o_meta = take(sizeof(PngMeta) * n);
     L.o_rows = take((size_t)L.rows * 16);
-    L.o_words = take((size_t)L.words * 4 + 64);
-    L.o_scrc = take((size_t)L.eblk * 16);
     L.scratch = o;
     return OMR_OK;
 }
@@ -3624,13 +3183,13 @@ static omr_status launch_png_batch(Ctx* ctx, PngBatchPlan& L, const PngImgHost* 
     }
     std::vector<PngImg>& I = L.I;
     std::vector<int32_t>& firsts = L.firsts;
-    const int64_t pblk = L.pblk, grp = L.grp, eblk = L.eblk, cblk = L.cblk;
+    const int64_t pblk = L.pblk, grp = L.grp, cblk = L.cblk;
     const size_t rows_lds = L.rows_lds, parse_lds = L.parse_lds;
     const bool uniform = L.uniform;
     auto at = [&](size_t rel) { return ws_off + rel; };
     const size_t o_img = at(L.o_img), o_first = at(L.o_first), o_flt = at(L.o_flt),
                  o_blk = at(L.o_blk), o_hist = at(L.o_hist), o_tab = at(L.o_tab), o_meta = at(L.o_meta),
-                 o_rows = at(L.o_rows), o_words = at(L.o_words), o_scrc = at(L.o_scrc);
+                 o_rows = at(L.o_rows);
     uint8_t* ws = static_cast<uint8_t*>(ctx->ws);
     PngBatch Bt{};
     Bt.img = reinterpret_cast<const PngImg*>(ws + o_img);
@@ -3639,15 +3198,13 @@ static omr_status launch_png_batch(Ctx* ctx, PngBatchPlan& L, const PngImgHost* 
     Bt.rblk_per = (im[0].H + kPngRowsPerWg - 1) / kPngRowsPerWg;
     Bt.pblk_per = n > 1 ? I[1].pblk0 : (int32_t)pblk;
     Bt.grp_per = n > 1 ? I[1].grp0 : (int32_t)grp;
-    Bt.eblk_per = n > 1 ? (int32_t)I[1].eblk0 : (int32_t)eblk;
     Bt.cblk_per = n > 1 ? (int32_t)I[1].cblk0 : (int32_t)cblk;
     Bt.total_grp = (int32_t)grp;
     const int32_t* fd = reinterpret_cast<const int32_t*>(ws + o_first);
     Bt.rblk0 = fd;
     Bt.pblk0 = fd + n;
     Bt.grp0 = fd + 2 * (size_t)n;
-    Bt.eblk0 = fd + 3 * (size_t)n;
-    Bt.cblk0 = fd + 4 * (size_t)n;
+    Bt.cblk0 = fd + 3 * (size_t)n;
     Bt.flt = ws + o_flt;
     Bt.bh = reinterpret_cast<uint16_t*>(ws + at(L.o_bh));
     Bt.poff = reinterpret_cast<uint32_t*>(ws + at(L.o_poff));
@@ -3663,17 +3220,14 @@ static omr_status launch_png_batch(Ctx* ctx, PngBatchPlan& L, const PngImgHost* 
     Bt.tab = reinterpret_cast<DflTables*>(ws + o_tab);
     Bt.meta = reinterpret_cast<PngMeta*>(ws + o_meta);
     Bt.row_sums = reinterpret_cast<unsigned long long*>(ws + o_rows);
-    Bt.words = reinterpret_cast<uint32_t*>(ws + o_words);
     Bt.out = d_out;
     Bt.out_cap = out_cap;
     Bt.d_offsets = d_offsets;
     Bt.d_lengths = d_lengths;
     Bt.d_status = d_status;
     Bt.crc_pow = ctx->d_crc_pow;
-    Bt.strip_crc = reinterpret_cast<uint32_t*>(ws + o_scrc);
-    Bt.direct = png_direct() ? 1 : 0;
     st = stage_h2d2(ctx, ws + o_img, I.data(), sizeof(PngImg) * n, ws + o_first, firsts.data(),
-                    sizeof(int32_t) * 5 * n);
+                    sizeof(int32_t) * 4 * n);
     if (st) return st;
     OMR_HIP(ctx, hipMemsetAsync(ws + o_hist, 0, (size_t)n * 316 * 4, ctx->stream));
     if (rows_lds > (size_t)60 * 1024)
@@ -3737,51 +3291,27 @@ static omr_status launch_png_batch(Ctx* ctx, PngBatchPlan& L, const PngImgHost* 
         hipLaunchKernelGGL(k_pngb_tables, dim3((unsigned)n), dim3(kHuffThreads), 0, s, Bt);
         hipLaunchKernelGGL(k_pngb_block_offsets, dim3((unsigned)n), dim3(kBoffThreads), 0, s, Bt);
     }
-    if (Bt.direct) {
-        // P5b, P6 (the files' lengths and offsets), P4 into the files, P5, P8 around the
-        // streams, P9, P10 (timer kinds: 24 meta + offsets, 23 encode, 25 fixup + emit, 26 CRC)
-        {
-            KernelTimer t(ctx, 24);
-            hipLaunchKernelGGL(k_pngb_meta, dim3((unsigned)n), dim3(256), 0, s, Bt);
-            hipLaunchKernelGGL(k_pngb_offsets, dim3(1), dim3(1024), 0, s, Bt);
-        }
-        {
-            KernelTimer t(ctx, 23);
-            hipLaunchKernelGGL(k_pngb_encode, dim3((unsigned)grp), dim3(kPngbGroup), 0, s, Bt);
-        }
-        {
-            KernelTimer t(ctx, 25);
-            hipLaunchKernelGGL(k_pngb_fixup, dim3((unsigned)((grp + 255) / 256)), dim3(256), 0, s, Bt);
-            hipLaunchKernelGGL(k_pngb_emit_direct, dim3((unsigned)(n * kEmitDirectWgs)), dim3(256), 0, s, Bt);
-        }
-        {
-            KernelTimer t(ctx, 26);
-            hipLaunchKernelGGL(k_pngb_crc, dim3((unsigned)cblk), dim3(256), 0, s, Bt);
-            hipLaunchKernelGGL(k_pngb_finish, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, Bt);
-        }
-        OMR_HIP(ctx, hipGetLastError());
-        return OMR_OK;
+    // P5b, P6 (the files' lengths and offsets), P4 into the files, P5, P8 around the streams, P9,
+    // P10 (timer kinds: 24 meta + offsets, 23 encode, 25 fixup + emit, 26 CRC)
+    {
+        KernelTimer t(ctx, 24);
+        hipLaunchKernelGGL(k_pngb_meta, dim3((unsigned)n), dim3(256), 0, s, Bt);
+        hipLaunchKernelGGL(k_pngb_offsets, dim3(1), dim3(1024), 0, s, Bt);
     }
     {
         KernelTimer t(ctx, 23);
         hipLaunchKernelGGL(k_pngb_encode, dim3((unsigned)grp), dim3(kPngbGroup), 0, s, Bt);
     }
     {
-        KernelTimer t(ctx, 24);
+        KernelTimer t(ctx, 25);
         hipLaunchKernelGGL(k_pngb_fixup, dim3((unsigned)((grp + 255) / 256)), dim3(256), 0, s, Bt);
-        hipLaunchKernelGGL(k_pngb_meta, dim3((unsigned)n), dim3(256), 0, s, Bt);
-        hipLaunchKernelGGL(k_pngb_offsets, dim3(1), dim3(1024), 0, s, Bt);
+        hipLaunchKernelGGL(k_pngb_emit_direct, dim3((unsigned)(n * kEmitDirectWgs)), dim3(256), 0, s, Bt);
     }
     {
-        KernelTimer t(ctx, 25);
-        if (png_crc_separate()) hipLaunchKernelGGL(k_pngb_emit, dim3((unsigned)eblk), dim3(256), 0, s, Bt);
-        else hipLaunchKernelGGL(k_pngb_emit_crc, dim3((unsigned)eblk), dim3(256), 0, s, Bt);   // P8 + P9
+        KernelTimer t(ctx, 26);
+        hipLaunchKernelGGL(k_pngb_crc, dim3((unsigned)cblk), dim3(256), 0, s, Bt);
+        hipLaunchKernelGGL(k_pngb_finish, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, Bt);
     }
-    KernelTimer t_crc(ctx, 26);
-    if (png_crc_separate()) hipLaunchKernelGGL(k_pngb_crc, dim3((unsigned)cblk), dim3(256), 0, s, Bt);
-    else hipLaunchKernelGGL(k_pngb_crc_combine, dim3((unsigned)((eblk * 4 + 255) / 256)), dim3(256), 0, s, Bt,
-                            (int64_t)(eblk * 4));
-    hipLaunchKernelGGL(k_pngb_finish, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, Bt);
     OMR_HIP(ctx, hipGetLastError());
     return OMR_OK;
 }
@@ -3870,6 +3400,55 @@ omr_status encode_png_gray_batch(Ctx* ctx, const omr_raw_tile* tiles, int32_t n,
     st = ensure_workspace(ctx, L.scratch);
     if (st) return st;
     return launch_png_batch(ctx, L, im.data(), n, 0, d_out, out_cap, d_offsets, d_lengths, d_status);
+}
+
+// One shape mask as both entry points (the single call and every job of the batch) prepare it,
+// before any device work.
+struct MaskPrep {
+    int kind;                      // kIdx1 (bitsPerPixel 1, width % 8 == 0) or kIdx8 (:174-178)
+    const uint8_t* bits;           // the mask to render: the caller's, or `flipped`
+    int flip_h, flip_v;            // the flips left for the device
+    bool fits_batch;               // the batched pipeline can take it
+    std::vector<uint8_t> flipped;  // the packed-buffer flip's result
+};
+
+// Every exception the reference raises inside renderShapeMask fails its future, which
+// ShapeMaskVerticle.java:119-128 answers with 404 ("Cannot render Mask"): OMR_NOT_FOUND with the
+// reason in `why`, else OMR_OK and P filled.
+static omr_status mask_prepare(const Ctx* ctx, const uint8_t* bits, size_t n_bytes, int32_t width, int32_t height,
+                               int flip_h, int flip_v, MaskPrep& P, std::string& why) {
+    if (width <= 0 || height <= 0) { why = "Attempted to flip image with 0 size"; return OMR_NOT_FOUND; }
+    const int64_t npx = (int64_t)width * height;
+    if (npx > INT32_MAX) { why = "width*height overflows a Java int"; return OMR_NOT_FOUND; }
+    if (!bits) { why = "NullPointerException: null mask bytes"; return OMR_NOT_FOUND; }
+    if ((int64_t)n_bytes * 8 < npx) { why = "mask shorter than width*height bits"; return OMR_NOT_FOUND; }
+    P.bits = bits;
+    P.flip_h = flip_h ? 1 : 0;
+    P.flip_v = flip_v ? 1 : 0;
+    // width % 8 == 0: the reference skips the unpack (:175-178) and flips the still-packed buffer as
+    // one byte per pixel (:179-181, :145-150) unless OMR_SEM_MASK_PIXEL_FLIP asks for the pixel flip
+    if (width % 8 == 0 && (flip_h || flip_v) && !(ctx->sem & OMR_SEM_MASK_PIXEL_FLIP)) {
+        if ((int64_t)n_bytes < npx) {
+            why = "ArrayIndexOutOfBoundsException: flip of the packed mask reads " + std::to_string(npx) +
+                  " bytes of " + std::to_string(n_bytes);
+            return OMR_NOT_FOUND;
+        }
+        P.flipped.assign(n_bytes, 0);     // new byte[src.length]; bytes past width*height stay 0
+        for (int64_t y = 0; y < height; ++y) {
+            const int64_t drow = (flip_v ? height - 1 - y : y) * width;
+            for (int64_t x = 0; x < width; ++x) P.flipped[drow + (flip_h ? width - 1 - x : x)] = bits[y * width + x];
+        }
+        P.bits = P.flipped.data();        // rendered as packed bits, no further flip
+        P.flip_h = P.flip_v = 0;
+    }
+    P.kind = width % 8 == 0 ? kIdx1 : kIdx8;
+    // the batch's 32-bit bit offsets hold a stream of up to 2^27 bytes (16 bits per byte worst
+    // case), its filter one row in LDS; beyond either the one-image pipeline encodes the mask
+    // (and answers the too-wide row)
+    const PngPlan plan = png_plan(P.kind, width, height);
+    P.fits_batch = plan.raw <= ((int64_t)1 << 27) &&
+                   align_up((size_t)png_filter_lds(plan.rowlen - 1) + 16, 16) <= (size_t)kPngFilterLdsMax + 64;
+    return OMR_OK;
 }
 
 }  // namespace omr
@@ -3992,49 +3571,27 @@ omr_status omr_render_shape_mask_png_batch(omr_ctx* ctx, const omr_mask_job* job
     // the batch's 32-bit bit offsets go through the single-mask path after the batch.
     std::vector<PngImgHost> im;
     std::vector<int> idx, big;
-    std::vector<std::vector<uint8_t>> flipped(n);
+    std::vector<MaskPrep> prep(n);                     // (keeps each packed flip's buffer until the upload)
     std::vector<size_t> boff;
     size_t bits_total = 0;
+    std::string why;
     for (int i = 0; i < n; ++i) {
         const omr_mask_job& j = jobs[i];
         offsets[i] = 0;
         lengths[i] = 0;
-        status[i] = OMR_OK;
-        const int64_t npx = (int64_t)j.width * j.height;
-        if (j.width <= 0 || j.height <= 0 || npx > INT32_MAX || !j.bits || (int64_t)j.n_bytes * 8 < npx) {
-            status[i] = OMR_NOT_FOUND;
-            continue;
-        }
-        const uint8_t* bits = j.bits;
-        int fh = j.flip_h ? 1 : 0, fv = j.flip_v ? 1 : 0;
-        if (j.width % 8 == 0 && (fh || fv) && !(ctx->sem & OMR_SEM_MASK_PIXEL_FLIP)) {
-            if ((int64_t)j.n_bytes < npx) {        // ArrayIndexOutOfBoundsException in the packed flip
-                status[i] = OMR_NOT_FOUND;
-                continue;
-            }
-            std::vector<uint8_t>& f = flipped[i];
-            f.assign(j.n_bytes, 0);
-            for (int64_t y = 0; y < j.height; ++y) {
-                const int64_t drow = (fv ? j.height - 1 - y : y) * j.width;
-                for (int64_t x = 0; x < j.width; ++x) f[drow + (fh ? j.width - 1 - x : x)] = j.bits[y * j.width + x];
-            }
-            bits = f.data();
-            fh = fv = 0;
-        }
-        const int kind = j.width % 8 == 0 ? kIdx1 : kIdx8;
-        const PngPlan P = png_plan(kind, j.width, j.height);
-        // > 2^31 bits worst case, or a row too wide for the batch filter's LDS: the single path
-        // (which answers the too-wide row for this mask alone)
-        if (P.raw > ((int64_t)1 << 27) ||
-            align_up((size_t)png_filter_lds(P.rowlen - 1) + 16, 16) > (size_t)kPngFilterLdsMax + 64) {
+        status[i] = mask_prepare(ctx, j.bits, j.n_bytes, j.width, j.height, j.flip_h, j.flip_v, prep[i], why);
+        if (status[i]) continue;
+        const MaskPrep& P = prep[i];
+        if (!P.fits_batch) {
             big.push_back(i);
             continue;
         }
-        PngImgHost h{nullptr, bits, kind, j.width, j.height, fh, fv, {j.rgba[0], j.rgba[1], j.rgba[2], j.rgba[3]}};
+        PngImgHost h{nullptr, P.bits, P.kind, j.width, j.height, P.flip_h, P.flip_v,
+                     {j.rgba[0], j.rgba[1], j.rgba[2], j.rgba[3]}};
         im.push_back(h);
         idx.push_back(i);
         boff.push_back(bits_total);
-        bits_total += align_up((size_t)((npx + 7) / 8), 16);
+        bits_total += align_up((size_t)(((int64_t)j.width * j.height + 7) / 8), 16);
     }
     const int m = (int)im.size();
     size_t used = 0;
@@ -4102,53 +3659,30 @@ omr_status omr_render_shape_mask_png(omr_ctx* ctx, const uint8_t* bits, size_t n
                                      uint8_t* out, size_t cap, size_t* out_len) {
     if (!ctx) return OMR_INVALID_ARGUMENT;
     if (!rgba) return fail(ctx, OMR_INVALID_ARGUMENT, "null fill colour");
-    // Every exception the reference raises inside renderShapeMask fails its future, which
-    // ShapeMaskVerticle.java:119-128 answers with 404 ("Cannot render Mask").
-    if (width <= 0 || height <= 0) return fail(ctx, OMR_NOT_FOUND, "Attempted to flip image with 0 size");
-    const int64_t npx = (int64_t)width * height;
-    if (npx > INT32_MAX) return fail(ctx, OMR_NOT_FOUND, "width*height overflows a Java int");
-    if (!bits) return fail(ctx, OMR_NOT_FOUND, "NullPointerException: null mask bytes");
-    if ((int64_t)n_bytes * 8 < npx) return fail(ctx, OMR_NOT_FOUND, "mask shorter than width*height bits");
-    // width % 8 == 0: the reference skips the unpack (:175-178) and flips the still-packed buffer as
-    // one byte per pixel (:179-181, :145-150) unless OMR_SEM_MASK_PIXEL_FLIP asks for the pixel flip
-    std::vector<uint8_t> packed_flip;
-    if (width % 8 == 0 && (flip_h || flip_v) && !(ctx->sem & OMR_SEM_MASK_PIXEL_FLIP)) {
-        if ((int64_t)n_bytes < npx)
-            return fail(ctx, OMR_NOT_FOUND, "ArrayIndexOutOfBoundsException: flip of the packed mask reads " +
-                                                std::to_string(npx) + " bytes of " + std::to_string(n_bytes));
-        packed_flip.assign(n_bytes, 0);   // new byte[src.length]; bytes past width*height stay 0
-        for (int64_t y = 0; y < height; ++y) {
-            const int64_t drow = (flip_v ? height - 1 - y : y) * width;
-            for (int64_t x = 0; x < width; ++x) packed_flip[drow + (flip_h ? width - 1 - x : x)] = bits[y * width + x];
-        }
-        bits = packed_flip.data();        // rendered as packed bits, no further flip
-        flip_h = flip_v = 0;
-    }
+    MaskPrep P;
+    std::string why;
+    if (mask_prepare(ctx, bits, n_bytes, width, height, flip_h, flip_v, P, why)) return fail(ctx, OMR_NOT_FOUND, why);
     OMR_HIP(ctx, hipSetDevice(ctx->device));
-    const int kind = width % 8 == 0 ? kIdx1 : kIdx8;   // bitsPerPixel 1 or 8 (:174-178)
-    const PngPlan P1 = png_plan(kind, width, height);
-    if (ctx->png_single_batched && P1.raw <= ((int64_t)1 << 27) &&
-        align_up((size_t)png_filter_lds(P1.rowlen - 1) + 16, 16) <= (size_t)kPngFilterLdsMax + 64) {
-        // the batch of one (the mask bits go to the workspace below base; packed flip done above)
+    const int64_t npx = (int64_t)width * height;
+    if (ctx->png_single_batched && P.fits_batch) {
+        // the batch of one (the mask bits go to the workspace below base)
         const size_t nbits = align_up((size_t)((npx + 7) / 8), 256);
-        PngImgHost im{nullptr, nullptr, kind, width, height, flip_h ? 1 : 0, flip_v ? 1 : 0,
-                      {rgba[0], rgba[1], rgba[2], rgba[3]}};
+        PngImgHost im{nullptr, nullptr, P.kind, width, height, P.flip_h, P.flip_v, {rgba[0], rgba[1], rgba[2], rgba[3]}};
         PngBatchPlan L;
         PngSingleLayout S;
         omr_status st = png_single_layout(ctx, im, nbits, L, S);
         if (!st) st = ensure_workspace(ctx, S.total);
         if (st) return st;
         im.bits = static_cast<const uint8_t*>(ctx->ws);
-        OMR_HIP(ctx, hipMemcpyAsync(ctx->ws, bits, (size_t)((npx + 7) / 8), hipMemcpyHostToDevice, ctx->stream));
+        OMR_HIP(ctx, hipMemcpyAsync(ctx->ws, P.bits, (size_t)((npx + 7) / 8), hipMemcpyHostToDevice, ctx->stream));
         return png_single_batched(ctx, im, L, S, out, cap, out_len);
     }
     const size_t nb = align_up(n_bytes, 256);
-    omr_status st = ensure_workspace(ctx, nb + png_scratch(kind, width, height));
+    omr_status st = ensure_workspace(ctx, nb + png_scratch(P.kind, width, height));
     if (st) return st;
     uint8_t* d_bits = static_cast<uint8_t*>(ctx->ws);
-    OMR_HIP(ctx, hipMemcpyAsync(d_bits, bits, n_bytes, hipMemcpyHostToDevice, ctx->stream));
-    return encode_png_ws(ctx, kind, nullptr, d_bits, width, height, flip_h ? 1 : 0, flip_v ? 1 : 0, rgba, nb, out,
-                         cap, out_len);
+    OMR_HIP(ctx, hipMemcpyAsync(d_bits, P.bits, n_bytes, hipMemcpyHostToDevice, ctx->stream));
+    return encode_png_ws(ctx, P.kind, nullptr, d_bits, width, height, P.flip_h, P.flip_v, rgba, nb, out, cap, out_len);
 }
 
 }  // extern "C"

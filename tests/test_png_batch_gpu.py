@@ -9,7 +9,10 @@ round-1..3 PNG tests already cover; noise takes stored blocks (of the filtered r
 Masks are checked against the CPU restatement's unpack/flip (oracle mask_indices), including the
 reference's 404 cases and its packed-buffer flip (ShapeMaskRequestHandler.java:165-207).
 """
+import hashlib
 import io
+import json
+import os
 import struct
 import zlib
 
@@ -355,42 +358,33 @@ def test_png_batch_sparse_noisy_segments(ctx):
         assert png == ctx.encode_png(argb[i], w, h)
 
 
-_MODES_SCRIPT = r"""
-import hashlib, os, sys
-import numpy as np
-sys.path.insert(0, os.path.join(os.environ["OMR_REPO"], "omero-ms-image-region_amd"))
-sys.path.insert(0, os.path.join(os.environ["OMR_REPO"], "tests"))
-import omr, torch
-from test_png_batch_gpu import tiles, encode_batch
-h = hashlib.sha256()
-with omr.Context(0) as ctx:
-    for kind, n, w, h_, seed in (("image", 5, 256, 200, 1), ("noise", 3, 130, 70, 2), ("flat", 2, 64, 8, 3),
-                                 ("image", 3, 1, 1, 4), ("image", 2, 1023, 33, 5)):
+GOLDEN_FILES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "png_batch_files.json")
+
+
+def pinned_files_digest(ctx, cases):
+    """sha256 over the files of `cases` (the case list of tests/golden/png_batch_files.json), in
+    order: per batched case its files, then one single-request file; then the shape masks."""
+    h = hashlib.sha256()
+    for c in cases["batched"]:
+        kind, n, w, h_, seed = c["kind"], c["n"], c["w"], c["h"], c["seed"]
         for st, off, png in encode_batch(ctx, tiles(kind, n, w, h_, seed)):
             assert st == 0
             h.update(png)
-        h.update(ctx.encode_png(tiles(kind, 1, w, h_, seed + 7)[0], w, h_))
-    rng = np.random.default_rng(6)
-    for w, h_ in ((333, 77), (64, 48)):
-        h.update(ctx.render_shape_mask_png(np.packbits(rng.integers(0, 2, w * h_)).tobytes(), w, h_, (9, 8, 7, 6)))
-print(h.hexdigest())
-"""
+        h.update(ctx.encode_png(tiles(kind, 1, w, h_, seed + cases["single_seed_offset"])[0], w, h_))
+    m = cases["masks"]
+    rng = np.random.default_rng(m["seed"])
+    for w, h_ in m["sizes"]:
+        h.update(ctx.render_shape_mask_png(np.packbits(rng.integers(0, 2, w * h_)).tobytes(), w, h_, tuple(m["rgba"])))
+    return h.hexdigest()
 
 
-def test_png_direct_mode_matches_words_buffer_forms():
-    """Direct mode (the default since round 6: P4 codes into the files in place, P8 stores only the
-    bytes around the streams) writes the same bytes as the words-buffer forms it replaced -- P8
-    with the CRC fused (OMR_PNG_DIRECT=0) and P8 + a separate P9 (OMR_PNG_CRC_P9=1).  The modes
-    are read once per process, so each runs in a child process, one after another."""
-    import os
-    import subprocess
-    import sys
-    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    digests = {}
-    for name, env in (("direct", {}), ("fused", {"OMR_PNG_DIRECT": "0"}),
-                      ("separate", {"OMR_PNG_DIRECT": "0", "OMR_PNG_CRC_P9": "1"})):
-        e = dict(os.environ, OMR_REPO=repo, **env)
-        r = subprocess.run([sys.executable, "-c", _MODES_SCRIPT], env=e, capture_output=True, text=True, timeout=110)
-        assert r.returncode == 0, f"{name}: {r.stderr[-2000:]}"
-        digests[name] = r.stdout.strip().splitlines()[-1]
-    assert digests["direct"] == digests["fused"] == digests["separate"], digests
+def test_png_batch_files_match_pinned_digest(ctx):
+    """The batched pipeline writes the bytes recorded in tests/golden/png_batch_files.json.  The
+    digest was taken from the last build that still had the words-buffer forms (P8 with the CRC
+    fused, and P8 + a separate P9), after the three forms were shown to write the same bytes over
+    these cases; it is how that guarantee survives their removal.  The golden pins the coded bytes,
+    not only the decoded pixels: a later change that alters them on purpose (another parse, another
+    code) refreshes the file with tools/png_golden.py and says so."""
+    with open(GOLDEN_FILES) as f:
+        golden = json.load(f)
+    assert pinned_files_digest(ctx, golden["cases"]) == golden["sha256"]
