@@ -610,7 +610,19 @@ omr_status omr_flip_mask_device(omr_ctx* ctx, const uint8_t* d_src, uint8_t* d_d
  * (ProjectionService.java:46-120): one channel's stack [size_z][size_y][size_x] -> one plane
  * of the same pixel type.  Max over z in [start,end] inclusive; mean/sum over [start,end)
  * (ProjectionService.java:184 vs :271).  Host memory; synchronous.
+ *
+ * Stepping: the planes read are z = start + i * stepping for i < omr_projection_plane_count(),
+ * counted in 64 bits, so a stepping up to INT32_MAX is valid while start + stepping <= INT32_MAX
+ * (start = 0, stepping = INT32_MAX projects plane 0).  Every projection call answers
+ * OMR_INVALID_ARGUMENT when the loop runs at least once (start <= end for max, start < end for
+ * mean and sum) and (int64)start + stepping > INT32_MAX -- in general, when z after the last
+ * plane read would pass INT32_MAX: there the reference's int z wraps negative, its loop goes
+ * on and the plane read throws.
  */
+/* The number of planes a projection reads (0 for an empty range), or the rejection above.  Also
+ * OMR_INVALID_ARGUMENT for a negative bound, stepping <= 0 or an unknown algorithm.  No context. */
+omr_status omr_projection_plane_count(int32_t algorithm, int32_t start, int32_t end, int32_t stepping,
+                                      int64_t* count);
 omr_status omr_project_stack(omr_ctx* ctx, const void* stack, int32_t pixel_type,
                              int32_t big_endian_in, int32_t size_x, int32_t size_y, int32_t size_z,
                              int32_t algorithm, int32_t start, int32_t end, int32_t stepping,

@@ -18,6 +18,7 @@ struct K3Args {
     uint8_t* outs[kMaxStacks];
     int32_t n_stacks;
     int32_t start, end, stepping;
+    uint32_t n_iter;      // planes read (omr_projection_plane_count): z = start + i * stepping, i < n_iter
     int64_t plane;        // pixels per plane
     uint32_t chunks;      // chunks per plane
     // exact unsigned division by the mean's plane count (Granlund-Montgomery, any 32-bit
@@ -125,6 +126,10 @@ __global__ void __launch_bounds__(kBlock) k_project(K3Args A) {
     const uint8_t* __restrict__ stack = A.stacks[s];
     uint8_t* __restrict__ out = A.outs[s];
     const int64_t plane_bytes = A.plane * (int64_t)sizeof(T);
+    // the reference's loops (:184, :271) by count: no z is stepped past end (a stepping near
+    // INT32_MAX would wrap it), and with one plane to read there is no stride to form
+    const uint32_t n_iter = A.n_iter;
+    const int64_t step = n_iter > 1 ? plane_bytes * A.stepping : 0;
     for (uint32_t c = blockIdx.x * kBlock + threadIdx.x; c < A.chunks; c += gridDim.x * kBlock) {
         const int64_t px0 = (int64_t)c * V;
         const int nv = (int)min<int64_t>(V, A.plane - px0);
@@ -133,11 +138,9 @@ __global__ void __launch_bounds__(kBlock) k_project(K3Args A) {
 #pragma unroll
             for (int j = 0; j < V; ++j) best[j] = (T)0;
             const uint8_t* p = stack + (int64_t)A.start * plane_bytes + px0 * (int64_t)sizeof(T);
-            const int64_t step = plane_bytes * A.stepping;
             if (nv == V) {
-                int z = A.start;
 #pragma unroll 4
-                for (; z <= A.end; z += A.stepping, p += step) {
+                for (uint32_t i = 0; i < n_iter; ++i, p += step) {
 #pragma unroll
                     for (int j = 0; j < V; ++j) {
                         const T v = load_px<T, BEI>(p + j * sizeof(T));
@@ -145,7 +148,7 @@ __global__ void __launch_bounds__(kBlock) k_project(K3Args A) {
                     }
                 }
             } else {
-                for (int z = A.start; z <= A.end; z += A.stepping, p += step)
+                for (uint32_t i = 0; i < n_iter; ++i, p += step)
                     for (int j = 0; j < nv; ++j) {
                         const T v = load_px<T, BEI>(p + j * sizeof(T));
                         if (v > best[j]) best[j] = v;
@@ -157,26 +160,21 @@ __global__ void __launch_bounds__(kBlock) k_project(K3Args A) {
             AT sum[V];
 #pragma unroll
             for (int j = 0; j < V; ++j) sum[j] = 0;
-            int count = 0;
             const uint8_t* p = stack + (int64_t)A.start * plane_bytes + px0 * (int64_t)sizeof(T);
-            const int64_t step = plane_bytes * A.stepping;
             if (nv == V) {
 #pragma unroll 4
-                for (int z = A.start; z < A.end; z += A.stepping, p += step) {
+                for (uint32_t i = 0; i < n_iter; ++i, p += step) {
 #pragma unroll
                     for (int j = 0; j < V; ++j) sum[j] += (AT)load_px<T, BEI>(p + j * sizeof(T));
-                    ++count;
                 }
             } else {
-                for (int z = A.start; z < A.end; z += A.stepping, p += step) {
+                for (uint32_t i = 0; i < n_iter; ++i, p += step)
                     for (int j = 0; j < nv; ++j) sum[j] += (AT)load_px<T, BEI>(p + j * sizeof(T));
-                    ++count;
-                }
             }
             const double pmax = type_max<T>();
             for (int j = 0; j < nv; ++j) {
                 double v = (double)sum[j];
-                if (ALG == OMR_PROJECTION_MEAN) v = v / (double)count;
+                if (ALG == OMR_PROJECTION_MEAN) v = v / (double)n_iter;   // projectedPlaneCount (:273)
                 if (v > pmax) v = pmax;
                 store_px<T, BEO>(out + (px0 + j) * sizeof(T), narrow<T>(v));
             }
@@ -491,9 +489,9 @@ omr_status enqueue_project_render(Ctx* ctx, const void* const* stacks, const Fus
     if ((plane * bpp) % 16 || reinterpret_cast<uintptr_t>(d_out) % 4) return OMR_OK;
     for (int a = 0; a < R.n_active; ++a)
         if (!stacks[a] || reinterpret_cast<uintptr_t>(stacks[a]) % 16) return OMR_OK;
-    uint32_t n_iter;
-    if (algorithm == OMR_PROJECTION_MAX) n_iter = end >= start ? (uint32_t)((end - start) / stepping + 1) : 0u;
-    else n_iter = end > start ? (uint32_t)((end - start + stepping - 1) / stepping) : 0u;
+    int64_t n_iter = 0;
+    if (omr_projection_plane_count(algorithm, start, end, stepping, &n_iter))
+        return fail(ctx, OMR_INVALID_ARGUMENT, "stepping: z wraps past INT32_MAX");
     if (n_iter > 32767 || (algorithm != OMR_PROJECTION_MAX && n_iter == 0)) return OMR_OK;   // |sum| < 2^31
     K3RArgs a;
     std::memset(&a, 0, sizeof(a));
@@ -508,8 +506,8 @@ omr_status enqueue_project_render(Ctx* ctx, const void* const* stacks, const Fus
     a.flip_v = flip_v ? 1 : 0;
     a.mean = algorithm == OMR_PROJECTION_MEAN ? 1 : 0;
     a.chunks = (uint32_t)(plane * bpp / 16);
-    a.n_iter = n_iter;
-    a.ndiv = make_fastdiv(n_iter ? n_iter : 1);
+    a.n_iter = (uint32_t)n_iter;
+    a.ndiv = make_fastdiv(n_iter ? (uint32_t)n_iter : 1u);
     const dim3 g((a.chunks + kK3RChunks - 1) / kK3RChunks);
     const bool mx = algorithm == OMR_PROJECTION_MAX, fast = R.mode == kFusedFast16, be = be_in != 0;
     hipError_t e;
@@ -596,6 +594,12 @@ static omr_status validate_projection(Ctx* ctx, int32_t pixel_type, int32_t size
     if (stepping <= 0) return fail(ctx, OMR_INVALID_ARGUMENT, "stepping: " + std::to_string(stepping) + " <= 0");
     if (algorithm < OMR_PROJECTION_MAX || algorithm > OMR_PROJECTION_SUM)
         return fail(ctx, OMR_INVALID_ARGUMENT, "Unknown algorithm: " + std::to_string(algorithm));
+    // the reference's `z += stepping` (:184, :271) wraps negative past INT32_MAX after a plane it
+    // reads, the loop goes on and getPixelValue throws on the negative index
+    int64_t count = 0;
+    if (omr_projection_plane_count(algorithm, start, end, stepping, &count))
+        return fail(ctx, OMR_INVALID_ARGUMENT, "stepping: " + std::to_string(stepping) + " steps z past " +
+                                                   std::to_string(INT32_MAX));
     return OMR_OK;
 }
 
@@ -617,6 +621,12 @@ omr_status enqueue_projection(Ctx* ctx, const void* const* d_stacks, void* const
     a.stepping = stepping;
     a.plane = (int64_t)size_x * size_y;
     if (a.plane == 0) return OMR_OK;
+    // planes read: max over z in [start, end], mean/sum over z in [start, end) (ProjectionService.java:184, :271)
+    int64_t planes = 0;
+    if (omr_projection_plane_count(algorithm, start, end, stepping, &planes))
+        return fail(ctx, OMR_INVALID_ARGUMENT, "stepping: z wraps past INT32_MAX");
+    const uint32_t n_iter = (uint32_t)planes;      // <= INT32_MAX
+    a.n_iter = n_iter;
     const int bpp = bytes_per_pixel(pixel_type);
     const int v = bpp >= 8 ? 2 : 16 / bpp;
     const int64_t chunks = (a.plane + v - 1) / v;
@@ -635,10 +645,6 @@ omr_status enqueue_projection(Ctx* ctx, const void* const* d_stacks, void* const
         const uint32_t c16 = (uint32_t)(a.plane * bpp / 16);
         K3Args b = a;
         b.chunks = c16;
-        // iterations: max over z in [start, end], mean/sum over z in [start, end) (ProjectionService.java:184, :271)
-        uint32_t n_iter = 0;
-        if (algorithm == OMR_PROJECTION_MAX) n_iter = end >= start ? (uint32_t)((end - start) / stepping + 1) : 0u;
-        else n_iter = end > start ? (uint32_t)((end - start + stepping - 1) / stepping) : 0u;
         set_udiv(b, n_iter ? n_iter : 1u);
         switch (pixel_type) {
         case OMR_PIXELS_INT8: e = launch_project_vt<int8_t>(b, algorithm, bi, bo, n_iter, c16, n, ctx->stream); break;
@@ -717,6 +723,22 @@ omr_status omr_flip_mask_device(omr_ctx* ctx, const uint8_t* d_src, uint8_t* d_d
                                 int32_t size_y, int32_t flip_h, int32_t flip_v) {
     if (!ctx) return OMR_INVALID_ARGUMENT;
     return flip_device<uint8_t>(ctx, d_src, d_dest, size_x, size_y, flip_h, flip_v);
+}
+
+omr_status omr_projection_plane_count(int32_t algorithm, int32_t start, int32_t end, int32_t stepping,
+                                      int64_t* count) {
+    if (!count) return OMR_INVALID_ARGUMENT;
+    *count = 0;
+    if (start < 0 || end < 0 || stepping <= 0) return OMR_INVALID_ARGUMENT;
+    if (algorithm < OMR_PROJECTION_MAX || algorithm > OMR_PROJECTION_SUM) return OMR_INVALID_ARGUMENT;
+    const int64_t last = algorithm == OMR_PROJECTION_MAX ? (int64_t)end : (int64_t)end - 1;   // last z the loop admits
+    if (last < start) return OMR_OK;
+    const int64_t n = (last - start) / stepping + 1;
+    // z after the last plane read, start + n * stepping: past INT32_MAX the reference's int wraps
+    // negative, its loop goes on and the plane read throws (n == 1: start + stepping > INT32_MAX)
+    if (start + n * stepping > INT32_MAX) return OMR_INVALID_ARGUMENT;
+    *count = n;
+    return OMR_OK;
 }
 
 omr_status omr_project_stack_device(omr_ctx* ctx, const void* d_stack, int32_t pixel_type,

@@ -238,6 +238,7 @@ _SIGS = {
     "omr_thumbnail_size": (_i32, [_i32, _i32, _i32, ctypes.POINTER(_i32), ctypes.POINTER(_i32)]),
     "omr_flip_argb_device": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32]),
     "omr_flip_mask_device": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32]),
+    "omr_projection_plane_count": (_i32, [_i32, _i32, _i32, _i32, ctypes.POINTER(_i64)]),
     "omr_project_stack": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
                                  _vp, _i32]),
     "omr_project_stack_device": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,

@@ -41,6 +41,8 @@
  *          channel renders 0xFF000000.
  *   S9 [H] projection exactly as ProjectionService.java:176-291 (max over [start,end] from 0,
  *          mean/sum over [start,end), double sum, clamp to type max, Java narrowing store).
+ *          The loops run by a 64-bit plane count; where the reference's int z would wrap past
+ *          INT32_MAX and its plane read throw, the answer is OMR_INVALID_ARGUMENT.
  *   S10[M] JPEG tables: JPEG.convertToLinearQuality + JPEGQTable.getScaledInstance of the
  *          Annex K luminance and chrominance tables.
  *
@@ -353,6 +355,24 @@ static void set_pixel_value(uint8_t* p, int t, int be, double v) {
     store_raw(p, nb, be, raw);
 }
 
+/* Planes the projection reads: max over z in [start, end], mean and sum over [start, end)
+ * (ProjectionService.java:184, :271), counted in 64 bits.  OMR_INVALID_ARGUMENT where the
+ * reference's `z += stepping` would pass INT32_MAX after a plane it reads: its z wraps negative,
+ * the loop goes on and getPixelValue throws.  (The expression of omr_projection_plane_count.) */
+omr_status oracle_projection_plane_count(int32_t algorithm, int32_t start, int32_t end, int32_t stepping,
+                                         int64_t* count) {
+    if (!count) return OMR_INVALID_ARGUMENT;
+    *count = 0;
+    if (start < 0 || end < 0 || stepping <= 0) return OMR_INVALID_ARGUMENT;
+    if (algorithm < OMR_PROJECTION_MAX || algorithm > OMR_PROJECTION_SUM) return OMR_INVALID_ARGUMENT;
+    const int64_t last = algorithm == OMR_PROJECTION_MAX ? (int64_t)end : (int64_t)end - 1;
+    if (last < start) return OMR_OK;
+    const int64_t n = (last - start) / stepping + 1;
+    if (start + n * stepping > INT32_MAX) return OMR_INVALID_ARGUMENT;
+    *count = n;
+    return OMR_OK;
+}
+
 omr_status oracle_project_stack(const void* stack, int32_t pixel_type, int32_t big_endian_in,
                                 int32_t size_x, int32_t size_y, int32_t size_z, int32_t algorithm,
                                 int32_t start, int32_t end, int32_t stepping, void* out,
@@ -364,22 +384,25 @@ omr_status oracle_project_stack(const void* stack, int32_t pixel_type, int32_t b
     if (start >= size_z || end >= size_z) return OMR_INVALID_ARGUMENT;
     if (stepping <= 0) return OMR_INVALID_ARGUMENT;
     if (algorithm < OMR_PROJECTION_MAX || algorithm > OMR_PROJECTION_SUM) return OMR_INVALID_ARGUMENT;
+    int64_t count = 0;                               /* == projectedPlaneCount (:267-274) */
+    if (oracle_projection_plane_count(algorithm, start, end, stepping, &count)) return OMR_INVALID_ARGUMENT;
     const int64_t plane = (int64_t)size_x * size_y;
     const uint8_t* from = (const uint8_t*)stack;
     uint8_t* to = (uint8_t*)out;
     const double plane_max = type_maximum(pixel_type);
     for (int64_t i = 0; i < plane; ++i) {
         double pv = 0;
-        if (algorithm == OMR_PROJECTION_MAX) {       /* :182-196 */
-            for (int z = start; z <= end; z += stepping) {
+        /* the loops of :182-196 and :268-288 by count: z = start + k * stepping never passes end */
+        if (algorithm == OMR_PROJECTION_MAX) {
+            for (int64_t k = 0; k < count; ++k) {
+                const int64_t z = start + k * stepping;
                 const double sv = pixel_value(from + (plane * z + i) * nb, pixel_type, big_endian_in);
                 if (sv > pv) pv = sv;
             }
-        } else {                                      /* :268-288 */
-            int count = 0;
-            for (int z = start; z < end; z += stepping) {
+        } else {
+            for (int64_t k = 0; k < count; ++k) {
+                const int64_t z = start + k * stepping;
                 pv += pixel_value(from + (plane * z + i) * nb, pixel_type, big_endian_in);
-                count++;
             }
             if (algorithm == OMR_PROJECTION_MEAN) pv = pv / count;
             if (pv > plane_max) pv = plane_max;

@@ -26,6 +26,8 @@ omr_status oracle_flip_int(const uint32_t* src, uint32_t* dest, int32_t size_x, 
                            int32_t flip_h, int32_t flip_v);
 omr_status oracle_flip_byte(const uint8_t* src, uint8_t* dest, int32_t size_x, int32_t size_y,
                             int32_t flip_h, int32_t flip_v);
+omr_status oracle_projection_plane_count(int32_t algorithm, int32_t start, int32_t end, int32_t stepping,
+                                         int64_t* count);
 omr_status oracle_project_stack(const void* stack, int32_t pixel_type, int32_t big_endian_in,
                                 int32_t size_x, int32_t size_y, int32_t size_z, int32_t algorithm,
                                 int32_t start, int32_t end, int32_t stepping, void* out,

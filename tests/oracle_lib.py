@@ -52,6 +52,7 @@ for name, res, args in [
     ("oracle_render_packed_int", _i32, [_QD, _CB, _i32, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
     ("oracle_flip_int", _i32, [_vp, _vp, _i32, _i32, _i32, _i32]),
     ("oracle_flip_byte", _i32, [_vp, _vp, _i32, _i32, _i32, _i32]),
+    ("oracle_projection_plane_count", _i32, [_i32, _i32, _i32, _i32, ctypes.POINTER(_i64)]),
     ("oracle_project_stack", _i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32]),
     ("oracle_mask_indices", _i32, [_vp, _sz, _i32, _i32, _i32, _i32, _vp]),
     ("oracle_jpeg_quant_tables", None, [_f32, _vp, _vp]),
