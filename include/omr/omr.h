@@ -125,7 +125,8 @@ void*       omr_ctx_get_stream(omr_ctx* ctx);
  * render, 11 = ARGB scaler: omr_render_scaled_batch_device; 12 = pyramid levels:
  * omr_pyramid_build_device; 20..26 = the batched PNG stages and 27 = the grey wave filter:
  * omr_encode_png_gray_batch_device; 30 = LZW decode and 31 = TIFF place:
- * omr_tiff_image_read_regions_device).
+ * omr_tiff_image_read_regions_device; 32 = zlib inflate: omr_inflate_batch_device and, with 31,
+ * omr_zarr_image_read_regions_device).
  */
 omr_status  omr_ctx_enable_kernel_timing(omr_ctx* ctx, int32_t enable);
 int32_t     omr_ctx_kernel_timings(omr_ctx* ctx, float* ms_out, int32_t* kind_out, int32_t cap);
@@ -1084,6 +1085,87 @@ omr_status omr_tiff_image_read_regions_device(omr_ctx* ctx, const omr_tiff_image
  * omr_render_batch_strided_device with the file's byte order.  size_c must be the image's.
  */
 omr_status omr_render_tiff_tiles(omr_ctx* ctx, const omr_tiff_image* img, int32_t level,
+                                 const omr_quantum_def* qdef, const omr_channel_binding* channels,
+                                 int32_t size_c, const omr_tile_request* reqs, int32_t n, int32_t width,
+                                 int32_t height, int32_t flip_h, int32_t flip_v, uint32_t* argb_out,
+                                 int32_t out_on_device);
+
+/* ---- OME-Zarr pyramids, zlib chunks inflated on the device (K14) -------------------------- */
+/*
+ * The third backend of PixelsService.getPixelBuffer: OME-Zarr as bioformats2raw writes it -- a
+ * Zarr v2 directory per image (series), one 5-D TCZYX array per resolution, one file per chunk.
+ * group_path is the image group (".../image.zarr/0").  Its .zattrs multiscales[0].datasets[*].path
+ * lists the levels in order; without multiscales the levels are the sub-directories 0, 1, ... that
+ * hold a .zarray.  axes, when present, must name t, c, z, y, x in that order.  Z, C and T come from
+ * the array shape; OME-XML is not read.
+ *
+ * Supported per array: zarr_format 2, order "C", a 5-D shape with chunks [1, 1, 1, ch, cw], dtype
+ * |u1 |i1 <u2 >u2 <i2 >i2 <u4 >u4 <i4 >i4 <f4 >f4 <f8 >f8 (the eight OMR_PIXELS_* types), filters
+ * null, compressor null or {"id": "zlib"}, fill_value 0 / 0.0 / null, dimension_separator "." (the
+ * default) or "/".  All levels have the same dtype, compressor and Z, C, T; level sizes are as the
+ * arrays state them.  Edge chunks are stored whole (ch * cw * bpp bytes decoded); a chunk file that
+ * does not exist reads as zeros.
+ *
+ * open: OMR_NOT_FOUND when the group directory or its first .zarray is missing;
+ * OMR_INVALID_ARGUMENT for anything unsupported (another compressor id, any filter, order "F", not
+ * five dimensions, a chunk deeper than 1 in t, c or z, a non-zero fill, another dtype, zarr_format
+ * 3, levels that disagree, a chunk above 256 MiB decoded); OMR_INTERNAL for corrupt input (JSON
+ * that does not parse, a shape or chunk that is not a positive integer or whose product
+ * overflows).  Read-only; safe to share between contexts and threads.
+ */
+typedef struct omr_zarr_image omr_zarr_image;
+typedef struct omr_zarr_info {
+    int32_t size_x, size_y, size_z, size_c, size_t_;   /* level 0 */
+    int32_t pixel_type;                                /* OMR_PIXELS_* */
+    int32_t big_endian;                                /* the arrays' byte order (">": 1) */
+    int32_t n_levels;
+    int32_t compression;                               /* 0 none, 1 zlib */
+    int32_t chunk_width, chunk_height;                 /* level 0 */
+    int32_t dimension_separator;                       /* '.' or '/' */
+} omr_zarr_info;
+omr_status omr_zarr_image_open(const char* group_path, omr_zarr_image** out);
+void       omr_zarr_image_close(omr_zarr_image* img);
+omr_status omr_zarr_image_info(const omr_zarr_image* img, omr_zarr_info* info);
+/* As omr_tiff_image_level_sizes. */
+int32_t    omr_zarr_image_level_sizes(const omr_zarr_image* img, int32_t* sizes_out, int32_t cap_pairs);
+/*
+ * The host route (no GPU): the bounds rule and packed rows of omr_tiff_image_get_tile, bytes in
+ * the array's byte order, zlib chunks decoded by omr_inflate_host.  OMR_INTERNAL: an uncompressed
+ * chunk file whose size is not ch * cw * bpp, a bad zlib stream, an I/O error.
+ */
+omr_status omr_zarr_image_get_tile(const omr_zarr_image* img, int32_t level, int32_t z, int32_t c, int32_t t,
+                                   int32_t x, int32_t y, int32_t w, int32_t h, void* dst, size_t cap);
+/*
+ * The host decoder alone, a plain serial one (nothing links libz): an RFC 1950 stream -- header
+ * with CM = 8, CINFO <= 7, a good FCHECK and no FDICT -- of RFC 1951 blocks of all three types.
+ * OMR_OK only when the stream yields exactly `expected` bytes, then the end-of-block of a final
+ * block, then the Adler-32 of those bytes; anything else is OMR_INTERNAL (unlike the LZW rule of
+ * cutting an overrunning string: a Zarr chunk's size is known exactly).  Bytes behind the Adler-32
+ * are not looked at.
+ */
+omr_status omr_inflate_host(const uint8_t* src, size_t length, uint8_t* dst, size_t expected);
+/*
+ * K14a alone: n independent zlib streams, the table layout of omr_lzw_decode_batch_device (streams
+ * below 512 MiB, d_expected[i] at most 256 MiB; nothing is written behind d_dst + d_dst_offsets[i]
+ * + d_expected[i]); d_status[i] = OMR_OK or OMR_INTERNAL by the rule of omr_inflate_host, one
+ * stream's failure leaving the others alone.  Asynchronous on the context stream;
+ * omr_ctx_kernel_timings reports kind 32.
+ */
+omr_status omr_inflate_batch_device(omr_ctx* ctx, const uint8_t* d_src, const uint64_t* d_offsets,
+                                    const uint32_t* d_lengths, const uint32_t* d_expected, int32_t n,
+                                    uint8_t* d_dst, const uint64_t* d_dst_offsets, int32_t* d_status);
+/*
+ * The contract of omr_tiff_image_read_regions_device for a Zarr level: the host lists the chunks
+ * the regions touch, each once per group, reads the chunk files into pinned staging on up to 16
+ * threads and sends bytes and tables in one copy; K14a inflates into scratch (kind 32) and K13b
+ * (predictor 1, kind 31) crops and stores; uncompressed chunks skip K14a, missing chunks store
+ * zeros.  Synchronous; OMR_INTERNAL when a chunk is corrupt.
+ */
+omr_status omr_zarr_image_read_regions_device(omr_ctx* ctx, const omr_zarr_image* img, int32_t level,
+                                              const omr_raw_tile_request* reqs, int32_t n, int32_t width,
+                                              int32_t height, void* d_dst, int64_t region_stride_bytes);
+/* omr_render_tiff_tiles for a Zarr image level. */
+omr_status omr_render_zarr_tiles(omr_ctx* ctx, const omr_zarr_image* img, int32_t level,
                                  const omr_quantum_def* qdef, const omr_channel_binding* channels,
                                  int32_t size_c, const omr_tile_request* reqs, int32_t n, int32_t width,
                                  int32_t height, int32_t flip_h, int32_t flip_v, uint32_t* argb_out,

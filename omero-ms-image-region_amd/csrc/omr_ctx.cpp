@@ -238,6 +238,7 @@ void omr_ctx_destroy(omr_ctx* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->pixbuf_state && c->pixbuf_state_free) c->pixbuf_state_free(c->pixbuf_state);
     if (c->tiff_state && c->tiff_state_free) c->tiff_state_free(c->tiff_state);
+    if (c->zarr_state && c->zarr_state_free) c->zarr_state_free(c->zarr_state);
     for (auto& t : c->timed) { c->event_pool.push_back(t.start); c->event_pool.push_back(t.stop); }
     for (auto e : c->event_pool) (void)hipEventDestroy(e);
     for (int i = 0; i < Ctx::kPinSlots; ++i) {

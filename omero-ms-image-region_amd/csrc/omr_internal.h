@@ -178,6 +178,9 @@ struct Ctx {
     // tiled TIFF reader (omr_tiffread.cpp): pinned and device staging, scratch for decoded segments
     void* tiff_state = nullptr;
     void (*tiff_state_free)(void*) = nullptr;
+    // OME-Zarr reader (omr_zarr.cpp): the same kinds of staging, its own
+    void* zarr_state = nullptr;
+    void (*zarr_state_free)(void*) = nullptr;
 };
 
 // Bracket one hot-kernel launch with events when timing is enabled.
@@ -308,6 +311,10 @@ omr_status launch_lzw_decode(Ctx* ctx, const uint8_t* d_src, const uint64_t* d_o
 // the file's byte order is not the host's (it matters to predictor 2 only).
 omr_status launch_tiff_place(Ctx* ctx, const TiffPlace* d_places, int32_t n, int32_t max_rows, int32_t bps,
                              int32_t predictor, bool swap);
+// K14a (omr_inflate.hip): n zlib streams (omr_inflate_batch_device after its argument check).
+omr_status launch_inflate(Ctx* ctx, const uint8_t* d_src, const uint64_t* d_offsets, const uint32_t* d_lengths,
+                          const uint32_t* d_expected, int32_t n, uint8_t* d_dst, const uint64_t* d_dst_offsets,
+                          int32_t* d_status);
 
 #define OMR_HIP(ctx, expr)                                         \
     do {                                                            \

@@ -108,6 +108,12 @@ class TiffInfo(ctypes.Structure):
         "predictor", "tiled", "segment_width", "segment_height", "big_tiff")]
 
 
+class ZarrInfo(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in (
+        "size_x", "size_y", "size_z", "size_c", "size_t", "pixel_type", "big_endian", "n_levels", "compression",
+        "chunk_width", "chunk_height", "dimension_separator")]
+
+
 class Region(ctypes.Structure):
     _fields_ = [("x", ctypes.c_int32), ("y", ctypes.c_int32),
                 ("width", ctypes.c_int32), ("height", ctypes.c_int32)]
@@ -286,6 +292,15 @@ _SIGS = {
     "omr_lzw_decode_batch_device": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
     "omr_tiff_image_read_regions_device": (_i32, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _i64]),
     "omr_render_tiff_tiles": (_i32, [_vp, _vp, _i32, _QD, _CB, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32]),
+    "omr_zarr_image_open": (_i32, [ctypes.c_char_p, ctypes.POINTER(_vp)]),
+    "omr_zarr_image_close": (None, [_vp]),
+    "omr_zarr_image_info": (_i32, [_vp, ctypes.POINTER(ZarrInfo)]),
+    "omr_zarr_image_level_sizes": (_i32, [_vp, ctypes.POINTER(_i32), _i32]),
+    "omr_zarr_image_get_tile": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _sz]),
+    "omr_inflate_host": (_i32, [_vp, _sz, _vp, _sz]),
+    "omr_inflate_batch_device": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "omr_zarr_image_read_regions_device": (_i32, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _i64]),
+    "omr_render_zarr_tiles": (_i32, [_vp, _vp, _i32, _QD, _CB, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32]),
     "omr_render_shape_mask_png_batch": (_i32, [_vp, ctypes.POINTER(MaskJob), _i32, _vp, _sz, _vp, _vp, _vp]),
     "omr_split_html_color": (_i32, [ctypes.c_char_p, ctypes.POINTER(_i32)]),
     "omr_shape_mask_fill_color": (_i32, [_i32, _i32, ctypes.c_char_p, _vp]),

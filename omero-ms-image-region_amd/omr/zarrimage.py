@@ -1,0 +1,181 @@
+"""ZarrImage: OME-Zarr pixel data (K14), and write_zarr, the small writer that makes the test and
+probe groups.
+
+The third backend of pixelsService.getPixelBuffer beside the ROMIO file (pixbuf.PixelBuffer) and
+the tiled TIFF (tiffimage.TiffImage): a Zarr v2 directory as bioformats2raw writes it, one 5-D
+TCZYX array per resolution and one file per chunk.  Reads go through libomr.so: get_tile on the
+host (plain serial inflate), read_regions and render_tiles with the zlib chunks inflated on the GPU
+(omr_inflate.hip).
+"""
+import ctypes
+import json
+import os
+import zlib
+
+import numpy as np
+
+from . import _lib
+from ._lib import lib
+from .tiffimage import _NP_NAMES
+
+
+def write_zarr(path, planes, levels=(), chunk=(256, 256), byteorder="<", compressor="zlib", level=1, strategy=None,
+               dimension_separator="/", skip_zero_chunks=False, zarray_overrides=None):
+    """Write a [t][c][z][y][x] array as the image group `path` of an OME-Zarr (Zarr v2, NGFF 0.4
+    multiscales metadata): array "0" holds `planes`, arrays "1", "2", ... hold `levels` (arrays of
+    the same [t][c][z] with their own [y][x]).  chunk = (w, h): chunks [1, 1, 1, h, w], edge chunks
+    stored whole; byteorder "<" or ">"; compressor "zlib" (stdlib zlib at `level`, `strategy` one
+    of zlib.Z_* or None for the default) or None; dimension_separator "/" (as bioformats2raw) or
+    "."; skip_zero_chunks: an all-zero chunk is not written; zarray_overrides = {key: value}
+    replaces entries of every .zarray (to make groups a reader must reject)."""
+    planes = np.asarray(planes)
+    assert planes.ndim == 5, "planes must be [t][c][z][y][x]"
+    arrays = [planes] + [np.asarray(lv) for lv in levels]
+    for lv in arrays[1:]:
+        assert lv.ndim == 5 and lv.shape[:3] == planes.shape[:3] and lv.dtype == planes.dtype
+    assert compressor in ("zlib", None) and dimension_separator in ("/", ".")
+    dt = planes.dtype
+    fdt = dt.newbyteorder(byteorder) if dt.itemsize > 1 else dt
+    dtype_name = ("|" if dt.itemsize == 1 else byteorder) + dt.kind + str(dt.itemsize)
+    cw, ch = chunk
+    path = str(path)
+    os.makedirs(path, exist_ok=True)
+    with open(os.path.join(path, ".zgroup"), "w") as f:
+        json.dump({"zarr_format": 2}, f)
+    axes = [{"name": "t", "type": "time"}, {"name": "c", "type": "channel"}, {"name": "z", "type": "space"},
+            {"name": "y", "type": "space"}, {"name": "x", "type": "space"}]
+    datasets = [{"path": str(k), "coordinateTransformations": [{"type": "scale", "scale": [1.0, 1.0, 1.0, float(2 ** k), float(2 ** k)]}]}
+                for k in range(len(arrays))]
+    with open(os.path.join(path, ".zattrs"), "w") as f:
+        json.dump({"multiscales": [{"version": "0.4", "axes": axes, "datasets": datasets}]}, f, indent=1)
+    for k, a in enumerate(arrays):
+        adir = os.path.join(path, str(k))
+        os.makedirs(adir, exist_ok=True)
+        meta = {"zarr_format": 2, "shape": list(a.shape), "chunks": [1, 1, 1, ch, cw], "dtype": dtype_name,
+                "compressor": {"id": "zlib", "level": level} if compressor else None, "fill_value": 0, "order": "C",
+                "filters": None, "dimension_separator": dimension_separator}
+        meta.update(zarray_overrides or {})
+        with open(os.path.join(adir, ".zarray"), "w") as f:
+            json.dump(meta, f, indent=1)
+        st, sc, sz, h, w = a.shape
+        for t in range(st):
+            for c in range(sc):
+                for z in range(sz):
+                    for cy in range((h + ch - 1) // ch):
+                        for cx in range((w + cw - 1) // cw):
+                            part = a[t, c, z, cy * ch:(cy + 1) * ch, cx * cw:(cx + 1) * cw]
+                            if skip_zero_chunks and not part.any():
+                                continue
+                            full = np.zeros((ch, cw), dtype=fdt)
+                            full[:part.shape[0], :part.shape[1]] = part
+                            raw = full.tobytes()
+                            if compressor:
+                                co = zlib.compressobj(level, zlib.DEFLATED, 15, 8,
+                                                      zlib.Z_DEFAULT_STRATEGY if strategy is None else strategy)
+                                raw = co.compress(raw) + co.flush()
+                            name = dimension_separator.join(str(v) for v in (t, c, z, cy, cx))
+                            file = os.path.join(adir, name)
+                            os.makedirs(os.path.dirname(file), exist_ok=True)
+                            with open(file, "wb") as f:
+                                f.write(raw)
+
+
+class ZarrImage:
+    """An open OME-Zarr image group (omr_zarr_image): `path` is the image (series) group, for
+    instance image.zarr/0.  Z, C and T come from the array shape; OME-XML is not read."""
+
+    def __init__(self, path):
+        h = ctypes.c_void_p()
+        st = lib.omr_zarr_image_open(str(path).encode(), ctypes.byref(h))
+        if st != _lib.OK:
+            raise _lib.OmrError(st, f"cannot open Zarr image {path}")
+        self.h = h
+        i = _lib.ZarrInfo()
+        _lib.check(lib.omr_zarr_image_info(self.h, ctypes.byref(i)))
+        self.info = {n: int(getattr(i, n)) for n, _ in _lib.ZarrInfo._fields_}
+        self.size_x, self.size_y = i.size_x, i.size_y
+        self.size_z, self.size_c, self.size_t = i.size_z, i.size_c, i.size_t
+        self.pixel_type = i.pixel_type
+        self.big_endian = bool(i.big_endian)
+        self.dtype = np.dtype((">" if self.big_endian else "<") + _NP_NAMES[self.pixel_type])
+        sizes = (ctypes.c_int32 * (2 * i.n_levels))()
+        n = lib.omr_zarr_image_level_sizes(self.h, sizes, i.n_levels)
+        self.level_sizes = [[sizes[2 * k], sizes[2 * k + 1]] for k in range(n)]
+
+    def close(self):
+        if self.h:
+            lib.omr_zarr_image_close(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def getResolutionLevels(self):
+        return len(self.level_sizes)
+
+    def getResolutionDescriptions(self):
+        return [list(s) for s in self.level_sizes]
+
+    def get_tile(self, level, z, c, t, x, y, w, h):
+        """The host route: [h][w] array in the arrays' byte order (omr_zarr_image_get_tile)."""
+        if w < 0 or h < 0:
+            raise _lib.OmrError(_lib.INVALID_ARGUMENT, f"tile {w}x{h} out of bounds")
+        out = np.empty((h, w), dtype=self.dtype)
+        _lib.check(lib.omr_zarr_image_get_tile(self.h, int(level), z, c, t, x, y, w, h, out.ctypes.data,
+                                               max(out.nbytes, 1)))
+        return out
+
+    def read_regions(self, ctx, level, reqs, w, h, out=None, region_stride=None):
+        """reqs = [(z, c, t, x, y)], every region w x h of `level`, read and inflated on ctx's GPU
+        (omr_zarr_image_read_regions_device).  Returns a device uint8 tensor [n][region_stride]
+        (allocated when out is None; region_stride defaults to the region's bytes rounded up to
+        16): region i is its first w*h*bytes_per_pixel bytes, rows packed, the arrays' byte order."""
+        import torch
+        n = len(reqs)
+        bpp = _lib.BYTES_PER_PIXEL[self.pixel_type]
+        if region_stride is None:
+            region_stride = (w * h * bpp + 15) // 16 * 16
+        if out is None:
+            out = torch.zeros((max(n, 1), max(region_stride, 1)), dtype=torch.uint8, device=f"cuda:{ctx.device}")
+            ctx.order_after_torch()
+        tab = (_lib.RawTileRequest * max(n, 1))()
+        for i, r in enumerate(reqs):
+            tab[i].z, tab[i].c, tab[i].t, tab[i].x, tab[i].y = [int(v) for v in r]
+        _lib.check(lib.omr_zarr_image_read_regions_device(ctx.h, self.h, int(level), ctypes.addressof(tab), n, int(w),
+                                                          int(h), out.data_ptr(), int(region_stride)), ctx.h)
+        return out[:n]
+
+    def render_tiles(self, ctx, qdef, channels, level, requests, width, height, out=None, flip_h=False,
+                     flip_v=False, bindings=None):
+        """Context.render_pixel_buffer_tiles for this image's `level` (omr_render_zarr_tiles):
+        requests = [(z, t, x, y)]; out: host numpy [n][h][w] uint32 (allocated when None) or a
+        device tensor (rendered in place)."""
+        from .context import _ptr, make_bindings
+        arr, keep = make_bindings(channels) if bindings is None else bindings
+        n = len(requests)
+        reqs = (_lib.TileRequest * max(n, 1))(*[_lib.TileRequest(*r) for r in requests])
+        on_device = out is not None and hasattr(out, "data_ptr")
+        if out is None:
+            out = np.empty((n, height, width), dtype=np.uint32)
+        _lib.check(lib.omr_render_zarr_tiles(ctx.h, self.h, int(level), ctypes.byref(qdef), arr, len(channels), reqs, n,
+                                             int(width), int(height), int(flip_h), int(flip_v), _ptr(out),
+                                             int(on_device)), ctx.h)
+        return out
+
+
+def inflate_host(stream, expected):
+    """The host inflate alone (omr_inflate_host): a zlib stream into exactly `expected` bytes, or
+    OmrError(INTERNAL)."""
+    src = np.frombuffer(bytes(stream), dtype=np.uint8)
+    out = np.zeros(max(int(expected), 1), dtype=np.uint8)
+    _lib.check(lib.omr_inflate_host(src.ctypes.data if src.size else None, src.size, out.ctypes.data, int(expected)))
+    return out[:int(expected)].tobytes()
