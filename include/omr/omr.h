@@ -126,7 +126,8 @@ void*       omr_ctx_get_stream(omr_ctx* ctx);
  * omr_pyramid_build_device; 20..26 = the batched PNG stages and 27 = the grey wave filter:
  * omr_encode_png_gray_batch_device; 30 = LZW decode and 31 = TIFF place:
  * omr_tiff_image_read_regions_device; 32 = zlib inflate: omr_inflate_batch_device and, with 31,
- * omr_zarr_image_read_regions_device).
+ * omr_zarr_image_read_regions_device; 33 = LZ4 decode: omr_lz4_decode_batch_device and, with 34 =
+ * Blosc place, omr_zarr_image_read_regions_device on a Blosc image).
  */
 omr_status  omr_ctx_enable_kernel_timing(omr_ctx* ctx, int32_t enable);
 int32_t     omr_ctx_kernel_timings(omr_ctx* ctx, float* ms_out, int32_t* kind_out, int32_t cap);
@@ -1119,7 +1120,7 @@ typedef struct omr_zarr_info {
     int32_t pixel_type;                                /* OMR_PIXELS_* */
     int32_t big_endian;                                /* the arrays' byte order (">": 1) */
     int32_t n_levels;
-    int32_t compression;                               /* 0 none, 1 zlib */
+    int32_t compression;                               /* 0 none, 1 zlib, 2 Blosc (open_ex only) */
     int32_t chunk_width, chunk_height;                 /* level 0 */
     int32_t dimension_separator;                       /* '.' or '/' */
 } omr_zarr_info;
@@ -1170,6 +1171,63 @@ omr_status omr_render_zarr_tiles(omr_ctx* ctx, const omr_zarr_image* img, int32_
                                  int32_t size_c, const omr_tile_request* reqs, int32_t n, int32_t width,
                                  int32_t height, int32_t flip_h, int32_t flip_v, uint32_t* argb_out,
                                  int32_t out_on_device);
+
+/* ---- Blosc OME-Zarr chunks, LZ4 blocks decoded on the device (K15) -------------------------- */
+/*
+ * omr_zarr_image_open_ex is omr_zarr_image_open with the set of chunk codecs the caller accepts:
+ * omr_zarr_image_open(path, out) is open_ex with codecs = OMR_ZARR_CODEC_ZLIB, and opt == NULL
+ * means the same.  OMR_INVALID_ARGUMENT: unknown bits in codecs, a struct_size smaller than the
+ * struct, a codec named in .zarray but not in codecs.  With OMR_ZARR_CODEC_BLOSC the compressor
+ * {"id": "blosc", "cname": "lz4" | "lz4hc", "shuffle": 0 | 1} is accepted (bioformats2raw's
+ * default); "shuffle": -1 only for types wider than one byte (on a one-byte type numcodecs reads
+ * it as bit-shuffle); clevel and blocksize are ignored.  Any other cname (blosclz, zstd, zlib,
+ * snappy) and "shuffle": 2 are OMR_INVALID_ARGUMENT.  Every other rule of omr_zarr_image_open
+ * holds.  On a Blosc image omr_zarr_info.compression reads 2, and omr_zarr_image_get_tile,
+ * omr_zarr_image_read_regions_device and omr_render_zarr_tiles work unchanged: on the device route
+ * the host checks each chunk's container (OMR_INTERNAL before any launch) and lists its streams,
+ * K15a decodes the LZ4 streams and copies the stored ones into scratch (kind 33) and K15b crops
+ * with the byte un-shuffle folded into its loads (kind 34); memcpyed chunks are placed from the
+ * uploaded bytes, missing chunks store zeros.
+ *
+ * The Blosc 1 container as read here (as recalled, not pinned against c-blosc): a 16-byte header
+ * -- version 2, codec version, flags, typesize, int32 LE nbytes, blocksize, cbytes -- with flags
+ * 0x01 byte shuffle, 0x02 memcpyed, 0x04 bit shuffle (refused), 0x10 do not split, bits 5-7 the
+ * compressor format (1 = LZ4 / LZ4HC, any other refused); then int32 bstarts[ceil(nbytes /
+ * blocksize)]; a block is typesize splits when 0x10 is clear, typesize <= 16, blocksize / typesize
+ * >= 128 and it is not the leftover block, else one; a split is int32 csize and csize bytes,
+ * csize == its decoded size meaning stored raw.  The decoder follows the header's typesize.  The
+ * splits listed, with their csize words, may not add up to more than the bytes behind the table,
+ * and a chunk of more than 2^20 splits is refused (OMR_INTERNAL).
+ */
+#define OMR_ZARR_CODEC_ZLIB  1u
+#define OMR_ZARR_CODEC_BLOSC 2u
+typedef struct omr_zarr_open_options {
+    uint32_t struct_size;                              /* sizeof(omr_zarr_open_options) */
+    uint32_t codecs;                                   /* OMR_ZARR_CODEC_* bits */
+} omr_zarr_open_options;
+omr_status omr_zarr_image_open_ex(const char* group_path, const omr_zarr_open_options* opt, omr_zarr_image** out);
+/*
+ * One LZ4 block, serial (nothing links liblz4): sequences of a token (high nibble the literal
+ * length, low nibble the match length minus 4, a nibble of 15 extended by bytes until one is not
+ * 255), the literals, a 2-byte LE offset and the match, which may overlap its own output.  The
+ * block ends only right after a literal run (possibly empty) that consumes the last input byte.
+ * OMR_OK only when exactly `expected` bytes were produced at that point; OMR_INTERNAL for offset
+ * 0, an offset beyond the bytes produced, literals or an extension running past the input, output
+ * past `expected`, input that ends after a match or inside a sequence, too few or too many bytes.
+ */
+omr_status omr_lz4_decode_host(const uint8_t* src, size_t length, uint8_t* dst, size_t expected);
+/* One Blosc 1 chunk (the container above) into exactly `expected` bytes, un-shuffled; OMR_INTERNAL
+ * for anything the container rules or omr_lz4_decode_host refuse. */
+omr_status omr_blosc_decode_host(const uint8_t* src, size_t length, uint8_t* dst, size_t expected);
+/*
+ * K15a alone: n independent LZ4 blocks, the table layout and limits of omr_inflate_batch_device;
+ * d_status[i] = OMR_OK or OMR_INTERNAL by the rule of omr_lz4_decode_host, one stream's failure
+ * leaving the others alone, nothing written behind d_dst + d_dst_offsets[i] + d_expected[i].
+ * Asynchronous on the context stream; omr_ctx_kernel_timings reports kind 33.
+ */
+omr_status omr_lz4_decode_batch_device(omr_ctx* ctx, const uint8_t* d_src, const uint64_t* d_offsets,
+                                       const uint32_t* d_lengths, const uint32_t* d_expected, int32_t n,
+                                       uint8_t* d_dst, const uint64_t* d_dst_offsets, int32_t* d_status);
 
 #ifdef __cplusplus
 }

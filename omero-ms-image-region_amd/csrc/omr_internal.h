@@ -316,6 +316,43 @@ omr_status launch_inflate(Ctx* ctx, const uint8_t* d_src, const uint64_t* d_offs
                           const uint32_t* d_expected, int32_t n, uint8_t* d_dst, const uint64_t* d_dst_offsets,
                           int32_t* d_status);
 
+// K15, host half (omr_blosc.cpp).  One LZ4 block into exactly `expected` bytes (the rule of
+// omr_lz4_decode_host); every read and write is checked first.
+bool lz4_decode(const uint8_t* s, size_t len, uint8_t* d, size_t expected);
+// One stream of a Blosc chunk: csize bytes at src_off of the chunk file, neblock bytes at dst_off of
+// the chunk's (still shuffled) bytes; raw: stored, csize == neblock.
+struct BloscStream {
+    uint32_t src_off, csize, dst_off, neblock;
+    bool raw;
+};
+struct BloscLayout {
+    uint32_t nbytes = 0, blocksize = 0, typesize = 0;
+    bool shuffled = false;       // flag 0x01 and typesize > 1
+    bool memcpyed = false;       // the pixels follow the header raw and unshuffled; no streams
+    std::vector<BloscStream> streams;
+};
+// The container of a chunk file of `len` bytes that must decode to `expected`: header, bstarts and
+// the chain of csize words, all checked against len (no stream is decoded).  false: corrupt, or
+// more than kMaxBloscStreams streams.  The streams listed, with their csize words, never add up to
+// more than the bytes behind the table, so the list is bounded by the file's length as well.
+constexpr size_t kMaxBloscStreams = (size_t)1 << 20;
+bool blosc_parse(const uint8_t* p, size_t len, size_t expected, BloscLayout& out);
+// K15a (omr_blosc.hip): n streams (omr_lz4_decode_batch_device after its argument check); d_raw
+// (optional) marks the streams that are stored, not LZ4: they are copied, lengths[i] == expected[i].
+omr_status launch_lz4_decode(Ctx* ctx, const uint8_t* d_src, const uint64_t* d_offsets, const uint32_t* d_lengths,
+                             const uint32_t* d_expected, const uint8_t* d_raw, int32_t n, uint8_t* d_dst,
+                             const uint64_t* d_dst_offsets, int32_t* d_status);
+// K15b: a TiffPlace whose source holds a Blosc chunk's bytes, shuffled per block when `shuffled`
+// (decoded byte i * typesize + j of a block of nb bytes is its byte j * (nb / typesize) + i).
+struct BloscPlace {
+    const uint8_t* src;
+    uint8_t* dst;
+    int32_t seg_w, dst_pitch;
+    int32_t x0, x1, y0, y1;
+    uint32_t blocksize, nbytes, typesize, shuffled;
+};
+omr_status launch_blosc_place(Ctx* ctx, const BloscPlace* d_places, int32_t n, int32_t max_rows, int32_t bps);
+
 #define OMR_HIP(ctx, expr)                                         \
     do {                                                            \
         hipError_t _e = (expr);                                     \

@@ -7,7 +7,9 @@
 // route (omr_inflate_host, omr_zarr_image_get_tile: the reference of the tests and the route of
 // single reads) and the staging of the device route: the chunks the requested regions touch are
 // listed once each, their files go to pinned memory and in one copy to the device with the chunk
-// table, K14a inflates them (omr_inflate.hip) and K13b places them (omr_tiffread.hip).
+// table, K14a inflates them (omr_inflate.hip) and K13b places them (omr_tiffread.hip).  Blosc chunks
+// (K15, omr_zarr_image_open_ex) take the same staging: their container is read by omr_blosc.cpp, on
+// the device route into K15a's stream table, and K15b places them (omr_blosc.hip).
 #include "omr_internal.h"
 
 #include <dirent.h>
@@ -21,8 +23,18 @@
 #include <thread>
 #include <unordered_map>
 
+// The stand-alone host checks link this file without the kernels: the Blosc launches may be absent.
+namespace omr {
+omr_status launch_lz4_decode(Ctx* ctx, const uint8_t* d_src, const uint64_t* d_offsets, const uint32_t* d_lengths,
+                             const uint32_t* d_expected, const uint8_t* d_raw, int32_t n, uint8_t* d_dst,
+                             const uint64_t* d_dst_offsets, int32_t* d_status) __attribute__((weak));
+omr_status launch_blosc_place(Ctx* ctx, const BloscPlace* d_places, int32_t n, int32_t max_rows, int32_t bps)
+    __attribute__((weak));
+}  // namespace omr
+
 namespace {
 
+constexpr int kNone = 0, kZlib = 1, kBlosc = 2;             // omr_zarr_info.compression
 constexpr uint64_t kMaxChunkBytes = (uint64_t)256 << 20;    // decoded size of one chunk
 constexpr uint64_t kMaxStreamBytes = ((uint64_t)512 << 20) - 1;
 constexpr size_t kMaxJsonBytes = (size_t)1 << 20;
@@ -230,7 +242,8 @@ struct Level {
 struct omr_zarr_image {
     int32_t sz = 0, sc = 0, st = 0;
     int32_t pt = 0, bpp = 0;
-    bool big = false, zlib = false;
+    bool big = false;
+    int comp = kNone;
     std::vector<Level> levels;
 };
 
@@ -438,7 +451,8 @@ bool inflate(const uint8_t* s, size_t len, uint8_t* d, size_t expected) {
 struct ArrayMeta {
     int64_t shape[5], chunks[5];
     int32_t pt = 0;
-    bool big = false, zlib = false;
+    bool big = false;
+    int comp = kNone;
     char sep = '.';
 };
 
@@ -452,7 +466,7 @@ omr_status five(const Json* v, int64_t* out) {
     return OMR_OK;
 }
 
-omr_status parse_zarray(const std::vector<uint8_t>& text, ArrayMeta& m) {
+omr_status parse_zarray(const std::vector<uint8_t>& text, uint32_t codecs, ArrayMeta& m) {
     Json j;
     if (!json_parse(reinterpret_cast<const char*>(text.data()), text.size(), j) || j.type != Json::Object) return OMR_INTERNAL;
     const Json* v = j.get("zarr_format");
@@ -478,11 +492,25 @@ omr_status parse_zarray(const std::vector<uint8_t>& text, ArrayMeta& m) {
     v = j.get("filters");
     if (v && v->type != Json::Null && !(v->type == Json::Array && v->arr.empty())) return OMR_INVALID_ARGUMENT;
     v = j.get("compressor");
-    m.zlib = false;
+    m.comp = kNone;
     if (v && v->type != Json::Null) {
         const Json* id = v->get("id");
-        if (!id || id->type != Json::String || id->s != "zlib") return OMR_INVALID_ARGUMENT;
-        m.zlib = true;
+        if (!id || id->type != Json::String) return OMR_INVALID_ARGUMENT;
+        if (id->s == "zlib" && (codecs & OMR_ZARR_CODEC_ZLIB)) {
+            m.comp = kZlib;
+        } else if (id->s == "blosc" && (codecs & OMR_ZARR_CODEC_BLOSC)) {
+            // LZ4 inside (lz4hc writes the same block format); byte shuffle or none.  -1 is numcodecs'
+            // automatic choice: byte shuffle for types wider than a byte, bit shuffle for the others.
+            const Json* cname = v->get("cname");
+            if (!cname || cname->type != Json::String || (cname->s != "lz4" && cname->s != "lz4hc")) return OMR_INVALID_ARGUMENT;
+            if (const Json* sh = v->get("shuffle")) {
+                if (sh->type != Json::Number || !sh->is_int) return OMR_INVALID_ARGUMENT;
+                if (sh->i != 0 && sh->i != 1 && !(sh->i == -1 && !one_byte)) return OMR_INVALID_ARGUMENT;
+            }
+            m.comp = kBlosc;
+        } else {
+            return OMR_INVALID_ARGUMENT;
+        }
     }
     v = j.get("fill_value");
     if (v && v->type != Json::Null && !(v->type == Json::Number && v->d == 0)) return OMR_INVALID_ARGUMENT;
@@ -562,7 +590,7 @@ omr_status load_chunk(const omr_zarr_image* im, const Level& L, int32_t t, int32
                       std::vector<uint8_t>& comp, std::vector<uint8_t>& out) {
     const size_t expected = (size_t)L.ch * L.cw * im->bpp;
     const std::string path = chunk_path(L, t, c, z, cy, cx);
-    if (!im->zlib) {
+    if (im->comp == kNone) {
         const Slurp r = read_file(path, expected, out);
         if (r == Slurp::Missing) {
             out.assign(expected, 0);
@@ -574,6 +602,7 @@ omr_status load_chunk(const omr_zarr_image* im, const Level& L, int32_t t, int32
     out.assign(expected, 0);
     if (r == Slurp::Missing) return OMR_OK;
     if (r != Slurp::Ok) return OMR_INTERNAL;
+    if (im->comp == kBlosc) return omr_blosc_decode_host(comp.data(), comp.size(), out.data(), expected);
     return inflate(comp.data(), comp.size(), out.data(), expected) ? OMR_OK : OMR_INTERNAL;
 }
 
@@ -589,9 +618,13 @@ struct ZarrPipe {
     size_t regions_cap = 0;
     void* d_out = nullptr;       // and its ARGB when the caller's output is host memory
     size_t out_cap = 0;
+    void* pin_tab = nullptr;     // Blosc: the stream table and the placements, sized after the files are read
+    void* d_tab = nullptr;
+    size_t tab_cap = 0;
     ~ZarrPipe() {
         if (pin) (void)hipHostFree(pin);
-        for (void* p : {d_in, d_scratch, d_regions, d_out})
+        if (pin_tab) (void)hipHostFree(pin_tab);
+        for (void* p : {d_in, d_scratch, d_regions, d_out, d_tab})
             if (p) (void)hipFree(p);
     }
 };
@@ -640,6 +673,95 @@ struct UniqueChunk {
 constexpr size_t kGroupInBytes = (size_t)128 << 20;        // chunk file bytes per group (as K13)
 constexpr size_t kGroupScratchBytes = (size_t)512 << 20;   // decoded bytes per group
 constexpr size_t kRenderGroupBytes = (size_t)256 << 20;    // region bytes per render group
+
+// The Blosc half of read_group, from the chunk files in pinned memory on: the host checks every
+// chunk's container and lists its streams (a bad one ends the call before any launch), the bytes go
+// up, the tables behind them in a copy of their own (their size is known only now), K15a decodes
+// the streams into the chunks' scratch and K15b places with the un-shuffle in its loads.
+omr_status finish_blosc(omr::Ctx* ctx, ZarrPipe* T, const std::vector<UniqueChunk>& chunks,
+                        const std::vector<omr::TiffPlace>& places, const std::vector<int32_t>& place_chunk,
+                        uint32_t expected, size_t in_bytes, int32_t max_rows, int32_t bpp) {
+    using omr::align_up;
+    using omr::BloscPlace;
+    if (!omr::launch_lz4_decode || !omr::launch_blosc_place) return omr::fail(ctx, OMR_DEVICE, "zarr: built without the Blosc kernels");
+    uint8_t* pin = static_cast<uint8_t*>(T->pin);
+    uint8_t* din = static_cast<uint8_t*>(T->d_in);
+    uint8_t* dscr = static_cast<uint8_t*>(T->d_scratch);
+    std::vector<omr::BloscLayout> layouts(chunks.size());
+    size_t m = 0;
+    for (size_t k = 0; k < chunks.size(); ++k) {
+        const UniqueChunk& u = chunks[k];
+        if (!u.cnt) continue;
+        if (!omr::blosc_parse(pin + u.in_off, (size_t)u.cnt, expected, layouts[k]))
+            return omr::fail(ctx, OMR_INTERNAL, "zarr: corrupt blosc chunk");
+        m += layouts[k].streams.size();
+    }
+    // tables: [offsets u64 m][dst offsets u64 m][lengths u32 m][expected u32 m][raw u8 m][places] | [status i32 m]
+    const size_t o_dst = 8 * m, o_len = o_dst + 8 * m, o_exp = o_len + 4 * m, o_raw = o_exp + 4 * m;
+    const size_t o_place = align_up(o_raw + m, 16), up_bytes = o_place + places.size() * sizeof(BloscPlace);
+    const size_t o_status = align_up(up_bytes, 256), total = o_status + 4 * m;
+    if (total > T->tab_cap) {
+        if (T->pin_tab) OMR_HIP(ctx, hipHostFree(T->pin_tab));
+        T->pin_tab = nullptr;
+        const size_t keep = T->tab_cap;
+        T->tab_cap = 0;
+        omr_status st = grow_device(ctx, T->d_tab, T->tab_cap, std::max(total, keep + keep / 2));
+        if (st) return st;
+        const hipError_t e = hipHostMalloc(&T->pin_tab, T->tab_cap, hipHostMallocDefault);
+        if (e != hipSuccess) {
+            T->tab_cap = 0;                              // both are made again on the next call
+            return omr::hip_fail(ctx, e, "hipHostMalloc(zarr tables)");
+        }
+    }
+    uint8_t* tab = static_cast<uint8_t*>(T->pin_tab);
+    uint8_t* dtab = static_cast<uint8_t*>(T->d_tab);
+    uint64_t* h_off = reinterpret_cast<uint64_t*>(tab);
+    uint64_t* h_dst = reinterpret_cast<uint64_t*>(tab + o_dst);
+    uint32_t* h_len = reinterpret_cast<uint32_t*>(tab + o_len);
+    uint32_t* h_exp = reinterpret_cast<uint32_t*>(tab + o_exp);
+    uint8_t* h_raw = tab + o_raw;
+    size_t j = 0;
+    for (size_t k = 0; k < chunks.size(); ++k)
+        for (const omr::BloscStream& s : layouts[k].streams) {
+            h_off[j] = chunks[k].in_off + s.src_off;
+            h_dst[j] = chunks[k].scratch_off + s.dst_off;
+            h_len[j] = s.csize;
+            h_exp[j] = s.neblock;
+            h_raw[j] = s.raw;
+            ++j;
+        }
+    BloscPlace* h_place = reinterpret_cast<BloscPlace*>(tab + o_place);
+    for (size_t k = 0; k < places.size(); ++k) {
+        const size_t ck = (size_t)place_chunk[k];
+        const UniqueChunk& u = chunks[ck];
+        const omr::BloscLayout& L = layouts[ck];
+        const omr::TiffPlace& p = places[k];
+        BloscPlace b;
+        b.src = !u.cnt ? nullptr : L.memcpyed ? din + u.in_off + 16 : dscr + u.scratch_off;
+        b.dst = p.dst;
+        b.seg_w = p.seg_w; b.dst_pitch = p.dst_pitch;
+        b.x0 = p.x0; b.x1 = p.x1; b.y0 = p.y0; b.y1 = p.y1;
+        b.blocksize = L.blocksize; b.nbytes = L.nbytes; b.typesize = L.typesize;
+        b.shuffled = u.cnt && L.shuffled && !L.memcpyed;
+        h_place[k] = b;
+    }
+    if (in_bytes) OMR_HIP(ctx, hipMemcpyAsync(din, pin, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    OMR_HIP(ctx, hipMemcpyAsync(dtab, tab, up_bytes, hipMemcpyHostToDevice, ctx->stream));
+    omr_status st = omr::launch_lz4_decode(ctx, din, reinterpret_cast<const uint64_t*>(dtab),
+                                           reinterpret_cast<const uint32_t*>(dtab + o_len),
+                                           reinterpret_cast<const uint32_t*>(dtab + o_exp), dtab + o_raw, (int32_t)m, dscr,
+                                           reinterpret_cast<const uint64_t*>(dtab + o_dst),
+                                           reinterpret_cast<int32_t*>(dtab + o_status));
+    if (st) return st;
+    st = omr::launch_blosc_place(ctx, reinterpret_cast<const BloscPlace*>(dtab + o_place), (int32_t)places.size(), max_rows, bpp);
+    if (st) return st;
+    if (m) OMR_HIP(ctx, hipMemcpyAsync(tab + o_status, dtab + o_status, 4 * m, hipMemcpyDeviceToHost, ctx->stream));
+    OMR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const int32_t* h_status = reinterpret_cast<const int32_t*>(tab + o_status);
+    for (size_t i = 0; i < m; ++i)
+        if (h_status[i] != OMR_OK) return omr::fail(ctx, OMR_INTERNAL, "zarr: corrupt blosc chunk");
+    return OMR_OK;
+}
 
 // One group of regions: reqs[r0, r1).
 omr_status read_group(omr::Ctx* ctx, const omr_zarr_image* im, int32_t level, const omr_raw_tile_request* reqs, int32_t r0,
@@ -693,7 +815,7 @@ omr_status read_group(omr::Ctx* ctx, const omr_zarr_image* im, int32_t level, co
             return;
         }
         if (!S_ISREG(sb.st_mode)) bad = 1;
-        else if (im->zlib ? (uint64_t)sb.st_size > kMaxStreamBytes || sb.st_size == 0 : (uint64_t)sb.st_size != expected) bad = 2;
+        else if (im->comp != kNone ? (uint64_t)sb.st_size > kMaxStreamBytes || sb.st_size == 0 : (uint64_t)sb.st_size != expected) bad = 2;
         else u.cnt = (uint64_t)sb.st_size;
     });
     if (bad == 1) return omr::fail(ctx, OMR_INTERNAL, "zarr: chunk file cannot be read");
@@ -705,16 +827,17 @@ omr_status read_group(omr::Ctx* ctx, const omr_zarr_image* im, int32_t level, co
         if (!u.cnt) continue;
         u.in_off = in_bytes;
         in_bytes += align_up((size_t)u.cnt, 16);
-        if (im->zlib) {
+        if (im->comp != kNone) {
             u.scratch_off = scratch_bytes;
             scratch_bytes += align_up((size_t)expected, 16);
-            coded.push_back((int32_t)k);
+            if (im->comp == kZlib) coded.push_back((int32_t)k);
         }
     }
+    const bool blosc = im->comp == kBlosc;                 // its tables go up behind the bytes, from T->pin_tab
     const size_t m = coded.size();
     // staging: [bytes][offsets u64 m][dst offsets u64 m][lengths u32 m][expected u32 m][places] | [status i32 m]
     const size_t o_off = align_up(in_bytes, 256), o_dst = o_off + 8 * m, o_len = o_dst + 8 * m, o_exp = o_len + 4 * m;
-    const size_t o_place = align_up(o_exp + 4 * m, 16), up_bytes = o_place + places.size() * sizeof(TiffPlace);
+    const size_t o_place = align_up(o_exp + 4 * m, 16), up_bytes = o_place + (blosc ? 0 : places.size() * sizeof(TiffPlace));
     const size_t o_status = align_up(up_bytes, 256), total = o_status + 4 * m;
     ZarrPipe* T = get_zarr_pipe(ctx);
     if (total > T->in_cap) {
@@ -755,6 +878,7 @@ omr_status read_group(omr::Ctx* ctx, const omr_zarr_image* im, int32_t level, co
         if (got != u.cnt) io_error = true;
     });
     if (io_error) return omr::fail(ctx, OMR_INTERNAL, "zarr: chunk read failed");
+    if (blosc) return finish_blosc(ctx, T, chunks, places, place_chunk, expected, in_bytes, max_rows, im->bpp);
     uint64_t* h_off = reinterpret_cast<uint64_t*>(pin + o_off);
     uint64_t* h_dst = reinterpret_cast<uint64_t*>(pin + o_dst);
     uint32_t* h_len = reinterpret_cast<uint32_t*>(pin + o_len);
@@ -769,7 +893,7 @@ omr_status read_group(omr::Ctx* ctx, const omr_zarr_image* im, int32_t level, co
     TiffPlace* h_place = reinterpret_cast<TiffPlace*>(pin + o_place);
     for (size_t k = 0; k < places.size(); ++k) {
         const UniqueChunk& u = chunks[(size_t)place_chunk[k]];
-        places[k].src = !u.cnt ? nullptr : im->zlib ? dscr + u.scratch_off : din + u.in_off;
+        places[k].src = !u.cnt ? nullptr : im->comp == kZlib ? dscr + u.scratch_off : din + u.in_off;
         h_place[k] = places[k];
     }
     OMR_HIP(ctx, hipMemcpyAsync(din, pin, up_bytes, hipMemcpyHostToDevice, ctx->stream));
@@ -796,9 +920,19 @@ using namespace omr;
 extern "C" {
 
 omr_status omr_zarr_image_open(const char* group_path, omr_zarr_image** out) {
+    return omr_zarr_image_open_ex(group_path, nullptr, out);
+}
+
+omr_status omr_zarr_image_open_ex(const char* group_path, const omr_zarr_open_options* opt, omr_zarr_image** out) {
     if (!out) return OMR_INVALID_ARGUMENT;
     *out = nullptr;
     if (!group_path || !*group_path) return OMR_INVALID_ARGUMENT;
+    uint32_t codecs = OMR_ZARR_CODEC_ZLIB;
+    if (opt) {
+        if (opt->struct_size < sizeof(omr_zarr_open_options)) return OMR_INVALID_ARGUMENT;
+        if (opt->codecs & ~(OMR_ZARR_CODEC_ZLIB | OMR_ZARR_CODEC_BLOSC)) return OMR_INVALID_ARGUMENT;
+        codecs = opt->codecs;
+    }
     std::string root(group_path);
     while (root.size() > 1 && root.back() == '/') root.pop_back();
     struct stat sb;
@@ -826,16 +960,16 @@ omr_status omr_zarr_image_open(const char* group_path, omr_zarr_image** out) {
         }
         if (r != Slurp::Ok) return OMR_INTERNAL;
         ArrayMeta m;
-        const omr_status st = parse_zarray(text, m);
+        const omr_status st = parse_zarray(text, codecs, m);
         if (st) return st;
         if (k == 0) {
             im->st = (int32_t)m.shape[0]; im->sc = (int32_t)m.shape[1]; im->sz = (int32_t)m.shape[2];
             im->pt = m.pt;
             im->bpp = bytes_per_pixel(m.pt);
             im->big = m.big;
-            im->zlib = m.zlib;
+            im->comp = m.comp;
             sep0 = m.sep;
-        } else if (m.pt != im->pt || m.big != im->big || m.zlib != im->zlib || m.sep != sep0 || m.shape[0] != im->st ||
+        } else if (m.pt != im->pt || m.big != im->big || m.comp != im->comp || m.sep != sep0 || m.shape[0] != im->st ||
                    m.shape[1] != im->sc || m.shape[2] != im->sz) {
             return OMR_INVALID_ARGUMENT;                 // levels that disagree
         }
@@ -860,7 +994,7 @@ omr_status omr_zarr_image_info(const omr_zarr_image* img, omr_zarr_info* info) {
     info->pixel_type = img->pt;
     info->big_endian = img->big;
     info->n_levels = (int32_t)img->levels.size();
-    info->compression = img->zlib;
+    info->compression = img->comp;
     info->chunk_width = L.cw;
     info->chunk_height = L.ch;
     info->dimension_separator = L.sep;

@@ -114,6 +114,13 @@ class ZarrInfo(ctypes.Structure):
         "chunk_width", "chunk_height", "dimension_separator")]
 
 
+ZARR_CODEC_ZLIB, ZARR_CODEC_BLOSC = 1, 2
+
+
+class ZarrOpenOptions(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("codecs", ctypes.c_uint32)]
+
+
 class Region(ctypes.Structure):
     _fields_ = [("x", ctypes.c_int32), ("y", ctypes.c_int32),
                 ("width", ctypes.c_int32), ("height", ctypes.c_int32)]
@@ -301,6 +308,10 @@ _SIGS = {
     "omr_inflate_batch_device": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
     "omr_zarr_image_read_regions_device": (_i32, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _i64]),
     "omr_render_zarr_tiles": (_i32, [_vp, _vp, _i32, _QD, _CB, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32]),
+    "omr_zarr_image_open_ex": (_i32, [ctypes.c_char_p, ctypes.POINTER(ZarrOpenOptions), ctypes.POINTER(_vp)]),
+    "omr_lz4_decode_host": (_i32, [_vp, _sz, _vp, _sz]),
+    "omr_blosc_decode_host": (_i32, [_vp, _sz, _vp, _sz]),
+    "omr_lz4_decode_batch_device": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
     "omr_render_shape_mask_png_batch": (_i32, [_vp, ctypes.POINTER(MaskJob), _i32, _vp, _sz, _vp, _vp, _vp]),
     "omr_split_html_color": (_i32, [ctypes.c_char_p, ctypes.POINTER(_i32)]),
     "omr_shape_mask_fill_color": (_i32, [_i32, _i32, ctypes.c_char_p, _vp]),

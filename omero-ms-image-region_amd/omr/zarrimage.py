@@ -5,7 +5,10 @@ The third backend of pixelsService.getPixelBuffer beside the ROMIO file (pixbuf.
 the tiled TIFF (tiffimage.TiffImage): a Zarr v2 directory as bioformats2raw writes it, one 5-D
 TCZYX array per resolution and one file per chunk.  Reads go through libomr.so: get_tile on the
 host (plain serial inflate), read_regions and render_tiles with the zlib chunks inflated on the GPU
-(omr_inflate.hip).
+(omr_inflate.hip).  Blosc chunks with LZ4 inside (K15, bioformats2raw's default) are read when the
+image is opened with codecs=("zlib", "blosc"): their streams are decoded on the GPU by
+omr_blosc.hip.  lz4_encode and blosc_encode are small pure-Python encoders for the tests and the
+probe, so that neither needs an outside library.
 """
 import ctypes
 import json
@@ -19,21 +22,124 @@ from ._lib import lib
 from .tiffimage import _NP_NAMES
 
 
+def lz4_encode(data):
+    """One LZ4 block of `data`: a small greedy encoder (a table of the last position of every four
+    bytes, longer steps over what does not compress).  As the format asks of an encoder, the last
+    five bytes are literals and no match starts within the last twelve."""
+    data = bytes(data)
+    n = len(data)
+    out = bytearray()
+
+    def sequence(lits, offset=0, mlen=0):
+        ll = len(lits)
+        ml = mlen - 4 if mlen else 0
+        out.append(min(ll, 15) << 4 | min(ml, 15))
+        if ll >= 15:
+            out.extend(b"\xff" * ((ll - 15) // 255))
+            out.append((ll - 15) % 255)
+        out.extend(lits)
+        if mlen:
+            out.extend(offset.to_bytes(2, "little"))
+            if ml >= 15:
+                out.extend(b"\xff" * ((ml - 15) // 255))
+                out.append((ml - 15) % 255)
+
+    anchor = i = 0
+    table = {}
+    misses = 0
+    while i + 12 <= n:
+        key = data[i:i + 4]
+        cand = table.get(key)
+        table[key] = i
+        if cand is None or i - cand > 65535:
+            misses += 1
+            i += 1 + (misses >> 5)
+            continue
+        misses = 0
+        m, top = 4, n - 5 - i                      # the match ends before the last five bytes
+        while m + 64 <= top and data[cand + m:cand + m + 64] == data[i + m:i + m + 64]:
+            m += 64
+        while m < top and data[cand + m] == data[i + m]:
+            m += 1
+        sequence(data[anchor:i], i - cand, m)
+        i += m
+        anchor = i
+    sequence(data[anchor:])
+    return bytes(out)
+
+
+def _shuffle(block, typesize):
+    q = len(block) // typesize
+    a = np.frombuffer(block, dtype=np.uint8)
+    return a[:q * typesize].reshape(q, typesize).T.tobytes() + block[q * typesize:]
+
+
+def blosc_encode(data, typesize, shuffle=1, blocksize=0, split=None, memcpy=False):
+    """`data` as one Blosc 1 chunk with LZ4 inside (the container as recalled, see omr.h): shuffle 0
+    or 1 (byte shuffle per block, flag 0x01); blocksize 0: one block of up to 256 KiB, a multiple of
+    typesize; split None or True: a block is typesize streams where the format's rule allows it,
+    False: flag 0x10 (do not split); a stream that does not compress is stored raw; memcpy: flag
+    0x02, the bytes follow the header as they are."""
+    data = bytes(data)
+    n = len(data)
+    assert 1 <= typesize <= 255 and shuffle in (0, 1) and n > 0
+    if blocksize <= 0:
+        blocksize = min(n, 256 << 10)
+        if blocksize > typesize:
+            blocksize -= blocksize % typesize
+    flags = 1 << 5 | (1 if shuffle else 0) | (0x10 if split is False else 0) | (2 if memcpy else 0)
+
+    def header(cbytes):
+        return bytes([2, 1, flags, typesize]) + b"".join(int(v).to_bytes(4, "little") for v in (n, blocksize, cbytes))
+
+    if memcpy:
+        return header(n + 16) + data
+    nblocks = (n + blocksize - 1) // blocksize
+    body, bstarts, at = bytearray(), [], 16 + 4 * nblocks
+    for b in range(nblocks):
+        block = data[b * blocksize:(b + 1) * blocksize]
+        leftover = len(block) < blocksize
+        if shuffle and typesize > 1:
+            block = _shuffle(block, typesize)
+        nsplits = typesize if (split is not False and typesize <= 16 and blocksize // typesize >= 128
+                               and not leftover) else 1
+        if nsplits > 1:
+            assert blocksize % typesize == 0, "a split block holds whole elements"
+        ne = len(block) // nsplits
+        bstarts.append(at + len(body))
+        for k in range(nsplits):
+            part = block[k * ne:(k + 1) * ne]
+            stream = lz4_encode(part)
+            if len(stream) >= ne:
+                stream = part                            # stored raw: csize == neblock
+            body += len(stream).to_bytes(4, "little") + stream
+    return header(at + len(body)) + b"".join(v.to_bytes(4, "little") for v in bstarts) + bytes(body)
+
+
 def write_zarr(path, planes, levels=(), chunk=(256, 256), byteorder="<", compressor="zlib", level=1, strategy=None,
-               dimension_separator="/", skip_zero_chunks=False, zarray_overrides=None):
+               dimension_separator="/", skip_zero_chunks=False, zarray_overrides=None, blosc=None):
     """Write a [t][c][z][y][x] array as the image group `path` of an OME-Zarr (Zarr v2, NGFF 0.4
     multiscales metadata): array "0" holds `planes`, arrays "1", "2", ... hold `levels` (arrays of
     the same [t][c][z] with their own [y][x]).  chunk = (w, h): chunks [1, 1, 1, h, w], edge chunks
     stored whole; byteorder "<" or ">"; compressor "zlib" (stdlib zlib at `level`, `strategy` one
     of zlib.Z_* or None for the default) or None; dimension_separator "/" (as bioformats2raw) or
     "."; skip_zero_chunks: an all-zero chunk is not written; zarray_overrides = {key: value}
-    replaces entries of every .zarray (to make groups a reader must reject)."""
+    replaces entries of every .zarray (to make groups a reader must reject).  compressor "blosc":
+    chunks written by blosc_encode with the arguments in `blosc` = {"shuffle", "blocksize", "split",
+    "memcpy", "typesize" (default: the sample size)}, and its "cname" (default "lz4") and "clevel"
+    (default 5) written to the .zarray beside them."""
     planes = np.asarray(planes)
     assert planes.ndim == 5, "planes must be [t][c][z][y][x]"
     arrays = [planes] + [np.asarray(lv) for lv in levels]
     for lv in arrays[1:]:
         assert lv.ndim == 5 and lv.shape[:3] == planes.shape[:3] and lv.dtype == planes.dtype
-    assert compressor in ("zlib", None) and dimension_separator in ("/", ".")
+    assert compressor in ("zlib", "blosc", None) and dimension_separator in ("/", ".")
+    bl = dict(blosc or {})
+    cmeta = {"id": "zlib", "level": level} if compressor == "zlib" else None
+    if compressor == "blosc":
+        cmeta = {"id": "blosc", "cname": bl.pop("cname", "lz4"), "clevel": bl.pop("clevel", 5),
+                 "shuffle": bl.get("shuffle", 1), "blocksize": bl.get("blocksize", 0)}
+        bl.setdefault("typesize", planes.dtype.itemsize)
     dt = planes.dtype
     fdt = dt.newbyteorder(byteorder) if dt.itemsize > 1 else dt
     dtype_name = ("|" if dt.itemsize == 1 else byteorder) + dt.kind + str(dt.itemsize)
@@ -52,7 +158,7 @@ def write_zarr(path, planes, levels=(), chunk=(256, 256), byteorder="<", compres
         adir = os.path.join(path, str(k))
         os.makedirs(adir, exist_ok=True)
         meta = {"zarr_format": 2, "shape": list(a.shape), "chunks": [1, 1, 1, ch, cw], "dtype": dtype_name,
-                "compressor": {"id": "zlib", "level": level} if compressor else None, "fill_value": 0, "order": "C",
+                "compressor": cmeta, "fill_value": 0, "order": "C",
                 "filters": None, "dimension_separator": dimension_separator}
         meta.update(zarray_overrides or {})
         with open(os.path.join(adir, ".zarray"), "w") as f:
@@ -69,7 +175,9 @@ def write_zarr(path, planes, levels=(), chunk=(256, 256), byteorder="<", compres
                             full = np.zeros((ch, cw), dtype=fdt)
                             full[:part.shape[0], :part.shape[1]] = part
                             raw = full.tobytes()
-                            if compressor:
+                            if compressor == "blosc":
+                                raw = blosc_encode(raw, **bl)
+                            elif compressor:
                                 co = zlib.compressobj(level, zlib.DEFLATED, 15, 8,
                                                       zlib.Z_DEFAULT_STRATEGY if strategy is None else strategy)
                                 raw = co.compress(raw) + co.flush()
@@ -84,9 +192,22 @@ class ZarrImage:
     """An open OME-Zarr image group (omr_zarr_image): `path` is the image (series) group, for
     instance image.zarr/0.  Z, C and T come from the array shape; OME-XML is not read."""
 
-    def __init__(self, path):
+    CODECS = {"zlib": _lib.ZARR_CODEC_ZLIB, "blosc": _lib.ZARR_CODEC_BLOSC}
+
+    def __init__(self, path, codecs=("zlib",)):
+        """codecs: the chunk compressors accepted, ("zlib",) as omr_zarr_image_open or ("zlib",
+        "blosc") (omr_zarr_image_open_ex); uncompressed groups always open."""
         h = ctypes.c_void_p()
-        st = lib.omr_zarr_image_open(str(path).encode(), ctypes.byref(h))
+        if tuple(codecs) == ("zlib",):
+            st = lib.omr_zarr_image_open(str(path).encode(), ctypes.byref(h))
+        else:
+            mask = 0
+            for name in codecs:
+                if name not in self.CODECS:
+                    raise _lib.OmrError(_lib.INVALID_ARGUMENT, f"unknown Zarr codec {name!r}")
+                mask |= self.CODECS[name]
+            opt = _lib.ZarrOpenOptions(ctypes.sizeof(_lib.ZarrOpenOptions), mask)
+            st = lib.omr_zarr_image_open_ex(str(path).encode(), ctypes.byref(opt), ctypes.byref(h))
         if st != _lib.OK:
             raise _lib.OmrError(st, f"cannot open Zarr image {path}")
         self.h = h
@@ -179,3 +300,21 @@ def inflate_host(stream, expected):
     out = np.zeros(max(int(expected), 1), dtype=np.uint8)
     _lib.check(lib.omr_inflate_host(src.ctypes.data if src.size else None, src.size, out.ctypes.data, int(expected)))
     return out[:int(expected)].tobytes()
+
+
+def _decode_host(fn, stream, expected):
+    src = np.frombuffer(bytes(stream), dtype=np.uint8)
+    out = np.zeros(max(int(expected), 1), dtype=np.uint8)
+    _lib.check(fn(src.ctypes.data if src.size else None, src.size, out.ctypes.data, int(expected)))
+    return out[:int(expected)].tobytes()
+
+
+def lz4_decode_host(stream, expected):
+    """The host LZ4 decoder alone (omr_lz4_decode_host): one LZ4 block into exactly `expected`
+    bytes, or OmrError(INTERNAL)."""
+    return _decode_host(lib.omr_lz4_decode_host, stream, expected)
+
+
+def blosc_decode_host(chunk, expected):
+    """One Blosc 1 chunk into exactly `expected` bytes (omr_blosc_decode_host), or OmrError(INTERNAL)."""
+    return _decode_host(lib.omr_blosc_decode_host, chunk, expected)
