@@ -1,7 +1,9 @@
 """The LZ4 blocks and Blosc chunks of the K15 tests (test_blosc_read_host.py, test_blosc_read_gpu.py):
 golden streams of a real encoder (tests/golden/lz4_blocks.npz, made by tools/make_lz4_golden.py with
 the system's liblz4), streams of the product's own encoders, and crafted ones written sequence by
-sequence.  Made once and shared; nothing here needs a GPU."""
+sequence: the length and offset edges, the edges of K15a's emit stage (edge_streams) and a seeded
+sweep (random_lz4_streams), each checked by lz4_decode_py where it is made.  Made once and shared;
+nothing here needs a GPU."""
 import functools
 import os
 
@@ -115,7 +117,274 @@ def crafted_streams():
         # the size is what the sequences say: decode with a generous limit first
         total = len(lz4_decode_py_unbounded(s))
         res.append((name, lz4_decode_py(s, total), s))
+    res += edge_streams() + [random_lz4_streams(seed) for seed in range(16)]
+    assert len({r[0] for r in res}) == len(res)
     return res
+
+
+class Lz4Script:
+    """Sequences and the data they stand for: the test chooses the sequences, the data is their
+    replay.  A round is 64 sequences, as the device decoder collects them; `first` is where the
+    round's first match is stored, `pos` where the last sequence's literals are, `ip` the stream's
+    length so far."""
+
+    def __init__(self, seed):
+        self.rng = np.random.default_rng(seed)
+        self.out = bytearray()
+        self.seqs = []
+        self.first = self.pos = self.ip = 0
+
+    def seq(self, nlit, mlen, dist=None, start=None):
+        """nlit new literals, then a match of mlen bytes `dist` back, or from output byte `start`."""
+        self.pos = len(self.out)
+        lits = self.rng.integers(0, 256, nlit, dtype=np.uint8).tobytes()
+        self.out += lits
+        mpos = len(self.out)
+        if len(self.seqs) % 64 == 0:
+            self.first = mpos
+        if dist is None:
+            dist = mpos - start
+        assert 1 <= dist <= min(mpos, 65535) and mlen >= 4, (nlit, mlen, dist, mpos)
+        for _ in range(mlen):
+            self.out.append(self.out[-dist])
+        self.seqs.append((lits, dist, mlen))
+        self.ip += 1 + len(_length(15, nlit)) + nlit + 2 + len(_length(15, mlen - 4))
+        return self
+
+    def to_round(self, k):
+        """Short sequences until the next one is sequence k of its round."""
+        while len(self.seqs) % 64 != k:
+            self.seq(1, 4, 1 + len(self.seqs) % 3)
+        return self
+
+    def end(self, nlit=0):
+        lits = self.rng.integers(0, 256, nlit, dtype=np.uint8).tobytes()
+        data, stream = bytes(self.out + lits), lz4_sequences(self.seqs + [(lits, 0, 0)])
+        assert len(stream) == self.ip + 1 + len(_length(15, nlit)) + nlit
+        assert lz4_decode_py(stream, len(data)) == data
+        return data, stream
+
+
+@functools.lru_cache(maxsize=None)
+def edge_streams():
+    """[(name, data, stream)]: the periods, thresholds, alignments and round borders of K15a's emit
+    stage, each stream the replay of its own sequences."""
+    out = []
+
+    def add(name, s, tail=0):
+        data, stream = s.end(tail)
+        out.append((name, data, stream))
+
+    # overlapped matches with real periods: 2 dist + 1 bytes, and long ones whose lanes step their phase
+    # through four and more turns, free (the source is the sequence's own literals) and not, stored
+    # at each of the four alignments
+    for dist in (8, 9, 31, 63, 64, 65, 100, 127, 128, 129, 255, 256, 257, 300):
+        s = Lz4Script(300 + dist)
+        for a in range(4):
+            for nlit, mlen in ((dist, 2 * dist + 1), (1, 1100 + 3 * a + dist % 7), (dist, 1150 + dist % 5)):
+                s.seq(nlit + (a - len(s.out) - nlit) % 4, mlen, dist)
+                assert (len(s.out) - mlen) % 4 == a
+        add(f"period {dist}, short and long", s, dist % 4)
+
+    s = Lz4Script(320)
+    for mlen in (4, 5, 32, 33, 64, 65, 257):
+        for dist in (mlen - 1, mlen, mlen + 1):
+            s.seq(dist + 2, mlen, dist)                    # free: it reads its own sequence's literals
+            s.seq(0, mlen, dist)                           # not free: it reads the match before it
+            s.seq(1, mlen, dist)
+    add("distance at, below and above the match length", s, 1)
+
+    # the sizes at which a lane hands a copy to the wave: literal runs of 16 and 17, matches of 32 and 33
+    s = Lz4Script(321).seq(40, 8, 40)
+    for n in (16, 17):
+        s.seq(n, 4, 3).seq(n, 32, 1).seq(n, 33, n)
+    s.seq(270, 6, 270).seq(15, 7, 285)                     # extension bytes 255, 0 and 0
+    for mlen in (32, 33):
+        s.seq(mlen + 3, mlen, mlen + 3)                    # free, from its own literals
+        s.seq(0, mlen, start=s.first - mlen)               # free, it ends where the round's first match begins
+        s.seq(2, mlen, mlen + 1)                           # not free, from the match before it
+        s.seq(0, mlen, 5)                                  # not free and overlapped
+    add("copies of 16, 17, 32 and 33 bytes", s, 17)
+
+    # wave_copy: every head, tail and source shift.  Literal runs stored at da and read at sa (mod 4): a
+    # spacer sequence of a literals and a match of m bytes moves the two positions apart
+    for n in range(17, 30):
+        s = Lz4Script(330 + n).seq(8, 4, 8)
+        for da in range(4):
+            for sa in range(4):
+                a, m = [(a, m) for a in range(4) for m in range(4, 8)
+                        if (len(s.out) + a + m) % 4 == da and (s.ip + 3 + a + 2) % 4 == sa][0]
+                s.seq(a, m, 1 + (da + sa) % 5)
+                assert len(s.out) % 4 == da and (s.ip + 2) % 4 == sa
+                s.seq(n, 4, 2)
+        add(f"literal runs of {n} at every alignment", s, n)
+    for mlen in range(33, 46):
+        s = Lz4Script(350 + mlen).seq(64, 4, 64)
+        for da in range(4):
+            for sa in range(4):
+                a = (da - len(s.out)) % 4
+                mpos = len(s.out) + a
+                s.seq(a, mlen, mlen + (mpos - sa - mlen) % 4)
+                assert mpos % 4 == da and (mpos - s.seqs[-1][1]) % 4 == sa and s.seqs[-1][1] >= mlen
+        add(f"matches of {mlen} at every alignment", s, 2)
+
+    # the round's border: the closing sequence as the 63rd, 64th and 1st of a round, with literals and bare
+    for total in (63, 64, 65, 128, 129):
+        for tail in (0, 5):
+            s = Lz4Script(370 + total)
+            for k in range(total - 1):
+                s.seq(k % 3 + 4 * (k == 0), 4 + k % 20, 1 + k % 4)
+            assert len(s.seqs) + 1 == total
+            add(f"{total} sequences, {tail} closing literals", s, tail)
+
+    # the rule of the free match at its edges, for a match a lane copies and one the wave copies
+    s = Lz4Script(380)
+
+    def scene():
+        return s.to_round(0).seq(40, 8, 40).seq(6, 4, 2)
+
+    for mlen in (8, 40):
+        for e in (0, 1):                                   # the source ends at the round's first match, and a byte above
+            scene().seq(5, mlen, start=s.first + e - mlen)
+        for e in (0, 1):                                   # it starts at its own literals, and a byte below
+            scene()
+            s.seq(mlen + 2, mlen, start=len(s.out) - e)
+        scene()                                            # wholly in the literals of an earlier sequence
+        p = len(s.out)
+        s.seq(mlen + 4, 4, 1).seq(1, mlen, start=p + 1)
+        scene()                                            # across a free match that a lane copied
+        p = len(s.out)
+        s.seq(6, 8, 6).seq(3, mlen, start=p + 2)
+        scene().seq(3, 12, 5)                              # X, not free; then sources about its two ends
+        x1 = len(s.out)
+        x0 = x1 - 12
+        s.seq(mlen, mlen, start=x1 - 1)                    # X's last byte and the literals above it
+        s.seq(4, 4, start=x0 - 4).seq(4, mlen, start=x0 - 3).seq(5, mlen, start=x1 - 12)
+        s.seq(3, mlen, start=x0 - 3 - 8)
+    add("free and dependent matches at the rule's edges", s, 3)
+
+    # the 256-byte window over the stream: tokens, offsets and the extension bytes of both lengths at every
+    # phase of the stream, so that each falls on both sides of a reload at each source alignment
+    for phase in range(33):                                # the pattern below repeats every 33 bytes
+        s = Lz4Script(400 + phase).seq(8 + phase, 4, 8)
+        for k in range(120):                               # no long literal run: the windows follow one another
+            if k % 5 == 2:
+                s.seq(0, 4 + 15 + 255 + 3, 1 + k % 7)      # extension bytes 255, 3
+            elif k % 5 == 4:
+                s.seq(15 + k % 3, 5, 6)                    # one extension byte
+            else:
+                s.seq(0, 4 + k % 11, 1 + k % 9)
+        assert s.ip > 700
+        add(f"window reloads, phase {phase}", s, phase % 3)
+    return out
+
+
+def lz4_census(stream):
+    """What a good LZ4 block holds, by a plain parse of its own (nothing of the product): a dict of
+      sequences   their number, the closing one included
+      closing     (the closing sequence's index in its round of 64, its literals)
+      matches     [(mlen, dist, mpos, free, start - pos, send - first)] with `free` by K15a's rule
+                  (send <= first or start >= pos; first: where the round's first match is stored)
+      sources     per match, what its source [start, send) touches of its own round, a set of
+                  "earlier rounds", "literals" (of an earlier sequence), "own literals", "free lane
+                  match" (free, of at most 32 bytes), "free wave match", "dependent match", and for
+                  a dependent match it crosses into from below or leaves at the top, "dependent
+                  match, its first byte" and "dependent match, its last byte"
+      literals    {(run length, store position mod 4, position in the stream mod 4)}
+      reloads     {mis: kinds of byte ("token", "lit ext", "offset 0", "offset 1", "match ext") on
+                  which a 256-byte window over the stream's dwords, `mis` bytes behind a dword
+                  boundary, is loaded anew}."""
+    s, ip, out = bytes(stream), 0, 0
+    reads, matches, literals, n, first = [], [], set(), 0, 0
+    sources, spans, round_start = [], [], 0
+
+    def ext(v, kind):
+        nonlocal ip
+        if v == 15:
+            while True:
+                reads.append((ip, kind))
+                v += s[ip]
+                ip += 1
+                if s[ip - 1] != 255:
+                    break
+        return v
+
+    while True:
+        reads.append((ip, "token"))
+        token = s[ip]
+        ip += 1
+        lit = ext(token >> 4, "lit ext")
+        literals.add((lit, out % 4, ip % 4))
+        if n % 64 == 0:
+            spans, round_start = [], out
+        pos, out, ip = out, out + lit, ip + lit
+        n += 1
+        if ip == len(s):
+            break
+        reads += [(ip, "offset 0"), (ip + 1, "offset 1")]
+        dist = s[ip] | s[ip + 1] << 8
+        ip += 2
+        mlen = ext(token & 15, "match ext") + 4
+        if n % 64 == 1:
+            first = out
+        start = out - dist
+        send = start + min(mlen, dist)
+        free = send <= first or start >= pos
+        matches.append((mlen, dist, out, free, start - pos, send - first))
+        seen = {"earlier rounds"} if start < round_start else set()
+        for lo, hi, what in spans + [(pos, out, "own literals")]:
+            if start < hi and lo < send and lo < hi:
+                seen.add(what)
+                if what == "dependent match":
+                    seen |= {what + ", its first byte"} if start < lo else set()
+                    seen |= {what + ", its last byte"} if hi < send else set()
+        sources.append(seen)
+        spans += [(pos, out, "literals"), (out, out + mlen, "dependent match" if not free else
+                                           "free lane match" if mlen <= 32 else "free wave match")]
+        out += mlen
+    reloads = {}
+    for mis in range(4):
+        lo, kinds = None, set()
+        for at, kind in reads:
+            k = (mis + at) >> 2
+            if lo is None or k < lo or k - lo >= 64:
+                if lo is not None:
+                    kinds.add(kind)
+                lo = k
+        reloads[mis] = kinds
+    return {"sequences": n, "closing": ((n - 1) % 64, lit), "matches": matches, "sources": sources, "literals": literals,
+            "reloads": reloads}
+
+
+def random_lz4_streams(seed):
+    """(name, data, stream): 100 .. 400 random sequences; offsets lean to 1 .. 70, to sources that
+    begin about the round's first match, and to the largest there is."""
+    s = Lz4Script(2000 + seed)
+    rng = s.rng
+    n = int(rng.integers(100, 401))
+    s.seq(int(rng.integers(1, 80)), 4, 1)
+    for _ in range(n - 2):
+        nlit = int(rng.choice([0, 1, 15, 16, 17, int(rng.integers(0, 8)), int(rng.integers(0, 8)), int(rng.integers(0, 40))]))
+        if rng.random() < 0.04:
+            nlit = 270
+        mlen = int(rng.choice([4, 19, 32, 33, 64, 65, int(rng.integers(4, 12)), int(rng.integers(4, 12)), int(rng.integers(4, 80))]))
+        if rng.random() < 0.04:
+            mlen = 274
+        mpos = len(s.out) + nlit
+        first = mpos if len(s.seqs) % 64 == 0 else s.first
+        how, have = rng.random(), min(mpos, 65535)
+        if how < 0.4:
+            dist = int(rng.integers(1, 71))
+        elif how < 0.7:
+            dist = mpos - first - int(rng.integers(-mlen - 2, 40))
+        elif how < 0.85:
+            dist = have - int(rng.integers(0, 3))
+        else:
+            dist = int(rng.integers(1, have + 1))
+        s.seq(nlit, mlen, max(1, min(dist, have)))
+    data, stream = s.end(int(rng.choice([0, 1, 16, 17, 300])))
+    assert len(s.seqs) + 1 == n
+    return f"sweep {seed}", data, stream
 
 
 def lz4_decode_py_unbounded(stream):

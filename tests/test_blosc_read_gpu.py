@@ -13,7 +13,8 @@ import omr
 from omr import _lib
 from omr.context import make_qdef
 from omr.synthetic import c2_channels
-from blosc_streams import bad_streams, chunk_pixels, crafted_streams, golden_streams, layout_image, mixed_streams
+from blosc_streams import (bad_streams, chunk_pixels, crafted_streams, edge_streams, golden_streams, layout_image,
+                           mixed_streams)
 
 pytestmark = pytest.mark.gpu
 
@@ -24,20 +25,24 @@ TYPES = {"int8": _lib.PIXELS_INT8, "uint8": _lib.PIXELS_UINT8, "int16": _lib.PIX
          "float32": _lib.PIXELS_FLOAT, "float64": _lib.PIXELS_DOUBLE}
 
 
-def decode_batch(ctx, streams, expected):
+def decode_batch(ctx, streams, expected, mis=None):
     """Streams through K15a in one call: [(status, bytes)], after checking every slot's canary.
-    Streams and slots are packed byte to byte, so they begin at every alignment."""
+    Streams and slots are packed byte to byte, so they begin at every alignment; with `mis` every
+    stream begins `mis` bytes behind a dword boundary."""
     import torch
     n = len(streams)
-    src_off, pos = [], 0
+    src_off, pos, gaps = [], 0, []
     for s in streams:
+        gaps.append(b"" if mis is None else b"\xEE" * ((mis - pos) % 4))
+        pos += len(gaps[-1])
         src_off.append(pos)
         pos += len(s)
     dst_off, dpos = [], 0
     for e in expected:
         dst_off.append(dpos)
         dpos += e + 16
-    src = torch.from_numpy(np.frombuffer(b"".join(streams) + b"\0", dtype=np.uint8).copy()).cuda()
+    src = torch.from_numpy(np.frombuffer(b"".join(g + s for g, s in zip(gaps, streams)) + b"\0", dtype=np.uint8).copy()).cuda()
+    assert src.data_ptr() % 4 == 0
     dst = torch.full((dpos,), CANARY, dtype=torch.uint8, device="cuda")
     offs = torch.tensor(src_off, dtype=torch.int64, device="cuda")
     lens = torch.tensor([len(s) for s in streams], dtype=torch.int32, device="cuda")
@@ -58,8 +63,8 @@ def decode_batch(ctx, streams, expected):
     return res
 
 
-def check_equal(ctx, datas, streams):
-    res = decode_batch(ctx, streams, [len(d) for d in datas])
+def check_equal(ctx, datas, streams, mis=None):
+    res = decode_batch(ctx, streams, [len(d) for d in datas], mis)
     for i, ((st, got), d, s) in enumerate(zip(res, datas, streams)):
         assert st == _lib.OK, (i, st)
         assert got == d, f"stream {i} ({len(d)} bytes) differs"
@@ -78,6 +83,14 @@ def test_lz4_stream(ctx, k):
 def test_lz4_all_good_streams_at_odd_alignments(ctx):
     datas, streams = [g[1] for g in GOOD], [g[2] for g in GOOD]
     check_equal(ctx, datas + datas[::-1], streams + streams[::-1])
+
+
+@pytest.mark.parametrize("mis", [0, 1, 2, 3])
+def test_lz4_edge_streams_at_each_source_alignment(ctx, mis):
+    """Every edge stream `mis` bytes behind a dword boundary: the 256-byte window counts from the
+    aligned dword below the stream, so its reloads fall on other bytes at each, and so do the
+    source dwords of the literal copies."""
+    check_equal(ctx, [e[1] for e in edge_streams()], [e[2] for e in edge_streams()], mis)
 
 
 def test_lz4_300_mixed_streams(ctx):

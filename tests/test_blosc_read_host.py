@@ -12,8 +12,8 @@ import pytest
 
 import omr
 from omr import _lib
-from blosc_streams import (bad_streams, chunk_pixels, crafted_streams, golden_streams, layout_image, lz4_decode_py,
-                           mixed_streams)
+from blosc_streams import (bad_streams, chunk_pixels, crafted_streams, edge_streams, golden_streams, layout_image,
+                           lz4_census, lz4_decode_py, mixed_streams)
 
 TYPES = {"int8": _lib.PIXELS_INT8, "uint8": _lib.PIXELS_UINT8, "int16": _lib.PIXELS_INT16,
          "uint16": _lib.PIXELS_UINT16, "int32": _lib.PIXELS_INT32, "uint32": _lib.PIXELS_UINT32,
@@ -71,6 +71,57 @@ def test_lz4_decode_host_against_liblz4_when_present():
             buf = ctypes.create_string_buffer(cap)
             m = lz.LZ4_compress_default(d, buf, n, cap)
             assert omr.lz4_decode_host(buf.raw[:m], n) == d
+
+
+def test_census_of_the_edge_streams():
+    """Conditions on the inputs, judged by lz4_census alone: the edge streams hold every case they
+    were written for.  A match is long when its body is more than 64 dwords, so that a lane steps
+    its phase more than once; a copy's alignments are counted from the stream's and the slot's
+    first bytes, and the device tests place both at every alignment."""
+    parts = {name: lz4_census(stream) for name, data, stream in edge_streams()}
+    matches = [m for c in parts.values() for m in c["matches"]]
+    periods = (8, 9, 31, 63, 64, 65, 100, 127, 128, 129, 255, 256, 257, 300)
+    for free in (True, False):
+        long = {(dist, mpos % 4) for mlen, dist, mpos, f, _, _ in matches if mlen >= 1100 and f == free}
+        assert long >= {(d, a) for d in periods for a in range(4)}, free
+    assert {(dist, mpos % 4) for mlen, dist, mpos, _, _, _ in matches if mlen == 2 * dist + 1} >= {(d, a) for d in periods for a in range(4)}
+    for mlen in (4, 5, 32, 33, 64, 65, 257):               # the switch between the plain copy and the period
+        for free in (True, False):
+            assert {m[1] - mlen for m in matches if m[0] == mlen and m[3] == free} >= {-1, 0, 1}, (mlen, free)
+    # the sizes at which a lane hands over to the wave, and wave_copy's grid
+    literals = set().union(*(c["literals"] for c in parts.values()))
+    assert {n for n, _, _ in literals} >= {0, 1, 15, 16, 17, 270}
+    assert literals >= {(n, da, sa) for n in range(17, 30) for da in range(4) for sa in range(4)}
+    plain = {(mlen, mpos % 4, (mpos - dist) % 4) for mlen, dist, mpos, _, _, _ in matches if dist >= mlen}
+    assert plain >= {(n, da, sa) for n in range(33, 46) for da in range(4) for sa in range(4)}
+    for mlen in (32, 33):
+        assert {m[3] for m in matches if m[0] == mlen} == {True, False}, mlen
+    # the round's border
+    assert {c["sequences"] for c in parts.values()} >= {63, 64, 65, 128, 129}
+    closing = {(k, min(lits, 1)) for k, lits in (c["closing"] for c in parts.values())}
+    assert closing >= {(62, 0), (62, 1), (63, 0), (63, 1), (0, 0), (0, 1)}
+    # the rule of the free match, from both sides of both edges, for lane-sized and wave-sized matches
+    edges = parts["free and dependent matches at the rule's edges"]["matches"]
+    for size in (8, 40):
+        mine = [m for m in edges if m[0] == size]
+        assert any(f and over == 0 and below < 0 for _, _, _, f, below, over in mine)          # ends at `first`
+        assert any(not f and over == 1 and below < 0 for _, _, _, f, below, over in mine)      # a byte above
+        assert any(f and below == 0 and over > 0 for _, _, _, f, below, over in mine)          # starts at `pos`
+        assert any(not f and below == -1 and over > 0 for _, _, _, f, below, over in mine)     # a byte below
+        # and what a dependent match reads: an earlier sequence's literals alone, literals and a match that a
+        # lane copied, a dependent match before it from below and from above
+        reads = [s for m, s in zip(edges, parts["free and dependent matches at the rule's edges"]["sources"])
+                 if m[0] == size and not m[3]]
+        assert {"literals"} in reads
+        assert any(s >= {"literals", "free lane match"} and "dependent match" not in s for s in reads)
+        assert any(s >= {"literals", "dependent match, its first byte"} for s in reads)
+        assert any("dependent match, its last byte" in s and "dependent match, its first byte" not in s for s in reads)
+    # the window over the stream: every kind of byte is the first of a reload at every alignment
+    for mis in range(4):
+        kinds = set().union(*(c["reloads"][mis] for name, c in parts.items() if name.startswith("window reloads")))
+        assert kinds == {"token", "lit ext", "offset 0", "offset 1", "match ext"}, (mis, kinds)
+    sweep = [lz4_census(s) for name, _, s in crafted_streams() if name.startswith("sweep ")]
+    assert len(sweep) == 16 and all(100 <= c["sequences"] <= 400 for c in sweep)
 
 
 def test_lz4_mixed_streams_host():

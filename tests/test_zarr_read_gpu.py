@@ -12,7 +12,7 @@ import omr
 from omr import _lib
 from omr.context import make_qdef
 from omr.synthetic import c2_channels
-from zarr_streams import bad_streams, deflate, good_streams, mixed_streams
+from zarr_streams import bad_streams, deflate, good_streams, mixed_streams, rare_streams, sweep_streams
 
 pytestmark = pytest.mark.gpu
 
@@ -22,19 +22,23 @@ TYPES = {"int8": _lib.PIXELS_INT8, "uint8": _lib.PIXELS_UINT8, "int16": _lib.PIX
          "float32": _lib.PIXELS_FLOAT, "float64": _lib.PIXELS_DOUBLE}
 
 
-def decode_batch(ctx, streams, expected):
-    """Streams through K14a in one call: [(status, bytes)], after checking every slot's canary."""
+def decode_batch(ctx, streams, expected, mis=None):
+    """Streams through K14a in one call: [(status, bytes)], after checking every slot's canary.
+    Streams are packed byte to byte, or with `mis` each `mis` bytes behind a dword boundary."""
     import torch
     n = len(streams)
-    src_off, pos = [], 0
+    src_off, pos, gaps = [], 0, []
     for s in streams:
+        gaps.append(b"" if mis is None else b"\xEE" * ((mis - pos) % 4))
+        pos += len(gaps[-1])
         src_off.append(pos)
         pos += len(s)
     dst_off, dpos = [], 0
     for e in expected:
         dst_off.append(dpos)
         dpos += e + 16
-    src = torch.from_numpy(np.frombuffer(b"".join(streams) + b"\0", dtype=np.uint8).copy()).cuda()
+    src = torch.from_numpy(np.frombuffer(b"".join(g + s for g, s in zip(gaps, streams)) + b"\0", dtype=np.uint8).copy()).cuda()
+    assert src.data_ptr() % 4 == 0
     dst = torch.full((dpos,), CANARY, dtype=torch.uint8, device="cuda")
     offs = torch.tensor(src_off, dtype=torch.int64, device="cuda")
     lens = torch.tensor([len(s) for s in streams], dtype=torch.int32, device="cuda")
@@ -55,8 +59,8 @@ def decode_batch(ctx, streams, expected):
     return res
 
 
-def check_equal(ctx, datas, streams):
-    res = decode_batch(ctx, streams, [len(d) for d in datas])
+def check_equal(ctx, datas, streams, mis=None):
+    res = decode_batch(ctx, streams, [len(d) for d in datas], mis)
     for i, ((st, got), d, s) in enumerate(zip(res, datas, streams)):
         assert zlib.decompress(s) == d
         assert st == _lib.OK, (i, st)
@@ -77,6 +81,25 @@ def test_inflate_empty_output(ctx):
 def test_inflate_300_mixed_streams(ctx):
     datas, streams = zip(*mixed_streams())
     check_equal(ctx, list(datas), list(streams))
+
+
+@pytest.mark.parametrize("k", range(len(rare_streams())), ids=[r[0] for r in rare_streams()])
+def test_inflate_rare_stream(ctx, k):
+    """What RFC 1951 allows and the stdlib compressor never writes, stream by stream."""
+    name, data, stream = rare_streams()[k]
+    check_equal(ctx, [data], [stream])
+
+
+def test_inflate_rare_streams_and_sweep_in_one_call(ctx):
+    both = rare_streams() + sweep_streams()
+    check_equal(ctx, [b[1] for b in both], [b[2] for b in both])
+
+
+@pytest.mark.parametrize("mis", [1, 2, 3])
+def test_inflate_rare_streams_misaligned(ctx, mis):
+    """Every rare stream `mis` bytes behind a dword boundary: the bit reader's window and the seek
+    behind a stored block count from the aligned dword below the stream."""
+    check_equal(ctx, [r[1] for r in rare_streams()], [r[2] for r in rare_streams()], mis)
 
 
 def test_inflate_malformed_between_good(ctx):

@@ -1,6 +1,8 @@
 """OME-Zarr pixel data on the host (K14): the image model (omr_zarr_image_open, its JSON reader),
 the host route (ZarrImage.get_tile) against numpy, the rejections and corrupt inputs with their
-status codes, and omr_inflate_host against the stdlib zlib.  No GPU."""
+status codes, and omr_inflate_host against the stdlib zlib: on the stdlib compressor's streams, and on
+the forms of RFC 1951 that it never writes (zarr_streams.rare_streams, the seeded sweep), whose
+census is asserted here so that the list cannot lose a case unnoticed.  No GPU."""
 import json
 import os
 import zlib
@@ -10,7 +12,8 @@ import pytest
 
 import omr
 from omr import _lib
-from zarr_streams import bad_streams, deflate, good_streams, mixed_streams
+from zarr_streams import (DEXT, LEXT, bad_streams, deflate, deflate_census, good_streams, merge_census, mixed_streams,
+                          rare_streams, sweep_streams)
 
 TYPES = {"int8": _lib.PIXELS_INT8, "uint8": _lib.PIXELS_UINT8, "int16": _lib.PIXELS_INT16,
          "uint16": _lib.PIXELS_UINT16, "int32": _lib.PIXELS_INT32, "uint32": _lib.PIXELS_UINT32,
@@ -245,3 +248,62 @@ def test_inflate_host_equals_zlib():
         assert omr.inflate_host(stream, len(data)) == data
     assert omr.inflate_host(deflate(b""), 0) == b""
     assert omr.inflate_host(deflate(b"abc") + b"trailing", 3) == b"abc"       # bytes behind the Adler-32 are not read
+
+
+RARE = rare_streams()
+
+
+@pytest.mark.parametrize("k", range(len(RARE)), ids=[r[0] for r in RARE])
+def test_inflate_host_rare_stream(k):
+    name, data, stream = RARE[k]
+    assert zlib.decompress(stream) == data                 # the reference, as where the stream was made
+    assert omr.inflate_host(stream, len(data)) == data
+    for expected in (len(data) + 1, len(data) - 1):
+        with pytest.raises(omr.OmrError) as e:
+            omr.inflate_host(stream, expected)
+        assert e.value.status == _lib.INTERNAL
+
+
+def test_inflate_host_sweep():
+    assert len(sweep_streams()) == 16
+    for name, data, stream in sweep_streams():
+        assert zlib.decompress(stream) == data and 200 <= len(data) <= 72000, name
+        assert omr.inflate_host(stream, len(data)) == data, name
+
+
+def test_census_of_the_rare_streams():
+    """Conditions on the inputs, judged by the census alone (deflate_census: a plain inflater of its
+    own): the rare streams and the sweep hold every form they were written for."""
+    parts = {name: deflate_census(stream) for name, data, stream in RARE + sweep_streams()}
+    for name, data, stream in RARE + sweep_streams():
+        assert parts[name]["data"] == data, name           # the census reads the streams as zlib does
+    c = merge_census(parts.values())
+    assert set(c["blocks"]) == {0, 1, 2}
+    for sym in range(257, 286):                            # every symbol, its extra bits all zeros and all ones
+        top = (1 << LEXT[sym - 257]) - 1
+        assert c["length_symbols"].get(sym, set()) >= {0, top if sym != 284 else 30}, sym
+    assert 31 not in c["length_symbols"][284]              # 258 is symbol 285
+    for sym in range(30):
+        assert c["distance_symbols"].get(sym, set()) >= {0, (1 << DEXT[sym]) - 1}, sym
+    for l in range(1, 16):
+        assert c["litlen_bits"].get(l, 0) > 0 and c["dist_bits"].get(l, 0) > 0, l
+    assert c["codelen_bits"].get(7, 0) > 0 and set(c["codelen_bits"]) == set(range(1, 8))
+    assert c["hclen"] >= {5, 6, 19}
+    assert c["crossing_repeats"] == {16, 17, 18}
+    assert c["distance_sets"] == {"empty", "single"}
+    assert c["overlaps"] >= set(range(1, 71)) | {127, 128, 129, 255, 256, 257}
+    # what single streams were written for
+    chain = parts["litlen chain 1..15, HCLEN 19"]
+    assert set(chain["litlen_bits"]) == set(range(1, 16)) and chain["hclen"] == {19} and chain["codelen_bits"].get(7, 0) > 0
+    deep = parts["every match symbol, deep codes"]
+    assert deep["litlen_bits"][15] >= 150 and set(deep["dist_bits"]) == set(range(2, 16))
+    assert set(deep["length_symbols"]) == set(range(257, 286)) and set(deep["distance_symbols"]) == set(range(30))
+    assert set(parts["distance chain 1..15"]["dist_bits"]) == set(range(1, 16))
+    assert parts["HCLEN 6"]["hclen"] == {6} and set(parts["HCLEN 6"]["litlen_bits"]) <= {7, 8}
+    for sym in (16, 17, 18):
+        assert parts[f"repeat {sym} over the border"]["crossing_repeats"] == {sym}
+    assert parts["a single distance code of one bit"]["distance_sets"] == {"single"}
+    assert parts["a single distance code of one bit"]["dist_bits"] == {1: 100}
+    assert 16 in parts["repeat 16 of the last literal/length length over the border"]["repeats_at_hlit"]
+    assert not parts["repeat 16 of the last literal/length length over the border"]["crossing_repeats"]
+    assert parts["stored blocks at every bit phase"]["blocks"][0] == 8
