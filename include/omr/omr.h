@@ -127,7 +127,9 @@ void*       omr_ctx_get_stream(omr_ctx* ctx);
  * omr_encode_png_gray_batch_device; 30 = LZW decode and 31 = TIFF place:
  * omr_tiff_image_read_regions_device; 32 = zlib inflate: omr_inflate_batch_device and, with 31,
  * omr_zarr_image_read_regions_device; 33 = LZ4 decode: omr_lz4_decode_batch_device and, with 34 =
- * Blosc place, omr_zarr_image_read_regions_device on a Blosc image).
+ * Blosc place, omr_zarr_image_read_regions_device on a Blosc image; 35 = Zstandard decode:
+ * omr_zstd_decode_batch_device and, with 34 or 31, omr_zarr_image_read_regions_device on a
+ * Blosc-Zstd or zstd image).
  */
 omr_status  omr_ctx_enable_kernel_timing(omr_ctx* ctx, int32_t enable);
 int32_t     omr_ctx_kernel_timings(omr_ctx* ctx, float* ms_out, int32_t* kind_out, int32_t cap);
@@ -1120,7 +1122,7 @@ typedef struct omr_zarr_info {
     int32_t pixel_type;                                /* OMR_PIXELS_* */
     int32_t big_endian;                                /* the arrays' byte order (">": 1) */
     int32_t n_levels;
-    int32_t compression;                               /* 0 none, 1 zlib, 2 Blosc (open_ex only) */
+    int32_t compression;                               /* 0 none, 1 zlib, 2 Blosc, 3 zstd (open_ex only) */
     int32_t chunk_width, chunk_height;                 /* level 0 */
     int32_t dimension_separator;                       /* '.' or '/' */
 } omr_zarr_info;
@@ -1228,6 +1230,77 @@ omr_status omr_blosc_decode_host(const uint8_t* src, size_t length, uint8_t* dst
 omr_status omr_lz4_decode_batch_device(omr_ctx* ctx, const uint8_t* d_src, const uint64_t* d_offsets,
                                        const uint32_t* d_lengths, const uint32_t* d_expected, int32_t n,
                                        uint8_t* d_dst, const uint64_t* d_dst_offsets, int32_t* d_status);
+
+/* ---- Blosc-Zstd and zstd OME-Zarr chunks, frames decoded on the device (K16) ---------------- */
+/*
+ * Two more codec bits of omr_zarr_open_options.codecs.  OMR_ZARR_CODEC_BLOSC_ZSTD accepts
+ * {"id": "blosc", "cname": "zstd"} under the shuffle rules of OMR_ZARR_CODEC_BLOSC (which alone
+ * still refuses a zstd group); OMR_ZARR_CODEC_ZSTD accepts the bare {"id": "zstd"} codec of
+ * numcodecs and tensorstore, whose level and checksum entries are ignored.  Bit 4u is not a codec:
+ * it stays unknown and OMR_INVALID_ARGUMENT.  A Blosc image remembers which inner formats its open
+ * allowed (1 = LZ4 with OMR_ZARR_CODEC_BLOSC, 4 = Zstd with OMR_ZARR_CODEC_BLOSC_ZSTD); a chunk
+ * whose header names another is a corrupt chunk.  omr_zarr_info.compression reads 2 for Blosc with
+ * either inner codec and 3 for bare zstd.  On the device route the Zstd streams of Blosc chunks and
+ * the chunks of a zstd image are decoded by K16a (kind 35) and placed by K15b (34) or K13b (31).
+ *
+ * A stream is exactly one Zstandard frame (RFC 8878; pinned against libzstd 1.4.8): magic
+ * 0xFD2FB528; single-segment or with a window descriptor (window log up to 31, as libzstd); Frame_Content_Size
+ * absent or of 1, 2, 4 or 8 bytes and then equal to `expected`; raw, RLE and compressed blocks no
+ * larger than the smaller of the window and 128 KiB; literals raw, RLE, Huffman (direct or
+ * FSE-compressed weights, code lengths up to 11, one or four streams, each consumed exactly) and
+ * treeless; sequence tables predefined, RLE, FSE-compressed (accuracy logs up to 9, 8, 9; offset
+ * codes up to 31) and repeat, the backward bit stream consumed exactly; repeat offsets 1, 4, 8;
+ * matches may reach into earlier blocks and overlap their own output; the content checksum (the
+ * low 32 bits of XXH64, seed 0), when flagged, is verified.  OMR_INTERNAL: anything else -- a
+ * skippable or second frame, trailing bytes, a dictionary id other than 0, a reserved bit, block
+ * type 3, a treeless or repeat form without a table from an earlier block of the frame, an offset
+ * beyond the bytes produced, and any output other than exactly `expected` bytes.  Blosc's format
+ * number 4 for Zstd, one frame per split, is as recalled, not pinned against c-blosc.
+ */
+#define OMR_ZARR_CODEC_BLOSC_ZSTD 8u
+#define OMR_ZARR_CODEC_ZSTD       16u
+/* One frame into exactly `expected` bytes, serial (nothing links libzstd). */
+omr_status omr_zstd_decode_host(const uint8_t* src, size_t length, uint8_t* dst, size_t expected);
+/*
+ * Walks a frame as the decoder does (the frame must be good; its size is taken from the frame, up
+ * to 256 MiB) and sets one bit per form met in forms[0 .. OMR_ZSTD_FORM_WORDS): form f is bit
+ * f & 31 of word f >> 5.  The tests use it to prove that their fixture reaches every branch.
+ */
+#define OMR_ZSTD_FORM_WORDS 2
+enum {
+    OMR_ZSTD_FORM_BLOCK_RAW = 0, OMR_ZSTD_FORM_BLOCK_RLE, OMR_ZSTD_FORM_BLOCK_COMPRESSED,
+    OMR_ZSTD_FORM_LIT_RAW, OMR_ZSTD_FORM_LIT_RLE, OMR_ZSTD_FORM_LIT_HUFFMAN, OMR_ZSTD_FORM_LIT_TREELESS,
+    OMR_ZSTD_FORM_STREAMS_1, OMR_ZSTD_FORM_STREAMS_4,
+    OMR_ZSTD_FORM_WEIGHTS_DIRECT, OMR_ZSTD_FORM_WEIGHTS_FSE,
+    OMR_ZSTD_FORM_SEQ_ZERO, OMR_ZSTD_FORM_SEQ_SHORT, OMR_ZSTD_FORM_SEQ_2BYTE, OMR_ZSTD_FORM_SEQ_3BYTE,
+    OMR_ZSTD_FORM_LL_PREDEFINED, OMR_ZSTD_FORM_LL_RLE, OMR_ZSTD_FORM_LL_FSE, OMR_ZSTD_FORM_LL_REPEAT,
+    OMR_ZSTD_FORM_OF_PREDEFINED, OMR_ZSTD_FORM_OF_RLE, OMR_ZSTD_FORM_OF_FSE, OMR_ZSTD_FORM_OF_REPEAT,
+    OMR_ZSTD_FORM_ML_PREDEFINED, OMR_ZSTD_FORM_ML_RLE, OMR_ZSTD_FORM_ML_FSE, OMR_ZSTD_FORM_ML_REPEAT,
+    OMR_ZSTD_FORM_SINGLE_SEGMENT, OMR_ZSTD_FORM_WINDOWED,
+    OMR_ZSTD_FORM_FCS_ABSENT, OMR_ZSTD_FORM_FCS_1, OMR_ZSTD_FORM_FCS_2, OMR_ZSTD_FORM_FCS_4, OMR_ZSTD_FORM_FCS_8,
+    OMR_ZSTD_FORM_CHECKSUM, OMR_ZSTD_FORM_MULTI_BLOCK,
+    OMR_ZSTD_FORM_COUNT
+};
+omr_status omr_zstd_frame_forms(const uint8_t* src, size_t length, uint32_t* forms);
+/*
+ * omr_blosc_decode_host with the set of inner codecs accepted: OMR_BLOSC_INNER_LZ4 takes the
+ * header's compressor format 1, OMR_BLOSC_INNER_ZSTD format 4 (each split one Zstandard frame).
+ * omr_blosc_decode_host itself is inner = OMR_BLOSC_INNER_LZ4.  OMR_INVALID_ARGUMENT: no bit, or
+ * an unknown one.
+ */
+#define OMR_BLOSC_INNER_LZ4  1u
+#define OMR_BLOSC_INNER_ZSTD 2u
+omr_status omr_blosc_decode_host_ex(const uint8_t* src, size_t length, uint8_t* dst, size_t expected, uint32_t inner);
+/*
+ * K16a alone: n independent Zstandard frames, the table layout and limits of
+ * omr_inflate_batch_device; d_status[i] = OMR_OK or OMR_INTERNAL by the rule of
+ * omr_zstd_decode_host, one stream's failure leaving the others alone, nothing written behind
+ * d_dst + d_dst_offsets[i] + d_expected[i].  Asynchronous on the context stream;
+ * omr_ctx_kernel_timings reports kind 35.
+ */
+omr_status omr_zstd_decode_batch_device(omr_ctx* ctx, const uint8_t* d_src, const uint64_t* d_offsets,
+                                        const uint32_t* d_lengths, const uint32_t* d_expected, int32_t n,
+                                        uint8_t* d_dst, const uint64_t* d_dst_offsets, int32_t* d_status);
 
 #ifdef __cplusplus
 }

@@ -54,12 +54,15 @@ inline int64_t le32(const uint8_t* p) {
 
 }  // namespace
 
-bool blosc_parse(const uint8_t* p, size_t len, size_t expected, BloscLayout& out) {
+bool blosc_parse(const uint8_t* p, size_t len, size_t expected, BloscLayout& out, uint32_t inner) {
     out = BloscLayout();
     if (len < 16 || len > 0x7FFFFFFFu || expected > 0x7FFFFFFFu) return false;
     const uint32_t flags = p[2];
     const int64_t nbytes = le32(p + 4), blocksize = le32(p + 8), cbytes = le32(p + 12);
-    if (p[0] != 2 || (flags & 0x04u) || (flags >> 5) != 1u) return false;
+    const uint32_t format = flags >> 5;
+    const bool known = (format == 1u && (inner & OMR_BLOSC_INNER_LZ4)) || (format == 4u && (inner & OMR_BLOSC_INNER_ZSTD));
+    if (p[0] != 2 || (flags & 0x04u) || !known) return false;
+    out.format = format;
     if (p[3] < 1 || nbytes != (int64_t)expected || cbytes != (int64_t)len || blocksize <= 0 || blocksize > nbytes)
         return false;
     out.nbytes = (uint32_t)nbytes;
@@ -125,9 +128,9 @@ void unshuffle(const BloscLayout& L, const uint8_t* src, uint8_t* dst) {
     }
 }
 
-bool blosc_decode(const uint8_t* p, size_t len, uint8_t* d, size_t expected) {
+bool blosc_decode(const uint8_t* p, size_t len, uint8_t* d, size_t expected, uint32_t inner) {
     BloscLayout L;
-    if (!blosc_parse(p, len, expected, L)) return false;
+    if (!blosc_parse(p, len, expected, L, inner)) return false;
     if (L.memcpyed) {
         std::memcpy(d, p + 16, expected);                  // cbytes == nbytes + 16 == len: checked
         return true;
@@ -140,7 +143,7 @@ bool blosc_decode(const uint8_t* p, size_t len, uint8_t* d, size_t expected) {
     }
     for (const BloscStream& s : L.streams) {               // src_off + csize <= len, dst_off + neblock <= nbytes
         if (s.raw) std::memcpy(to + s.dst_off, p + s.src_off, s.neblock);
-        else if (!lz4_decode(p + s.src_off, s.csize, to + s.dst_off, s.neblock)) return false;
+        else if (!(L.format == 4u ? zstd_decode : lz4_decode)(p + s.src_off, s.csize, to + s.dst_off, s.neblock)) return false;
     }
     if (L.shuffled) unshuffle(L, tmp.data(), d);
     return true;
@@ -158,7 +161,13 @@ omr_status omr_lz4_decode_host(const uint8_t* src, size_t length, uint8_t* dst, 
 
 omr_status omr_blosc_decode_host(const uint8_t* src, size_t length, uint8_t* dst, size_t expected) {
     if ((!src && length) || (!dst && expected)) return OMR_INVALID_ARGUMENT;
-    return omr::blosc_decode(src, length, dst, expected) ? OMR_OK : OMR_INTERNAL;
+    return omr::blosc_decode(src, length, dst, expected, OMR_BLOSC_INNER_LZ4) ? OMR_OK : OMR_INTERNAL;
+}
+
+omr_status omr_blosc_decode_host_ex(const uint8_t* src, size_t length, uint8_t* dst, size_t expected, uint32_t inner) {
+    if ((!src && length) || (!dst && expected)) return OMR_INVALID_ARGUMENT;
+    if (!inner || (inner & ~(OMR_BLOSC_INNER_LZ4 | OMR_BLOSC_INNER_ZSTD))) return OMR_INVALID_ARGUMENT;
+    return omr::blosc_decode(src, length, dst, expected, inner) ? OMR_OK : OMR_INTERNAL;
 }
 
 }  // extern "C"

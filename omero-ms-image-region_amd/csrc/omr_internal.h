@@ -327,6 +327,7 @@ struct BloscStream {
 };
 struct BloscLayout {
     uint32_t nbytes = 0, blocksize = 0, typesize = 0;
+    uint32_t format = 0;         // the header's compressor format: 1 LZ4, 4 Zstd
     bool shuffled = false;       // flag 0x01 and typesize > 1
     bool memcpyed = false;       // the pixels follow the header raw and unshuffled; no streams
     std::vector<BloscStream> streams;
@@ -336,7 +337,8 @@ struct BloscLayout {
 // more than kMaxBloscStreams streams.  The streams listed, with their csize words, never add up to
 // more than the bytes behind the table, so the list is bounded by the file's length as well.
 constexpr size_t kMaxBloscStreams = (size_t)1 << 20;
-bool blosc_parse(const uint8_t* p, size_t len, size_t expected, BloscLayout& out);
+// inner: the OMR_BLOSC_INNER_* bits whose compressor format the header may name.
+bool blosc_parse(const uint8_t* p, size_t len, size_t expected, BloscLayout& out, uint32_t inner = OMR_BLOSC_INNER_LZ4);
 // K15a (omr_blosc.hip): n streams (omr_lz4_decode_batch_device after its argument check); d_raw
 // (optional) marks the streams that are stored, not LZ4: they are copied, lengths[i] == expected[i].
 omr_status launch_lz4_decode(Ctx* ctx, const uint8_t* d_src, const uint64_t* d_offsets, const uint32_t* d_lengths,
@@ -352,6 +354,18 @@ struct BloscPlace {
     uint32_t blocksize, nbytes, typesize, shuffled;
 };
 omr_status launch_blosc_place(Ctx* ctx, const BloscPlace* d_places, int32_t n, int32_t max_rows, int32_t bps);
+
+// K16, host half (omr_zstd.cpp).  One Zstandard frame into exactly `expected` bytes (the rule of
+// omr_zstd_decode_host); every read and write is checked first.
+bool zstd_decode(const uint8_t* s, size_t len, uint8_t* d, size_t expected);
+// K16a (omr_zstd.hip): n frames (omr_zstd_decode_batch_device after its argument check); d_raw as
+// launch_lz4_decode's.  The literal buffers (128 KiB per workgroup of the grid) are kept in *lit /
+// *lit_cap, which the caller owns (the context's Zarr staging).
+omr_status launch_zstd_decode(Ctx* ctx, const uint8_t* d_src, const uint64_t* d_offsets, const uint32_t* d_lengths,
+                              const uint32_t* d_expected, const uint8_t* d_raw, int32_t n, uint8_t* d_dst,
+                              const uint64_t* d_dst_offsets, int32_t* d_status, void** lit, size_t* lit_cap);
+// The literal buffer of a context's Zarr staging (omr_zarr.cpp), made on first use.
+omr_status zarr_zstd_literals(Ctx* ctx, void*** lit, size_t** lit_cap);
 
 #define OMR_HIP(ctx, expr)                                         \
     do {                                                            \

@@ -9,7 +9,10 @@
 // listed once each, their files go to pinned memory and in one copy to the device with the chunk
 // table, K14a inflates them (omr_inflate.hip) and K13b places them (omr_tiffread.hip).  Blosc chunks
 // (K15, omr_zarr_image_open_ex) take the same staging: their container is read by omr_blosc.cpp, on
-// the device route into K15a's stream table, and K15b places them (omr_blosc.hip).
+// the device route into K15a's stream table, and K15b places them (omr_blosc.hip).  Zstandard (K16)
+// comes in both ways: as the inner codec of Blosc chunks, whose streams then go to K16a
+// (omr_zstd.hip) in a launch of their own, and as the bare zstd codec, which takes the zlib path
+// with K16a in place of K14a.
 #include "omr_internal.h"
 
 #include <dirent.h>
@@ -30,11 +33,15 @@ omr_status launch_lz4_decode(Ctx* ctx, const uint8_t* d_src, const uint64_t* d_o
                              const uint64_t* d_dst_offsets, int32_t* d_status) __attribute__((weak));
 omr_status launch_blosc_place(Ctx* ctx, const BloscPlace* d_places, int32_t n, int32_t max_rows, int32_t bps)
     __attribute__((weak));
+omr_status launch_zstd_decode(Ctx* ctx, const uint8_t* d_src, const uint64_t* d_offsets, const uint32_t* d_lengths,
+                              const uint32_t* d_expected, const uint8_t* d_raw, int32_t n, uint8_t* d_dst,
+                              const uint64_t* d_dst_offsets, int32_t* d_status, void** lit, size_t* lit_cap)
+    __attribute__((weak));
 }  // namespace omr
 
 namespace {
 
-constexpr int kNone = 0, kZlib = 1, kBlosc = 2;             // omr_zarr_info.compression
+constexpr int kNone = 0, kZlib = 1, kBlosc = 2, kZstd = 3;  // omr_zarr_info.compression
 constexpr uint64_t kMaxChunkBytes = (uint64_t)256 << 20;    // decoded size of one chunk
 constexpr uint64_t kMaxStreamBytes = ((uint64_t)512 << 20) - 1;
 constexpr size_t kMaxJsonBytes = (size_t)1 << 20;
@@ -244,6 +251,7 @@ struct omr_zarr_image {
     int32_t pt = 0, bpp = 0;
     bool big = false;
     int comp = kNone;
+    uint32_t inner = 0;           // kBlosc: the OMR_BLOSC_INNER_* formats the open allowed
     std::vector<Level> levels;
 };
 
@@ -498,11 +506,16 @@ omr_status parse_zarray(const std::vector<uint8_t>& text, uint32_t codecs, Array
         if (!id || id->type != Json::String) return OMR_INVALID_ARGUMENT;
         if (id->s == "zlib" && (codecs & OMR_ZARR_CODEC_ZLIB)) {
             m.comp = kZlib;
-        } else if (id->s == "blosc" && (codecs & OMR_ZARR_CODEC_BLOSC)) {
-            // LZ4 inside (lz4hc writes the same block format); byte shuffle or none.  -1 is numcodecs'
-            // automatic choice: byte shuffle for types wider than a byte, bit shuffle for the others.
+        } else if (id->s == "zstd" && (codecs & OMR_ZARR_CODEC_ZSTD)) {
+            m.comp = kZstd;                                // level and checksum: the frames say it themselves
+        } else if (id->s == "blosc" && (codecs & (OMR_ZARR_CODEC_BLOSC | OMR_ZARR_CODEC_BLOSC_ZSTD))) {
+            // LZ4 inside (lz4hc writes the same block format) or Zstd, each under its own bit; byte
+            // shuffle or none.  -1 is numcodecs' automatic choice: byte shuffle for types wider than a
+            // byte, bit shuffle for the others.
             const Json* cname = v->get("cname");
-            if (!cname || cname->type != Json::String || (cname->s != "lz4" && cname->s != "lz4hc")) return OMR_INVALID_ARGUMENT;
+            if (!cname || cname->type != Json::String) return OMR_INVALID_ARGUMENT;
+            const bool lz4 = (cname->s == "lz4" || cname->s == "lz4hc") && (codecs & OMR_ZARR_CODEC_BLOSC);
+            if (!lz4 && !(cname->s == "zstd" && (codecs & OMR_ZARR_CODEC_BLOSC_ZSTD))) return OMR_INVALID_ARGUMENT;
             if (const Json* sh = v->get("shuffle")) {
                 if (sh->type != Json::Number || !sh->is_int) return OMR_INVALID_ARGUMENT;
                 if (sh->i != 0 && sh->i != 1 && !(sh->i == -1 && !one_byte)) return OMR_INVALID_ARGUMENT;
@@ -602,7 +615,8 @@ omr_status load_chunk(const omr_zarr_image* im, const Level& L, int32_t t, int32
     out.assign(expected, 0);
     if (r == Slurp::Missing) return OMR_OK;
     if (r != Slurp::Ok) return OMR_INTERNAL;
-    if (im->comp == kBlosc) return omr_blosc_decode_host(comp.data(), comp.size(), out.data(), expected);
+    if (im->comp == kBlosc) return omr_blosc_decode_host_ex(comp.data(), comp.size(), out.data(), expected, im->inner);
+    if (im->comp == kZstd) return omr::zstd_decode(comp.data(), comp.size(), out.data(), expected) ? OMR_OK : OMR_INTERNAL;
     return inflate(comp.data(), comp.size(), out.data(), expected) ? OMR_OK : OMR_INTERNAL;
 }
 
@@ -621,10 +635,12 @@ struct ZarrPipe {
     void* pin_tab = nullptr;     // Blosc: the stream table and the placements, sized after the files are read
     void* d_tab = nullptr;
     size_t tab_cap = 0;
+    void* d_lit = nullptr;       // K16a: one literal buffer per workgroup of its grid
+    size_t lit_cap = 0;
     ~ZarrPipe() {
         if (pin) (void)hipHostFree(pin);
         if (pin_tab) (void)hipHostFree(pin_tab);
-        for (void* p : {d_in, d_scratch, d_regions, d_out, d_tab})
+        for (void* p : {d_in, d_scratch, d_regions, d_out, d_tab, d_lit})
             if (p) (void)hipFree(p);
     }
 };
@@ -680,21 +696,23 @@ constexpr size_t kRenderGroupBytes = (size_t)256 << 20;    // region bytes per r
 // the streams into the chunks' scratch and K15b places with the un-shuffle in its loads.
 omr_status finish_blosc(omr::Ctx* ctx, ZarrPipe* T, const std::vector<UniqueChunk>& chunks,
                         const std::vector<omr::TiffPlace>& places, const std::vector<int32_t>& place_chunk,
-                        uint32_t expected, size_t in_bytes, int32_t max_rows, int32_t bpp) {
+                        uint32_t expected, size_t in_bytes, int32_t max_rows, int32_t bpp, uint32_t inner) {
     using omr::align_up;
     using omr::BloscPlace;
-    if (!omr::launch_lz4_decode || !omr::launch_blosc_place) return omr::fail(ctx, OMR_DEVICE, "zarr: built without the Blosc kernels");
+    if (!omr::launch_lz4_decode || !omr::launch_blosc_place || !omr::launch_zstd_decode)
+        return omr::fail(ctx, OMR_DEVICE, "zarr: built without the Blosc kernels");
     uint8_t* pin = static_cast<uint8_t*>(T->pin);
     uint8_t* din = static_cast<uint8_t*>(T->d_in);
     uint8_t* dscr = static_cast<uint8_t*>(T->d_scratch);
     std::vector<omr::BloscLayout> layouts(chunks.size());
-    size_t m = 0;
+    size_t m = 0, m_lz4 = 0;                               // streams; those of LZ4 chunks come first in the tables
     for (size_t k = 0; k < chunks.size(); ++k) {
         const UniqueChunk& u = chunks[k];
         if (!u.cnt) continue;
-        if (!omr::blosc_parse(pin + u.in_off, (size_t)u.cnt, expected, layouts[k]))
+        if (!omr::blosc_parse(pin + u.in_off, (size_t)u.cnt, expected, layouts[k], inner))
             return omr::fail(ctx, OMR_INTERNAL, "zarr: corrupt blosc chunk");
         m += layouts[k].streams.size();
+        if (layouts[k].format != 4u) m_lz4 += layouts[k].streams.size();
     }
     // tables: [offsets u64 m][dst offsets u64 m][lengths u32 m][expected u32 m][raw u8 m][places] | [status i32 m]
     const size_t o_dst = 8 * m, o_len = o_dst + 8 * m, o_exp = o_len + 4 * m, o_raw = o_exp + 4 * m;
@@ -720,15 +738,15 @@ omr_status finish_blosc(omr::Ctx* ctx, ZarrPipe* T, const std::vector<UniqueChun
     uint32_t* h_len = reinterpret_cast<uint32_t*>(tab + o_len);
     uint32_t* h_exp = reinterpret_cast<uint32_t*>(tab + o_exp);
     uint8_t* h_raw = tab + o_raw;
-    size_t j = 0;
+    size_t j_lz4 = 0, j_zstd = m_lz4;                      // a stored split goes with its chunk's launch
     for (size_t k = 0; k < chunks.size(); ++k)
         for (const omr::BloscStream& s : layouts[k].streams) {
+            const size_t j = layouts[k].format != 4u ? j_lz4++ : j_zstd++;
             h_off[j] = chunks[k].in_off + s.src_off;
             h_dst[j] = chunks[k].scratch_off + s.dst_off;
             h_len[j] = s.csize;
             h_exp[j] = s.neblock;
             h_raw[j] = s.raw;
-            ++j;
         }
     BloscPlace* h_place = reinterpret_cast<BloscPlace*>(tab + o_place);
     for (size_t k = 0; k < places.size(); ++k) {
@@ -749,9 +767,15 @@ omr_status finish_blosc(omr::Ctx* ctx, ZarrPipe* T, const std::vector<UniqueChun
     OMR_HIP(ctx, hipMemcpyAsync(dtab, tab, up_bytes, hipMemcpyHostToDevice, ctx->stream));
     omr_status st = omr::launch_lz4_decode(ctx, din, reinterpret_cast<const uint64_t*>(dtab),
                                            reinterpret_cast<const uint32_t*>(dtab + o_len),
-                                           reinterpret_cast<const uint32_t*>(dtab + o_exp), dtab + o_raw, (int32_t)m, dscr,
+                                           reinterpret_cast<const uint32_t*>(dtab + o_exp), dtab + o_raw, (int32_t)m_lz4, dscr,
                                            reinterpret_cast<const uint64_t*>(dtab + o_dst),
                                            reinterpret_cast<int32_t*>(dtab + o_status));
+    if (st) return st;
+    st = omr::launch_zstd_decode(ctx, din, reinterpret_cast<const uint64_t*>(dtab) + m_lz4,
+                                 reinterpret_cast<const uint32_t*>(dtab + o_len) + m_lz4,
+                                 reinterpret_cast<const uint32_t*>(dtab + o_exp) + m_lz4, dtab + o_raw + m_lz4,
+                                 (int32_t)(m - m_lz4), dscr, reinterpret_cast<const uint64_t*>(dtab + o_dst) + m_lz4,
+                                 reinterpret_cast<int32_t*>(dtab + o_status) + m_lz4, &T->d_lit, &T->lit_cap);
     if (st) return st;
     st = omr::launch_blosc_place(ctx, reinterpret_cast<const BloscPlace*>(dtab + o_place), (int32_t)places.size(), max_rows, bpp);
     if (st) return st;
@@ -821,7 +845,7 @@ omr_status read_group(omr::Ctx* ctx, const omr_zarr_image* im, int32_t level, co
     if (bad == 1) return omr::fail(ctx, OMR_INTERNAL, "zarr: chunk file cannot be read");
     if (bad == 2) return omr::fail(ctx, OMR_INTERNAL, "zarr: chunk file of the wrong size");
     size_t in_bytes = 0, scratch_bytes = 0;
-    std::vector<int32_t> coded;                        // the chunks K14a inflates
+    std::vector<int32_t> coded;                        // the chunks K14a inflates, or K16a decodes
     for (size_t k = 0; k < chunks.size(); ++k) {
         UniqueChunk& u = chunks[k];
         if (!u.cnt) continue;
@@ -830,7 +854,7 @@ omr_status read_group(omr::Ctx* ctx, const omr_zarr_image* im, int32_t level, co
         if (im->comp != kNone) {
             u.scratch_off = scratch_bytes;
             scratch_bytes += align_up((size_t)expected, 16);
-            if (im->comp == kZlib) coded.push_back((int32_t)k);
+            if (im->comp == kZlib || im->comp == kZstd) coded.push_back((int32_t)k);
         }
     }
     const bool blosc = im->comp == kBlosc;                 // its tables go up behind the bytes, from T->pin_tab
@@ -878,7 +902,7 @@ omr_status read_group(omr::Ctx* ctx, const omr_zarr_image* im, int32_t level, co
         if (got != u.cnt) io_error = true;
     });
     if (io_error) return omr::fail(ctx, OMR_INTERNAL, "zarr: chunk read failed");
-    if (blosc) return finish_blosc(ctx, T, chunks, places, place_chunk, expected, in_bytes, max_rows, im->bpp);
+    if (blosc) return finish_blosc(ctx, T, chunks, places, place_chunk, expected, in_bytes, max_rows, im->bpp, im->inner);
     uint64_t* h_off = reinterpret_cast<uint64_t*>(pin + o_off);
     uint64_t* h_dst = reinterpret_cast<uint64_t*>(pin + o_dst);
     uint32_t* h_len = reinterpret_cast<uint32_t*>(pin + o_len);
@@ -893,14 +917,22 @@ omr_status read_group(omr::Ctx* ctx, const omr_zarr_image* im, int32_t level, co
     TiffPlace* h_place = reinterpret_cast<TiffPlace*>(pin + o_place);
     for (size_t k = 0; k < places.size(); ++k) {
         const UniqueChunk& u = chunks[(size_t)place_chunk[k]];
-        places[k].src = !u.cnt ? nullptr : im->comp == kZlib ? dscr + u.scratch_off : din + u.in_off;
+        places[k].src = !u.cnt ? nullptr : im->comp != kNone ? dscr + u.scratch_off : din + u.in_off;
         h_place[k] = places[k];
     }
     OMR_HIP(ctx, hipMemcpyAsync(din, pin, up_bytes, hipMemcpyHostToDevice, ctx->stream));
-    st = omr::launch_inflate(ctx, din, reinterpret_cast<const uint64_t*>(din + o_off),
-                             reinterpret_cast<const uint32_t*>(din + o_len), reinterpret_cast<const uint32_t*>(din + o_exp),
-                             (int32_t)m, dscr, reinterpret_cast<const uint64_t*>(din + o_dst),
-                             reinterpret_cast<int32_t*>(din + o_status));
+    if (im->comp == kZstd) {
+        if (!omr::launch_zstd_decode) return omr::fail(ctx, OMR_DEVICE, "zarr: built without the Zstandard kernel");
+        st = omr::launch_zstd_decode(ctx, din, reinterpret_cast<const uint64_t*>(din + o_off),
+                                     reinterpret_cast<const uint32_t*>(din + o_len), reinterpret_cast<const uint32_t*>(din + o_exp),
+                                     nullptr, (int32_t)m, dscr, reinterpret_cast<const uint64_t*>(din + o_dst),
+                                     reinterpret_cast<int32_t*>(din + o_status), &T->d_lit, &T->lit_cap);
+    } else {
+        st = omr::launch_inflate(ctx, din, reinterpret_cast<const uint64_t*>(din + o_off),
+                                 reinterpret_cast<const uint32_t*>(din + o_len), reinterpret_cast<const uint32_t*>(din + o_exp),
+                                 (int32_t)m, dscr, reinterpret_cast<const uint64_t*>(din + o_dst),
+                                 reinterpret_cast<int32_t*>(din + o_status));
+    }
     if (st) return st;
     st = omr::launch_tiff_place(ctx, reinterpret_cast<const TiffPlace*>(din + o_place), (int32_t)places.size(), max_rows,
                                 im->bpp, 1, false);
@@ -909,11 +941,21 @@ omr_status read_group(omr::Ctx* ctx, const omr_zarr_image* im, int32_t level, co
     OMR_HIP(ctx, hipStreamSynchronize(ctx->stream));
     const int32_t* h_status = reinterpret_cast<const int32_t*>(pin + o_status);
     for (size_t j = 0; j < m; ++j)
-        if (h_status[j] != OMR_OK) return omr::fail(ctx, OMR_INTERNAL, "zarr: corrupt zlib chunk");
+        if (h_status[j] != OMR_OK)
+            return omr::fail(ctx, OMR_INTERNAL, im->comp == kZstd ? "zarr: corrupt zstd chunk" : "zarr: corrupt zlib chunk");
     return OMR_OK;
 }
 
 }  // namespace
+
+namespace omr {
+omr_status zarr_zstd_literals(Ctx* ctx, void*** lit, size_t** lit_cap) {
+    ZarrPipe* T = get_zarr_pipe(ctx);
+    *lit = &T->d_lit;
+    *lit_cap = &T->lit_cap;
+    return OMR_OK;
+}
+}  // namespace omr
 
 using namespace omr;
 
@@ -930,7 +972,8 @@ omr_status omr_zarr_image_open_ex(const char* group_path, const omr_zarr_open_op
     uint32_t codecs = OMR_ZARR_CODEC_ZLIB;
     if (opt) {
         if (opt->struct_size < sizeof(omr_zarr_open_options)) return OMR_INVALID_ARGUMENT;
-        if (opt->codecs & ~(OMR_ZARR_CODEC_ZLIB | OMR_ZARR_CODEC_BLOSC)) return OMR_INVALID_ARGUMENT;
+        if (opt->codecs & ~(OMR_ZARR_CODEC_ZLIB | OMR_ZARR_CODEC_BLOSC | OMR_ZARR_CODEC_BLOSC_ZSTD | OMR_ZARR_CODEC_ZSTD))
+            return OMR_INVALID_ARGUMENT;
         codecs = opt->codecs;
     }
     std::string root(group_path);
@@ -948,6 +991,7 @@ omr_status omr_zarr_image_open_ex(const char* group_path, const omr_zarr_open_op
         if (st) return st;
     }
     std::unique_ptr<omr_zarr_image> im(new omr_zarr_image);
+    im->inner = (codecs & OMR_ZARR_CODEC_BLOSC ? OMR_BLOSC_INNER_LZ4 : 0u) | (codecs & OMR_ZARR_CODEC_BLOSC_ZSTD ? OMR_BLOSC_INNER_ZSTD : 0u);
     char sep0 = '.';
     for (int k = 0; listed ? k < (int)paths.size() : k < kMaxLevels; ++k) {
         Level L;

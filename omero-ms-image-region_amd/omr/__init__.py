@@ -7,7 +7,7 @@ Layers:
             (ImageRegionRequestHandler.java:436-440, :689-741, :559)
   pixbuf    PixelBuffer: ROMIO repository pixel files (getPixelBuffer, :302-309)
   tiffimage TiffImage: tiled TIFF / OME-TIFF pixel files, LZW decoded on the GPU; write_tiled_tiff
-  zarrimage ZarrImage: OME-Zarr pyramids, zlib and Blosc-LZ4 chunks decoded on the GPU; write_zarr
+  zarrimage ZarrImage: OME-Zarr pyramids, zlib, Blosc (LZ4 or Zstd inside) and zstd chunks decoded on the GPU; write_zarr
   batcher   Batcher: concurrent requests coalesced into GPU batches; Pool: one batcher per GPU
   request   ImageRegionCtx / ShapeMaskCtx parsing and the handler glue
             (ImageRegionCtx.java, ImageRegionRequestHandler.java, ShapeMaskRequestHandler.java)
@@ -18,7 +18,7 @@ from .context import Context, pyramid_level_count, pyramid_level_sizes, thumbnai
 from .pixbuf import PixelBuffer, write_pyramid, write_romio
 from .tiffimage import TiffImage, lzw_decode_host, lzw_encode, write_tiled_tiff
 from .zarrimage import (ZarrImage, blosc_decode_host, blosc_encode, inflate_host, lz4_decode_host, lz4_encode,
-                        write_zarr)
+                        write_zarr, zstd_decode_host, zstd_encode, zstd_frame_forms)
 from .batcher import Batcher, Pool
 from .renderer import (ChannelSettings, Renderer, ReverseIntensityContext, create_rendering_def,
                        flip, split_html_color)
@@ -77,4 +77,4 @@ __all__ = ["_lib", "OmrError", "Context", "Renderer", "histogram_bin_of", "histo
            "ShapeMaskCtx", "ShapeMaskRequestHandler", "PixelBuffer", "write_romio", "write_pyramid", "Batcher", "Pool",
            "TiffImage", "write_tiled_tiff", "lzw_encode", "lzw_decode_host",
            "ZarrImage", "write_zarr", "inflate_host", "lz4_encode", "lz4_decode_host", "blosc_encode",
-           "blosc_decode_host"]
+           "blosc_decode_host", "zstd_encode", "zstd_decode_host", "zstd_frame_forms"]

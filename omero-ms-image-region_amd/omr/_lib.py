@@ -115,6 +115,16 @@ class ZarrInfo(ctypes.Structure):
 
 
 ZARR_CODEC_ZLIB, ZARR_CODEC_BLOSC = 1, 2
+ZARR_CODEC_BLOSC_ZSTD, ZARR_CODEC_ZSTD = 8, 16            # 4 is no codec: it stays unknown
+BLOSC_INNER_LZ4, BLOSC_INNER_ZSTD = 1, 2
+# OMR_ZSTD_FORM_*: omr.zstd_frame_forms returns the set as one integer, form f its bit f
+ZSTD_FORM_NAMES = ("BLOCK_RAW", "BLOCK_RLE", "BLOCK_COMPRESSED", "LIT_RAW", "LIT_RLE", "LIT_HUFFMAN", "LIT_TREELESS",
+                   "STREAMS_1", "STREAMS_4", "WEIGHTS_DIRECT", "WEIGHTS_FSE", "SEQ_ZERO", "SEQ_SHORT", "SEQ_2BYTE",
+                   "SEQ_3BYTE", "LL_PREDEFINED", "LL_RLE", "LL_FSE", "LL_REPEAT", "OF_PREDEFINED", "OF_RLE", "OF_FSE",
+                   "OF_REPEAT", "ML_PREDEFINED", "ML_RLE", "ML_FSE", "ML_REPEAT", "SINGLE_SEGMENT", "WINDOWED",
+                   "FCS_ABSENT", "FCS_1", "FCS_2", "FCS_4", "FCS_8", "CHECKSUM", "MULTI_BLOCK")
+ZSTD_FORM = {n: k for k, n in enumerate(ZSTD_FORM_NAMES)}
+ZSTD_FORM_WORDS = 2
 
 
 class ZarrOpenOptions(ctypes.Structure):
@@ -312,6 +322,10 @@ _SIGS = {
     "omr_lz4_decode_host": (_i32, [_vp, _sz, _vp, _sz]),
     "omr_blosc_decode_host": (_i32, [_vp, _sz, _vp, _sz]),
     "omr_lz4_decode_batch_device": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "omr_zstd_decode_host": (_i32, [_vp, _sz, _vp, _sz]),
+    "omr_zstd_frame_forms": (_i32, [_vp, _sz, ctypes.POINTER(ctypes.c_uint32)]),
+    "omr_blosc_decode_host_ex": (_i32, [_vp, _sz, _vp, _sz, ctypes.c_uint32]),
+    "omr_zstd_decode_batch_device": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
     "omr_render_shape_mask_png_batch": (_i32, [_vp, ctypes.POINTER(MaskJob), _i32, _vp, _sz, _vp, _vp, _vp]),
     "omr_split_html_color": (_i32, [ctypes.c_char_p, ctypes.POINTER(_i32)]),
     "omr_shape_mask_fill_color": (_i32, [_i32, _i32, ctypes.c_char_p, _vp]),
