@@ -272,16 +272,14 @@ __global__ void __launch_bounds__(256) k_blosc_place(const BloscPlace* __restric
 
 }  // namespace
 
-omr_status launch_lz4_decode(Ctx* ctx, const uint8_t* d_src, const uint64_t* d_offsets, const uint32_t* d_lengths,
-                             const uint32_t* d_expected, const uint8_t* d_raw, int32_t n, uint8_t* d_dst,
-                             const uint64_t* d_dst_offsets, int32_t* d_status) {
-    if (n <= 0) return OMR_OK;
+omr_status launch_lz4_decode(Ctx* ctx, const StreamTable& t) {
+    if (t.n <= 0) return OMR_OK;
     // no LDS; 103 SGPRs (52 VGPRs would allow 8) hold the kernel to 7 waves per SIMD, so 28 of the 32
     // one-wave workgroups launched per CU are resident at once and the rest follow by the grid stride
-    const int blocks = std::min(n, std::max(1, ctx->cu_count) * 32);
+    const int blocks = std::min(t.n, std::max(1, ctx->cu_count) * 32);
     KernelTimer timer(ctx, kKindLz4Decode, true);
-    omr_launch(k_lz4_decode, dim3((unsigned)blocks), dim3(64), 0u, ctx->stream, d_src, d_offsets, d_lengths, d_expected,
-               d_raw, (int)n, d_dst, d_dst_offsets, d_status);
+    omr_launch(k_lz4_decode, dim3((unsigned)blocks), dim3(64), 0u, ctx->stream, t.src, t.offsets, t.lengths, t.expected,
+               t.raw, (int)t.n, t.dst, t.dst_offsets, t.status);
     OMR_HIP(ctx, hipGetLastError());
     return OMR_OK;
 }
@@ -316,5 +314,5 @@ extern "C" omr_status omr_lz4_decode_batch_device(omr_ctx* ctx, const uint8_t* d
     if (!d_src || !d_offsets || !d_lengths || !d_expected || !d_dst || !d_dst_offsets || !d_status)
         return fail(ctx, OMR_INVALID_ARGUMENT, "lz4: null argument");
     OMR_HIP(ctx, hipSetDevice(ctx->device));
-    return launch_lz4_decode(ctx, d_src, d_offsets, d_lengths, d_expected, nullptr, n, d_dst, d_dst_offsets, d_status);
+    return launch_lz4_decode(ctx, {d_src, d_offsets, d_lengths, d_expected, nullptr, n, d_dst, d_dst_offsets, d_status});
 }

@@ -510,15 +510,13 @@ __global__ void __launch_bounds__(64) k_inflate(const uint8_t* __restrict__ src,
 
 }  // namespace
 
-omr_status launch_inflate(Ctx* ctx, const uint8_t* d_src, const uint64_t* d_offsets, const uint32_t* d_lengths,
-                          const uint32_t* d_expected, int32_t n, uint8_t* d_dst, const uint64_t* d_dst_offsets,
-                          int32_t* d_status) {
-    if (n <= 0) return OMR_OK;
+omr_status launch_inflate(Ctx* ctx, const StreamTable& t) {
+    if (t.n <= 0) return OMR_OK;
     // about 5 KiB of LDS per wave, so registers and the 32-wave limit set the residency; 16 waves per CU
-    const int blocks = std::min(n, std::max(1, ctx->cu_count) * 16);
+    const int blocks = std::min(t.n, std::max(1, ctx->cu_count) * 16);
     KernelTimer timer(ctx, kKindInflate, true);
-    omr_launch(k_inflate, dim3((unsigned)blocks), dim3(64), 0u, ctx->stream, d_src, d_offsets, d_lengths, d_expected,
-               (int)n, d_dst, d_dst_offsets, d_status);
+    omr_launch(k_inflate, dim3((unsigned)blocks), dim3(64), 0u, ctx->stream, t.src, t.offsets, t.lengths, t.expected,
+               (int)t.n, t.dst, t.dst_offsets, t.status);
     OMR_HIP(ctx, hipGetLastError());
     return OMR_OK;
 }
@@ -536,5 +534,5 @@ extern "C" omr_status omr_inflate_batch_device(omr_ctx* ctx, const uint8_t* d_sr
     if (!d_src || !d_offsets || !d_lengths || !d_expected || !d_dst || !d_dst_offsets || !d_status)
         return fail(ctx, OMR_INVALID_ARGUMENT, "inflate: null argument");
     OMR_HIP(ctx, hipSetDevice(ctx->device));
-    return launch_inflate(ctx, d_src, d_offsets, d_lengths, d_expected, n, d_dst, d_dst_offsets, d_status);
+    return launch_inflate(ctx, {d_src, d_offsets, d_lengths, d_expected, nullptr, n, d_dst, d_dst_offsets, d_status});
 }

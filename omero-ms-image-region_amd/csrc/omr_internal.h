@@ -175,10 +175,10 @@ struct Ctx {
     void* pixbuf_state = nullptr;
     bool pixbuf_direct = true;   // DMA tile rows from a registered file mapping when possible
     void (*pixbuf_state_free)(void*) = nullptr;
-    // tiled TIFF reader (omr_tiffread.cpp): pinned and device staging, scratch for decoded segments
+    // tiled TIFF reader: pinned and device staging, scratch for decoded segments (a SegPipe, omr_segread.h)
     void* tiff_state = nullptr;
     void (*tiff_state_free)(void*) = nullptr;
-    // OME-Zarr reader (omr_zarr.cpp): the same kinds of staging, its own
+    // OME-Zarr reader: the same kinds of staging, its own
     void* zarr_state = nullptr;
     void (*zarr_state_free)(void*) = nullptr;
 };
@@ -303,18 +303,29 @@ struct TiffPlace {
     int32_t seg_w, dst_pitch;
     int32_t x0, x1, y0, y1;
 };
-// K13a: n LZW streams (omr_lzw_decode_batch_device after its argument check).
-omr_status launch_lzw_decode(Ctx* ctx, const uint8_t* d_src, const uint64_t* d_offsets, const uint32_t* d_lengths,
-                             const uint32_t* d_expected, int32_t n, uint8_t* d_dst, const uint64_t* d_dst_offsets,
-                             int32_t* d_status);
+// The argument of the stream decoders (K13a, K14a, K15a, K16a), all device memory: stream i is
+// lengths[i] bytes at src + offsets[i] and decodes to exactly expected[i] bytes at dst +
+// dst_offsets[i]; status[i] gets OMR_OK or OMR_INTERNAL.  raw (optional; K15a and K16a only) marks
+// the streams that are stored: they are copied, lengths[i] == expected[i].
+struct StreamTable {
+    const uint8_t* src;
+    const uint64_t* offsets;
+    const uint32_t* lengths;
+    const uint32_t* expected;
+    const uint8_t* raw;
+    int32_t n;
+    uint8_t* dst;
+    const uint64_t* dst_offsets;
+    int32_t* status;
+};
+// K13a: LZW streams (omr_lzw_decode_batch_device after its argument check).
+omr_status launch_lzw_decode(Ctx* ctx, const StreamTable& t);
 // K13b: n placements (a device table) of samples bps bytes wide, none taller than max_rows; swap:
 // the file's byte order is not the host's (it matters to predictor 2 only).
 omr_status launch_tiff_place(Ctx* ctx, const TiffPlace* d_places, int32_t n, int32_t max_rows, int32_t bps,
                              int32_t predictor, bool swap);
-// K14a (omr_inflate.hip): n zlib streams (omr_inflate_batch_device after its argument check).
-omr_status launch_inflate(Ctx* ctx, const uint8_t* d_src, const uint64_t* d_offsets, const uint32_t* d_lengths,
-                          const uint32_t* d_expected, int32_t n, uint8_t* d_dst, const uint64_t* d_dst_offsets,
-                          int32_t* d_status);
+// K14a (omr_inflate.hip): zlib streams (omr_inflate_batch_device after its argument check).
+omr_status launch_inflate(Ctx* ctx, const StreamTable& t);
 
 // K15, host half (omr_blosc.cpp).  One LZ4 block into exactly `expected` bytes (the rule of
 // omr_lz4_decode_host); every read and write is checked first.
@@ -339,11 +350,8 @@ struct BloscLayout {
 constexpr size_t kMaxBloscStreams = (size_t)1 << 20;
 // inner: the OMR_BLOSC_INNER_* bits whose compressor format the header may name.
 bool blosc_parse(const uint8_t* p, size_t len, size_t expected, BloscLayout& out, uint32_t inner = OMR_BLOSC_INNER_LZ4);
-// K15a (omr_blosc.hip): n streams (omr_lz4_decode_batch_device after its argument check); d_raw
-// (optional) marks the streams that are stored, not LZ4: they are copied, lengths[i] == expected[i].
-omr_status launch_lz4_decode(Ctx* ctx, const uint8_t* d_src, const uint64_t* d_offsets, const uint32_t* d_lengths,
-                             const uint32_t* d_expected, const uint8_t* d_raw, int32_t n, uint8_t* d_dst,
-                             const uint64_t* d_dst_offsets, int32_t* d_status);
+// K15a (omr_blosc.hip): LZ4 blocks (omr_lz4_decode_batch_device after its argument check).
+omr_status launch_lz4_decode(Ctx* ctx, const StreamTable& t);
 // K15b: a TiffPlace whose source holds a Blosc chunk's bytes, shuffled per block when `shuffled`
 // (decoded byte i * typesize + j of a block of nb bytes is its byte j * (nb / typesize) + i).
 struct BloscPlace {
@@ -358,14 +366,10 @@ omr_status launch_blosc_place(Ctx* ctx, const BloscPlace* d_places, int32_t n, i
 // K16, host half (omr_zstd.cpp).  One Zstandard frame into exactly `expected` bytes (the rule of
 // omr_zstd_decode_host); every read and write is checked first.
 bool zstd_decode(const uint8_t* s, size_t len, uint8_t* d, size_t expected);
-// K16a (omr_zstd.hip): n frames (omr_zstd_decode_batch_device after its argument check); d_raw as
-// launch_lz4_decode's.  The literal buffers (128 KiB per workgroup of the grid) are kept in *lit /
-// *lit_cap, which the caller owns (the context's Zarr staging).
-omr_status launch_zstd_decode(Ctx* ctx, const uint8_t* d_src, const uint64_t* d_offsets, const uint32_t* d_lengths,
-                              const uint32_t* d_expected, const uint8_t* d_raw, int32_t n, uint8_t* d_dst,
-                              const uint64_t* d_dst_offsets, int32_t* d_status, void** lit, size_t* lit_cap);
-// The literal buffer of a context's Zarr staging (omr_zarr.cpp), made on first use.
-omr_status zarr_zstd_literals(Ctx* ctx, void*** lit, size_t** lit_cap);
+// K16a (omr_zstd.hip): frames (omr_zstd_decode_batch_device after its argument check).  The literal
+// buffers (128 KiB per workgroup of the grid) are kept in *lit / *lit_cap, which the caller owns
+// (the context's Zarr staging, omr_segread.h).
+omr_status launch_zstd_decode(Ctx* ctx, const StreamTable& t, void** lit, size_t* lit_cap);
 
 #define OMR_HIP(ctx, expr)                                         \
     do {                                                            \

@@ -4,20 +4,19 @@
 // as raw2ometiff writes it, one IFD per plane and the lower resolutions in SubIFDs.  This file
 // holds the parser (pread, every offset bounds-checked: a file is user-uploaded data), the plain
 // serial LZW decoder of the host route (omr_tiff_image_get_tile: the reference of the tests and
-// the route of single reads) and the staging of the device route: the segments the requested
-// regions touch are listed once each, their compressed bytes go to pinned memory and in one copy
-// to the device with the segment table, K13a decodes them and K13b places them (omr_tiffread.hip).
-#include "omr_internal.h"
+// the route of single reads) and what the device route needs to know of a TIFF (TiffSource): a
+// segment's offset and byte count from the IFD tables, the rows of a short last strip, and the
+// pread of the segments' bytes from the one file.  The device route itself -- staging, planning,
+// K13a's and K13b's launches (omr_tiffread.hip), the tile renderer -- is omr_segread.cpp, shared
+// with the Zarr reader; this file calls no HIP function.
+#include "omr_segread.h"
 
 #include <fcntl.h>
 #include <sys/stat.h>
 #include <unistd.h>
 
-#include <atomic>
 #include <cerrno>
 #include <memory>
-#include <thread>
-#include <unordered_map>
 #include <unordered_set>
 
 namespace {
@@ -370,191 +369,43 @@ omr_status load_segment(const omr_tiff_image* im, const Level& L, const Segments
     return OMR_OK;
 }
 
-// ---- device route: staging of one context -------------------------------------------------------
+// ---- device route: what the shared pipeline (omr_segread.h) asks of a TIFF ---------------------------
 
-struct TiffPipe {
-    void* pin = nullptr;      // compressed bytes + tables (+ the statuses coming back)
-    void* d_in = nullptr;
-    size_t in_cap = 0;
-    void* d_scratch = nullptr;   // decoded segments, tile-packed
-    size_t scratch_cap = 0;
-    void* d_regions = nullptr;   // omr_render_tiff_tiles: [tile][channel][h][w]
-    size_t regions_cap = 0;
-    void* d_out = nullptr;       // and its ARGB when the caller's output is host memory
-    size_t out_cap = 0;
-    ~TiffPipe() {
-        if (pin) (void)hipHostFree(pin);
-        for (void* p : {d_in, d_scratch, d_regions, d_out})
-            if (p) (void)hipFree(p);
+struct TiffSource final : omr::SegSource {
+    const omr_tiff_image* im;
+    size_t level;
+    TiffSource(const omr_tiff_image* img, int32_t lv) : im(img), level((size_t)lv) {
+        const Level& L = im->levels[level];
+        kind = omr::SegKind::tiff;
+        tag = "tiff";
+        noun = "segment";
+        geom.seg_w = L.seg_w; geom.seg_h = L.seg_h; geom.across = L.across; geom.down = L.down; geom.bpp = im->bpp;
+        codec = im->compression == 5 ? omr::SegCodec::lzw : omr::SegCodec::none;
+        predictor = im->predictor;
+        swap = im->big == host_little_endian();
+        pt = im->pt; big = im->big;
     }
-};
-
-void free_tiff_pipe(void* p) { delete static_cast<TiffPipe*>(p); }
-
-TiffPipe* get_tiff_pipe(omr::Ctx* c) {
-    if (!c->tiff_state) {
-        c->tiff_state = new TiffPipe;
-        c->tiff_state_free = free_tiff_pipe;
-    }
-    return static_cast<TiffPipe*>(c->tiff_state);
-}
-
-omr_status grow_device(omr::Ctx* c, void*& p, size_t& cap, size_t bytes) {
-    if (bytes <= cap) return OMR_OK;
-    if (p) OMR_HIP(c, hipFree(p));
-    p = nullptr;
-    cap = 0;
-    OMR_HIP(c, hipMalloc(&p, bytes));
-    cap = bytes;
-    return OMR_OK;
-}
-
-// job(i) for i in [0, n) on up to 16 threads (the calling one included).
-template <typename F>
-void parallel_for(int n, bool threaded, const F& job) {
-    const unsigned hw = std::thread::hardware_concurrency();
-    const int extra = threaded ? std::min<int>(n, (int)std::min(hw ? hw : 4u, 16u)) - 1 : 0;
-    std::atomic<int> next{0};
-    auto work = [&] {
-        for (int i; (i = next.fetch_add(1)) < n;) job(i);
-    };
-    std::vector<std::thread> th;
-    for (int k = 0; k < extra; ++k) th.emplace_back(work);
-    work();
-    for (auto& t : th) t.join();
-}
-
-struct UniqueSeg {
-    uint64_t off, cnt;
-    uint32_t expected;
-    uint64_t in_off = 0, scratch_off = 0;
-};
-
-constexpr size_t kGroupInBytes = (size_t)128 << 20;        // compressed bytes per group
-constexpr size_t kGroupScratchBytes = (size_t)512 << 20;   // decoded bytes per group
-constexpr size_t kRenderGroupBytes = (size_t)256 << 20;    // region bytes per render group
-
-// One group of regions: reqs[r0, r1).
-omr_status read_group(omr::Ctx* ctx, const omr_tiff_image* im, int32_t level, const omr_raw_tile_request* reqs, int32_t r0,
-                      int32_t r1, int32_t width, int32_t height, uint8_t* d_dst, int64_t stride) {
-    using omr::align_up;
-    using omr::TiffPlace;
-    const Level& L = im->levels[(size_t)level];
-    const bool lzw = im->compression == 5;
-    std::unordered_map<uint64_t, int32_t> index;      // plane * segments + k -> unique segment
-    std::vector<UniqueSeg> segs;
-    std::vector<TiffPlace> places;
-    std::vector<int32_t> place_seg;
-    const uint64_t per_plane = (uint64_t)L.across * L.down;
-    size_t in_bytes = 0, scratch_bytes = 0;
-    int32_t max_rows = 0;
-    for (int32_t i = r0; i < r1; ++i) {
-        const omr_raw_tile_request& r = reqs[i];
-        const Segments& S = im->segs[(size_t)plane_index(im, r.z, r.c, r.t)][(size_t)level];
-        for (int32_t sy = r.y / L.seg_h; sy <= (r.y + height - 1) / L.seg_h; ++sy)
-            for (int32_t sx = r.x / L.seg_w; sx <= (r.x + width - 1) / L.seg_w; ++sx) {
-                const uint64_t k = (uint64_t)sy * L.across + sx;
-                const uint64_t key = (uint64_t)plane_index(im, r.z, r.c, r.t) * per_plane + k;
-                auto it = index.find(key);
-                if (it == index.end()) {
-                    UniqueSeg u;
-                    u.off = S.off[(size_t)k];
-                    u.cnt = S.cnt[(size_t)k];
-                    u.expected = (uint32_t)((size_t)rows_in_segment(L, sy) * L.seg_w * im->bpp);
-                    if (u.cnt) {
-                        if (!lzw) u.cnt = u.expected;                 // the stored bytes we need
-                        u.in_off = in_bytes;
-                        in_bytes += align_up((size_t)u.cnt, 16);
-                        if (lzw) {
-                            u.scratch_off = scratch_bytes;
-                            scratch_bytes += align_up((size_t)u.expected, 16);
-                        }
-                    }
-                    it = index.emplace(key, (int32_t)segs.size()).first;
-                    segs.push_back(u);
-                }
-                const int32_t ox = sx * L.seg_w, oy = sy * L.seg_h;
-                const int32_t X0 = std::max(r.x, ox), X1 = std::min(r.x + width, ox + L.seg_w);
-                const int32_t Y0 = std::max(r.y, oy), Y1 = std::min(r.y + height, oy + L.seg_h);
-                TiffPlace p;
-                p.src = nullptr;
-                p.dst = d_dst + (int64_t)i * stride + ((int64_t)(Y0 - r.y) * width + (X0 - r.x)) * im->bpp;
-                p.seg_w = L.seg_w;
-                p.dst_pitch = width;
-                p.x0 = X0 - ox; p.x1 = X1 - ox; p.y0 = Y0 - oy; p.y1 = Y1 - oy;
-                max_rows = std::max(max_rows, Y1 - Y0);
-                places.push_back(p);
-                place_seg.push_back(it->second);
-            }
-    }
-    if (places.empty()) return OMR_OK;
-    std::vector<int32_t> coded;                        // the segments K13a decodes
-    if (lzw)
-        for (size_t k = 0; k < segs.size(); ++k)
-            if (segs[k].cnt) coded.push_back((int32_t)k);
-    const size_t m = coded.size();
-    // staging: [bytes][offsets u64 m][dst offsets u64 m][lengths u32 m][expected u32 m][places] | [status i32 m]
-    const size_t o_off = align_up(in_bytes, 256), o_dst = o_off + 8 * m, o_len = o_dst + 8 * m, o_exp = o_len + 4 * m;
-    const size_t o_place = align_up(o_exp + 4 * m, 16), up_bytes = o_place + places.size() * sizeof(TiffPlace);
-    const size_t o_status = align_up(up_bytes, 256), total = o_status + 4 * m;
-    TiffPipe* T = get_tiff_pipe(ctx);
-    if (total > T->in_cap) {
-        if (T->pin) OMR_HIP(ctx, hipHostFree(T->pin));
-        T->pin = nullptr;
-        const size_t keep = T->in_cap;
-        T->in_cap = 0;
-        omr_status st = grow_device(ctx, T->d_in, T->in_cap, std::max(total, keep + keep / 2));
-        if (st) return st;
-        const hipError_t e = hipHostMalloc(&T->pin, T->in_cap, hipHostMallocDefault);
-        if (e != hipSuccess) {
-            T->in_cap = 0;                               // both are made again on the next call
-            return omr::hip_fail(ctx, e, "hipHostMalloc(tiff staging)");
+    const Segments& table(const omr::SegKey& k) const { return im->segs[(size_t)k.plane][level]; }
+    size_t slot(const omr::SegKey& k) const { return (size_t)k.sy * geom.across + k.sx; }
+    int64_t plane_of(const omr_raw_tile_request& r) const override { return plane_index(im, r.z, r.c, r.t); }
+    omr_status sizes(omr::Ctx*, const std::vector<omr::SegKey>& keys, std::vector<omr::SegBytes>& out) override {
+        for (size_t k = 0; k < keys.size(); ++k) {
+            out[k].expected = (uint32_t)((size_t)rows_in_segment(im->levels[level], keys[k].sy) * geom.seg_w * geom.bpp);
+            out[k].cnt = table(keys[k]).cnt[slot(keys[k])];
+            if (out[k].cnt && codec == omr::SegCodec::none) out[k].cnt = out[k].expected;   // the stored bytes we need
         }
+        return OMR_OK;
     }
-    omr_status st = grow_device(ctx, T->d_scratch, T->scratch_cap, scratch_bytes);
-    if (st) return st;
-    uint8_t* pin = static_cast<uint8_t*>(T->pin);
-    uint8_t* din = static_cast<uint8_t*>(T->d_in);
-    uint8_t* dscr = static_cast<uint8_t*>(T->d_scratch);
-    std::atomic<bool> io_error{false};
-    parallel_for((int)segs.size(), in_bytes > ((size_t)4 << 20), [&](int k) {
-        const UniqueSeg& u = segs[(size_t)k];
-        if (u.cnt && !read_full(im->fd, pin + u.in_off, (size_t)u.cnt, u.off)) io_error = true;
-    });
-    if (io_error) return omr::fail(ctx, OMR_INTERNAL, "tiff: segment read failed");
-    uint64_t* h_off = reinterpret_cast<uint64_t*>(pin + o_off);
-    uint64_t* h_dst = reinterpret_cast<uint64_t*>(pin + o_dst);
-    uint32_t* h_len = reinterpret_cast<uint32_t*>(pin + o_len);
-    uint32_t* h_exp = reinterpret_cast<uint32_t*>(pin + o_exp);
-    for (size_t j = 0; j < m; ++j) {
-        const UniqueSeg& u = segs[(size_t)coded[j]];
-        h_off[j] = u.in_off;
-        h_dst[j] = u.scratch_off;
-        h_len[j] = (uint32_t)u.cnt;
-        h_exp[j] = u.expected;
+    bool read(const std::vector<omr::SegKey>& keys, const std::vector<omr::SegBytes>& segs, uint8_t* pin, size_t in_bytes) override {
+        std::atomic<bool> io_error{false};
+        omr::parallel_for((int)segs.size(), in_bytes > ((size_t)4 << 20), [&](int k) {
+            const omr::SegBytes& u = segs[(size_t)k];
+            const omr::SegKey& key = keys[(size_t)k];
+            if (u.cnt && !read_full(im->fd, pin + u.in_off, (size_t)u.cnt, table(key).off[slot(key)])) io_error = true;
+        });
+        return !io_error;
     }
-    TiffPlace* h_place = reinterpret_cast<TiffPlace*>(pin + o_place);
-    for (size_t k = 0; k < places.size(); ++k) {
-        const UniqueSeg& u = segs[(size_t)place_seg[k]];
-        places[k].src = !u.cnt ? nullptr : lzw ? dscr + u.scratch_off : din + u.in_off;
-        h_place[k] = places[k];
-    }
-    OMR_HIP(ctx, hipMemcpyAsync(din, pin, up_bytes, hipMemcpyHostToDevice, ctx->stream));
-    st = omr::launch_lzw_decode(ctx, din, reinterpret_cast<const uint64_t*>(din + o_off),
-                                reinterpret_cast<const uint32_t*>(din + o_len),
-                                reinterpret_cast<const uint32_t*>(din + o_exp), (int32_t)m, dscr,
-                                reinterpret_cast<const uint64_t*>(din + o_dst), reinterpret_cast<int32_t*>(din + o_status));
-    if (st) return st;
-    st = omr::launch_tiff_place(ctx, reinterpret_cast<const TiffPlace*>(din + o_place), (int32_t)places.size(), max_rows,
-                                im->bpp, im->predictor, im->big == host_little_endian());
-    if (st) return st;
-    if (m) OMR_HIP(ctx, hipMemcpyAsync(pin + o_status, din + o_status, 4 * m, hipMemcpyDeviceToHost, ctx->stream));
-    OMR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const int32_t* h_status = reinterpret_cast<const int32_t*>(pin + o_status);
-    for (size_t j = 0; j < m; ++j)
-        if (h_status[j] != OMR_OK) return omr::fail(ctx, OMR_INTERNAL, "tiff: corrupt LZW segment");
-    return OMR_OK;
-}
+};
 
 }  // namespace
 
@@ -735,18 +586,8 @@ omr_status omr_tiff_image_read_regions_device(omr_ctx* ctx, const omr_tiff_image
     for (int32_t i = 0; i < n; ++i)
         if (!region_in_bounds(img, L, reqs[i].z, reqs[i].c, reqs[i].t, reqs[i].x, reqs[i].y, width, height))
             return fail(ctx, OMR_INVALID_ARGUMENT, "tiff: region " + std::to_string(i) + " outside the image");
-    if (n == 0 || width == 0 || height == 0) return OMR_OK;
-    OMR_HIP(ctx, hipSetDevice(ctx->device));
-    // groups of requests within the staging budgets (a request's segments counted without sharing)
-    const size_t seg_dec = align_up((size_t)L.seg_w * L.seg_h * img->bpp, 16);
-    const size_t per_req = (size_t)((width - 1) / L.seg_w + 2) * (size_t)((height - 1) / L.seg_h + 2) * seg_dec;
-    const int32_t G = (int32_t)std::max<size_t>(1, std::min<size_t>((size_t)n, std::min(kGroupInBytes, kGroupScratchBytes) / per_req));
-    for (int32_t r0 = 0; r0 < n; r0 += G) {
-        const omr_status st = read_group(ctx, img, level, reqs, r0, std::min(n, r0 + G), width, height,
-                                         static_cast<uint8_t*>(d_dst), region_stride_bytes);
-        if (st) return st;
-    }
-    return OMR_OK;
+    TiffSource src(img, level);
+    return read_regions(ctx, src, reqs, n, width, height, d_dst, region_stride_bytes);
 }
 
 omr_status omr_render_tiff_tiles(omr_ctx* ctx, const omr_tiff_image* img, int32_t level, const omr_quantum_def* qdef,
@@ -758,51 +599,11 @@ omr_status omr_render_tiff_tiles(omr_ctx* ctx, const omr_tiff_image* img, int32_
     if (size_c != img->sc) return fail(ctx, OMR_INVALID_ARGUMENT, "channel bindings do not match the image's sizeC");
     if (width <= 0 || height <= 0) return fail(ctx, OMR_INVALID_ARGUMENT, "bad tile size");
     if (level < 0 || level >= (int32_t)img->levels.size()) return fail(ctx, OMR_INVALID_ARGUMENT, "tiff: no such level");
-    if (n == 0) return OMR_OK;
-    // the rendered channels, compacted: [tile][active channel][h][w] with their bindings in order
-    std::vector<int32_t> act;
-    std::vector<omr_channel_binding> bind;
-    for (int c = 0; c < size_c; ++c)
-        if (channels[c].active) {
-            if (qdef->model == OMR_MODEL_GREYSCALE && !act.empty()) break;   // first active only
-            act.push_back(c);
-            bind.push_back(channels[c]);
-        }
-    const int na = (int)act.size();
-    if (act.empty()) bind.assign(channels, channels + size_c);   // nothing to read: the render's own answer
-    OMR_HIP(ctx, hipSetDevice(ctx->device));
-    TiffPipe* T = get_tiff_pipe(ctx);
-    const size_t plane_al = align_up((size_t)width * height * img->bpp, 16);   // K2's vector path: 16-byte strides
-    const size_t tile_out = (size_t)width * height * 4;
-    const int32_t G = (int32_t)std::max<size_t>(1, std::min<size_t>((size_t)n, kRenderGroupBytes / (plane_al * std::max(na, 1))));
-    omr_status st = grow_device(ctx, T->d_regions, T->regions_cap, std::max<size_t>(16, plane_al * na * (size_t)G));
-    if (st) return st;
-    if (!out_on_device) {
-        st = grow_device(ctx, T->d_out, T->out_cap, tile_out * (size_t)G);
-        if (st) return st;
-    }
-    std::vector<omr_raw_tile_request> rr;
-    for (int32_t t0 = 0; t0 < n; t0 += G) {
-        const int32_t cnt = std::min(G, n - t0);
-        rr.clear();
-        for (int32_t i = 0; i < cnt; ++i)
-            for (int a = 0; a < na; ++a) rr.push_back({reqs[t0 + i].z, act[(size_t)a], reqs[t0 + i].t, reqs[t0 + i].x, reqs[t0 + i].y});
-        st = omr_tiff_image_read_regions_device(ctx, img, level, rr.data(), cnt * na, width, height, T->d_regions,
-                                                (int64_t)plane_al);
-        if (st) return st;
-        uint32_t* dout = out_on_device ? argb_out + (size_t)t0 * width * height : static_cast<uint32_t*>(T->d_out);
-        st = omr_render_batch_strided_device(ctx, qdef, bind.data(), (int32_t)bind.size(), T->d_regions, (int64_t)(plane_al * na),
-                                             (int64_t)plane_al, cnt, 0, img->pt, img->big, width, height, flip_h, flip_v,
-                                             dout, nullptr);
-        if (st) return st;
-        if (!out_on_device) {
-            st = omr_ctx_synchronize(ctx);
-            if (st) return st;
-            OMR_HIP(ctx, hipMemcpy(reinterpret_cast<uint8_t*>(argb_out) + (size_t)t0 * tile_out, dout,
-                                   tile_out * (size_t)cnt, hipMemcpyDeviceToHost));
-        }
-    }
-    return out_on_device ? omr_ctx_synchronize(ctx) : OMR_OK;
+    return render_tiles(ctx, TiffSource(img, level),
+                        [&](const omr_raw_tile_request* rr, int32_t count, void* d_dst, int64_t stride) {
+                            return omr_tiff_image_read_regions_device(ctx, img, level, rr, count, width, height, d_dst, stride);
+                        },
+                        qdef, channels, size_c, reqs, n, width, height, flip_h, flip_v, argb_out, out_on_device);
 }
 
 }  // extern "C"

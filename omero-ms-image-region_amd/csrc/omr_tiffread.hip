@@ -288,15 +288,13 @@ void launch_place_bps(const dim3& g, hipStream_t s, const TiffPlace* d_places, i
 
 }  // namespace
 
-omr_status launch_lzw_decode(Ctx* ctx, const uint8_t* d_src, const uint64_t* d_offsets, const uint32_t* d_lengths,
-                             const uint32_t* d_expected, int32_t n, uint8_t* d_dst, const uint64_t* d_dst_offsets,
-                             int32_t* d_status) {
-    if (n <= 0) return OMR_OK;
+omr_status launch_lzw_decode(Ctx* ctx, const StreamTable& t) {
+    if (t.n <= 0) return OMR_OK;
     // 20 KiB of LDS per wave: 8 waves per CU
-    const int blocks = std::min(n, std::max(1, ctx->cu_count) * 8);
+    const int blocks = std::min(t.n, std::max(1, ctx->cu_count) * 8);
     KernelTimer timer(ctx, kKindLzwDecode, true);
-    omr_launch(k_lzw_decode, dim3((unsigned)blocks), dim3(64), 0u, ctx->stream, d_src, d_offsets, d_lengths, d_expected,
-               (int)n, d_dst, d_dst_offsets, d_status);
+    omr_launch(k_lzw_decode, dim3((unsigned)blocks), dim3(64), 0u, ctx->stream, t.src, t.offsets, t.lengths, t.expected,
+               (int)t.n, t.dst, t.dst_offsets, t.status);
     OMR_HIP(ctx, hipGetLastError());
     return OMR_OK;
 }
@@ -333,5 +331,5 @@ extern "C" omr_status omr_lzw_decode_batch_device(omr_ctx* ctx, const uint8_t* d
     if (!d_src || !d_offsets || !d_lengths || !d_expected || !d_dst || !d_dst_offsets || !d_status)
         return fail(ctx, OMR_INVALID_ARGUMENT, "lzw: null argument");
     OMR_HIP(ctx, hipSetDevice(ctx->device));
-    return launch_lzw_decode(ctx, d_src, d_offsets, d_lengths, d_expected, n, d_dst, d_dst_offsets, d_status);
+    return launch_lzw_decode(ctx, {d_src, d_offsets, d_lengths, d_expected, nullptr, n, d_dst, d_dst_offsets, d_status});
 }

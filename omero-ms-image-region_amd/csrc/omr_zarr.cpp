@@ -5,39 +5,21 @@
 // reader of the metadata (.zattrs, .zarray: user-uploaded data, so it has a depth and a length
 // limit and never reads past its buffer), the image model, the plain serial inflate of the host
 // route (omr_inflate_host, omr_zarr_image_get_tile: the reference of the tests and the route of
-// single reads) and the staging of the device route: the chunks the requested regions touch are
-// listed once each, their files go to pinned memory and in one copy to the device with the chunk
-// table, K14a inflates them (omr_inflate.hip) and K13b places them (omr_tiffread.hip).  Blosc chunks
-// (K15, omr_zarr_image_open_ex) take the same staging: their container is read by omr_blosc.cpp, on
-// the device route into K15a's stream table, and K15b places them (omr_blosc.hip).  Zstandard (K16)
-// comes in both ways: as the inner codec of Blosc chunks, whose streams then go to K16a
-// (omr_zstd.hip) in a launch of their own, and as the bare zstd codec, which takes the zlib path
-// with K16a in place of K14a.
-#include "omr_internal.h"
+// single reads) and what the device route needs to know of a Zarr group (ZarrSource): a chunk's
+// path, the stat pass that sizes the chunk files, and the read of one file per chunk.  The device
+// route itself -- staging, planning, the launches of K14a (zlib), K16a (zstd) and, for Blosc chunks
+// (K15, omr_zarr_image_open_ex), of K15a, K16a and K15b behind omr_blosc.cpp's container parser,
+// the tile renderer -- is omr_segread.cpp, shared with the TIFF reader; this file calls no HIP
+// function.
+#include "omr_segread.h"
 
 #include <dirent.h>
 #include <fcntl.h>
 #include <sys/stat.h>
 #include <unistd.h>
 
-#include <atomic>
 #include <cerrno>
 #include <memory>
-#include <thread>
-#include <unordered_map>
-
-// The stand-alone host checks link this file without the kernels: the Blosc launches may be absent.
-namespace omr {
-omr_status launch_lz4_decode(Ctx* ctx, const uint8_t* d_src, const uint64_t* d_offsets, const uint32_t* d_lengths,
-                             const uint32_t* d_expected, const uint8_t* d_raw, int32_t n, uint8_t* d_dst,
-                             const uint64_t* d_dst_offsets, int32_t* d_status) __attribute__((weak));
-omr_status launch_blosc_place(Ctx* ctx, const BloscPlace* d_places, int32_t n, int32_t max_rows, int32_t bps)
-    __attribute__((weak));
-omr_status launch_zstd_decode(Ctx* ctx, const uint8_t* d_src, const uint64_t* d_offsets, const uint32_t* d_lengths,
-                              const uint32_t* d_expected, const uint8_t* d_raw, int32_t n, uint8_t* d_dst,
-                              const uint64_t* d_dst_offsets, int32_t* d_status, void** lit, size_t* lit_cap)
-    __attribute__((weak));
-}  // namespace omr
 
 namespace {
 
@@ -620,342 +602,73 @@ omr_status load_chunk(const omr_zarr_image* im, const Level& L, int32_t t, int32
     return inflate(comp.data(), comp.size(), out.data(), expected) ? OMR_OK : OMR_INTERNAL;
 }
 
-// ---- device route: staging of one context -------------------------------------------------------
+// ---- device route: what the shared pipeline (omr_segread.h) asks of a Zarr group ----------------------
 
-struct ZarrPipe {
-    void* pin = nullptr;      // chunk files + tables (+ the statuses coming back)
-    void* d_in = nullptr;
-    size_t in_cap = 0;
-    void* d_scratch = nullptr;   // inflated chunks
-    size_t scratch_cap = 0;
-    void* d_regions = nullptr;   // omr_render_zarr_tiles: [tile][channel][h][w]
-    size_t regions_cap = 0;
-    void* d_out = nullptr;       // and its ARGB when the caller's output is host memory
-    size_t out_cap = 0;
-    void* pin_tab = nullptr;     // Blosc: the stream table and the placements, sized after the files are read
-    void* d_tab = nullptr;
-    size_t tab_cap = 0;
-    void* d_lit = nullptr;       // K16a: one literal buffer per workgroup of its grid
-    size_t lit_cap = 0;
-    ~ZarrPipe() {
-        if (pin) (void)hipHostFree(pin);
-        if (pin_tab) (void)hipHostFree(pin_tab);
-        for (void* p : {d_in, d_scratch, d_regions, d_out, d_tab, d_lit})
-            if (p) (void)hipFree(p);
+struct ZarrSource final : omr::SegSource {
+    const omr_zarr_image* im;
+    const Level& L;
+    std::vector<std::string> paths;      // of the group's chunks, from sizes() to read()
+    ZarrSource(const omr_zarr_image* img, int32_t level) : im(img), L(img->levels[(size_t)level]) {
+        kind = omr::SegKind::zarr;
+        tag = "zarr";
+        noun = "chunk";
+        geom.seg_w = L.cw; geom.seg_h = L.ch; geom.across = L.across; geom.down = L.down; geom.bpp = im->bpp;
+        codec = im->comp == kZlib ? omr::SegCodec::zlib : im->comp == kZstd ? omr::SegCodec::zstd
+                : im->comp == kBlosc ? omr::SegCodec::blosc : omr::SegCodec::none;
+        blosc_inner = im->inner;
+        pt = im->pt; big = im->big;
     }
-};
-
-void free_zarr_pipe(void* p) { delete static_cast<ZarrPipe*>(p); }
-
-ZarrPipe* get_zarr_pipe(omr::Ctx* c) {
-    if (!c->zarr_state) {
-        c->zarr_state = new ZarrPipe;
-        c->zarr_state_free = free_zarr_pipe;
-    }
-    return static_cast<ZarrPipe*>(c->zarr_state);
-}
-
-omr_status grow_device(omr::Ctx* c, void*& p, size_t& cap, size_t bytes) {
-    if (bytes <= cap) return OMR_OK;
-    if (p) OMR_HIP(c, hipFree(p));
-    p = nullptr;
-    cap = 0;
-    OMR_HIP(c, hipMalloc(&p, bytes));
-    cap = bytes;
-    return OMR_OK;
-}
-
-// job(i) for i in [0, n) on up to 16 threads (the calling one included).
-template <typename F>
-void parallel_for(int n, bool threaded, const F& job) {
-    const unsigned hw = std::thread::hardware_concurrency();
-    const int extra = threaded ? std::min<int>(n, (int)std::min(hw ? hw : 4u, 16u)) - 1 : 0;
-    std::atomic<int> next{0};
-    auto work = [&] {
-        for (int i; (i = next.fetch_add(1)) < n;) job(i);
-    };
-    std::vector<std::thread> th;
-    for (int k = 0; k < extra; ++k) th.emplace_back(work);
-    work();
-    for (auto& t : th) t.join();
-}
-
-struct UniqueChunk {
-    std::string path;
-    uint64_t cnt = 0;            // file size; 0: the chunk is missing
-    uint64_t in_off = 0, scratch_off = 0;
-};
-
-constexpr size_t kGroupInBytes = (size_t)128 << 20;        // chunk file bytes per group (as K13)
-constexpr size_t kGroupScratchBytes = (size_t)512 << 20;   // decoded bytes per group
-constexpr size_t kRenderGroupBytes = (size_t)256 << 20;    // region bytes per render group
-
-// The Blosc half of read_group, from the chunk files in pinned memory on: the host checks every
-// chunk's container and lists its streams (a bad one ends the call before any launch), the bytes go
-// up, the tables behind them in a copy of their own (their size is known only now), K15a decodes
-// the streams into the chunks' scratch and K15b places with the un-shuffle in its loads.
-omr_status finish_blosc(omr::Ctx* ctx, ZarrPipe* T, const std::vector<UniqueChunk>& chunks,
-                        const std::vector<omr::TiffPlace>& places, const std::vector<int32_t>& place_chunk,
-                        uint32_t expected, size_t in_bytes, int32_t max_rows, int32_t bpp, uint32_t inner) {
-    using omr::align_up;
-    using omr::BloscPlace;
-    if (!omr::launch_lz4_decode || !omr::launch_blosc_place || !omr::launch_zstd_decode)
-        return omr::fail(ctx, OMR_DEVICE, "zarr: built without the Blosc kernels");
-    uint8_t* pin = static_cast<uint8_t*>(T->pin);
-    uint8_t* din = static_cast<uint8_t*>(T->d_in);
-    uint8_t* dscr = static_cast<uint8_t*>(T->d_scratch);
-    std::vector<omr::BloscLayout> layouts(chunks.size());
-    size_t m = 0, m_lz4 = 0;                               // streams; those of LZ4 chunks come first in the tables
-    for (size_t k = 0; k < chunks.size(); ++k) {
-        const UniqueChunk& u = chunks[k];
-        if (!u.cnt) continue;
-        if (!omr::blosc_parse(pin + u.in_off, (size_t)u.cnt, expected, layouts[k], inner))
-            return omr::fail(ctx, OMR_INTERNAL, "zarr: corrupt blosc chunk");
-        m += layouts[k].streams.size();
-        if (layouts[k].format != 4u) m_lz4 += layouts[k].streams.size();
-    }
-    // tables: [offsets u64 m][dst offsets u64 m][lengths u32 m][expected u32 m][raw u8 m][places] | [status i32 m]
-    const size_t o_dst = 8 * m, o_len = o_dst + 8 * m, o_exp = o_len + 4 * m, o_raw = o_exp + 4 * m;
-    const size_t o_place = align_up(o_raw + m, 16), up_bytes = o_place + places.size() * sizeof(BloscPlace);
-    const size_t o_status = align_up(up_bytes, 256), total = o_status + 4 * m;
-    if (total > T->tab_cap) {
-        if (T->pin_tab) OMR_HIP(ctx, hipHostFree(T->pin_tab));
-        T->pin_tab = nullptr;
-        const size_t keep = T->tab_cap;
-        T->tab_cap = 0;
-        omr_status st = grow_device(ctx, T->d_tab, T->tab_cap, std::max(total, keep + keep / 2));
-        if (st) return st;
-        const hipError_t e = hipHostMalloc(&T->pin_tab, T->tab_cap, hipHostMallocDefault);
-        if (e != hipSuccess) {
-            T->tab_cap = 0;                              // both are made again on the next call
-            return omr::hip_fail(ctx, e, "hipHostMalloc(zarr tables)");
-        }
-    }
-    uint8_t* tab = static_cast<uint8_t*>(T->pin_tab);
-    uint8_t* dtab = static_cast<uint8_t*>(T->d_tab);
-    uint64_t* h_off = reinterpret_cast<uint64_t*>(tab);
-    uint64_t* h_dst = reinterpret_cast<uint64_t*>(tab + o_dst);
-    uint32_t* h_len = reinterpret_cast<uint32_t*>(tab + o_len);
-    uint32_t* h_exp = reinterpret_cast<uint32_t*>(tab + o_exp);
-    uint8_t* h_raw = tab + o_raw;
-    size_t j_lz4 = 0, j_zstd = m_lz4;                      // a stored split goes with its chunk's launch
-    for (size_t k = 0; k < chunks.size(); ++k)
-        for (const omr::BloscStream& s : layouts[k].streams) {
-            const size_t j = layouts[k].format != 4u ? j_lz4++ : j_zstd++;
-            h_off[j] = chunks[k].in_off + s.src_off;
-            h_dst[j] = chunks[k].scratch_off + s.dst_off;
-            h_len[j] = s.csize;
-            h_exp[j] = s.neblock;
-            h_raw[j] = s.raw;
-        }
-    BloscPlace* h_place = reinterpret_cast<BloscPlace*>(tab + o_place);
-    for (size_t k = 0; k < places.size(); ++k) {
-        const size_t ck = (size_t)place_chunk[k];
-        const UniqueChunk& u = chunks[ck];
-        const omr::BloscLayout& L = layouts[ck];
-        const omr::TiffPlace& p = places[k];
-        BloscPlace b;
-        b.src = !u.cnt ? nullptr : L.memcpyed ? din + u.in_off + 16 : dscr + u.scratch_off;
-        b.dst = p.dst;
-        b.seg_w = p.seg_w; b.dst_pitch = p.dst_pitch;
-        b.x0 = p.x0; b.x1 = p.x1; b.y0 = p.y0; b.y1 = p.y1;
-        b.blocksize = L.blocksize; b.nbytes = L.nbytes; b.typesize = L.typesize;
-        b.shuffled = u.cnt && L.shuffled && !L.memcpyed;
-        h_place[k] = b;
-    }
-    if (in_bytes) OMR_HIP(ctx, hipMemcpyAsync(din, pin, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-    OMR_HIP(ctx, hipMemcpyAsync(dtab, tab, up_bytes, hipMemcpyHostToDevice, ctx->stream));
-    omr_status st = omr::launch_lz4_decode(ctx, din, reinterpret_cast<const uint64_t*>(dtab),
-                                           reinterpret_cast<const uint32_t*>(dtab + o_len),
-                                           reinterpret_cast<const uint32_t*>(dtab + o_exp), dtab + o_raw, (int32_t)m_lz4, dscr,
-                                           reinterpret_cast<const uint64_t*>(dtab + o_dst),
-                                           reinterpret_cast<int32_t*>(dtab + o_status));
-    if (st) return st;
-    st = omr::launch_zstd_decode(ctx, din, reinterpret_cast<const uint64_t*>(dtab) + m_lz4,
-                                 reinterpret_cast<const uint32_t*>(dtab + o_len) + m_lz4,
-                                 reinterpret_cast<const uint32_t*>(dtab + o_exp) + m_lz4, dtab + o_raw + m_lz4,
-                                 (int32_t)(m - m_lz4), dscr, reinterpret_cast<const uint64_t*>(dtab + o_dst) + m_lz4,
-                                 reinterpret_cast<int32_t*>(dtab + o_status) + m_lz4, &T->d_lit, &T->lit_cap);
-    if (st) return st;
-    st = omr::launch_blosc_place(ctx, reinterpret_cast<const BloscPlace*>(dtab + o_place), (int32_t)places.size(), max_rows, bpp);
-    if (st) return st;
-    if (m) OMR_HIP(ctx, hipMemcpyAsync(tab + o_status, dtab + o_status, 4 * m, hipMemcpyDeviceToHost, ctx->stream));
-    OMR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const int32_t* h_status = reinterpret_cast<const int32_t*>(tab + o_status);
-    for (size_t i = 0; i < m; ++i)
-        if (h_status[i] != OMR_OK) return omr::fail(ctx, OMR_INTERNAL, "zarr: corrupt blosc chunk");
-    return OMR_OK;
-}
-
-// One group of regions: reqs[r0, r1).
-omr_status read_group(omr::Ctx* ctx, const omr_zarr_image* im, int32_t level, const omr_raw_tile_request* reqs, int32_t r0,
-                      int32_t r1, int32_t width, int32_t height, uint8_t* d_dst, int64_t stride) {
-    using omr::align_up;
-    using omr::TiffPlace;
-    const Level& L = im->levels[(size_t)level];
-    const uint32_t expected = (uint32_t)((size_t)L.ch * L.cw * im->bpp);
-    std::unordered_map<uint64_t, int32_t> index;      // plane * chunks + k -> unique chunk
-    std::vector<UniqueChunk> chunks;
-    std::vector<TiffPlace> places;
-    std::vector<int32_t> place_chunk;
-    const uint64_t per_plane = (uint64_t)L.across * L.down;
-    int32_t max_rows = 0;
-    for (int32_t i = r0; i < r1; ++i) {
-        const omr_raw_tile_request& r = reqs[i];
-        const uint64_t plane = ((uint64_t)r.t * im->sc + r.c) * im->sz + r.z;
-        for (int32_t cy = r.y / L.ch; cy <= (r.y + height - 1) / L.ch; ++cy)
-            for (int32_t cx = r.x / L.cw; cx <= (r.x + width - 1) / L.cw; ++cx) {
-                const uint64_t key = plane * per_plane + (uint64_t)cy * L.across + cx;
-                auto it = index.find(key);
-                if (it == index.end()) {
-                    UniqueChunk u;
-                    u.path = chunk_path(L, r.t, r.c, r.z, cy, cx);
-                    it = index.emplace(key, (int32_t)chunks.size()).first;
-                    chunks.push_back(std::move(u));
-                }
-                const int32_t ox = cx * L.cw, oy = cy * L.ch;
-                const int32_t X0 = std::max(r.x, ox), X1 = std::min(r.x + width, ox + L.cw);
-                const int32_t Y0 = std::max(r.y, oy), Y1 = std::min(r.y + height, oy + L.ch);
-                TiffPlace p;
-                p.src = nullptr;
-                p.dst = d_dst + (int64_t)i * stride + ((int64_t)(Y0 - r.y) * width + (X0 - r.x)) * im->bpp;
-                p.seg_w = L.cw;
-                p.dst_pitch = width;
-                p.x0 = X0 - ox; p.x1 = X1 - ox; p.y0 = Y0 - oy; p.y1 = Y1 - oy;
-                max_rows = std::max(max_rows, Y1 - Y0);
-                places.push_back(p);
-                place_chunk.push_back(it->second);
-            }
-    }
-    if (places.empty()) return OMR_OK;
+    bool threaded(size_t chunks) const { return chunks >= 32; }
+    int64_t plane_of(const omr_raw_tile_request& r) const override { return ((int64_t)r.t * im->sc + r.c) * im->sz + r.z; }
     // the sizes of the chunk files (a file per chunk: nothing but the file system knows them)
-    const bool threaded = chunks.size() >= 32;
-    std::atomic<int> bad{0};                               // 1: I/O error, 2: a file of the wrong size
-    parallel_for((int)chunks.size(), threaded, [&](int k) {
-        UniqueChunk& u = chunks[(size_t)k];
-        struct stat sb;
-        if (::stat(u.path.c_str(), &sb) != 0) {
-            if (errno != ENOENT && errno != ENOTDIR) bad = 1;
-            return;
-        }
-        if (!S_ISREG(sb.st_mode)) bad = 1;
-        else if (im->comp != kNone ? (uint64_t)sb.st_size > kMaxStreamBytes || sb.st_size == 0 : (uint64_t)sb.st_size != expected) bad = 2;
-        else u.cnt = (uint64_t)sb.st_size;
-    });
-    if (bad == 1) return omr::fail(ctx, OMR_INTERNAL, "zarr: chunk file cannot be read");
-    if (bad == 2) return omr::fail(ctx, OMR_INTERNAL, "zarr: chunk file of the wrong size");
-    size_t in_bytes = 0, scratch_bytes = 0;
-    std::vector<int32_t> coded;                        // the chunks K14a inflates, or K16a decodes
-    for (size_t k = 0; k < chunks.size(); ++k) {
-        UniqueChunk& u = chunks[k];
-        if (!u.cnt) continue;
-        u.in_off = in_bytes;
-        in_bytes += align_up((size_t)u.cnt, 16);
-        if (im->comp != kNone) {
-            u.scratch_off = scratch_bytes;
-            scratch_bytes += align_up((size_t)expected, 16);
-            if (im->comp == kZlib || im->comp == kZstd) coded.push_back((int32_t)k);
-        }
+    omr_status sizes(omr::Ctx* ctx, const std::vector<omr::SegKey>& keys, std::vector<omr::SegBytes>& out) override {
+        const uint32_t expected = (uint32_t)((size_t)L.ch * L.cw * im->bpp);
+        paths.resize(keys.size());
+        std::atomic<int> bad{0};                               // 1: I/O error, 2: a file of the wrong size
+        omr::parallel_for((int)keys.size(), threaded(keys.size()), [&](int k) {
+            const omr::SegKey& key = keys[(size_t)k];
+            const int64_t zc = key.plane / im->sz;
+            paths[(size_t)k] = chunk_path(L, (int32_t)(zc / im->sc), (int32_t)(zc % im->sc), (int32_t)(key.plane % im->sz), key.sy, key.sx);
+            out[(size_t)k].expected = expected;
+            struct stat sb;
+            if (::stat(paths[(size_t)k].c_str(), &sb) != 0) {
+                if (errno != ENOENT && errno != ENOTDIR) bad = 1;
+                return;
+            }
+            if (!S_ISREG(sb.st_mode)) bad = 1;
+            else if (im->comp != kNone ? (uint64_t)sb.st_size > kMaxStreamBytes || sb.st_size == 0 : (uint64_t)sb.st_size != expected) bad = 2;
+            else out[(size_t)k].cnt = (uint64_t)sb.st_size;
+        });
+        if (bad == 1) return omr::fail(ctx, OMR_INTERNAL, "zarr: chunk file cannot be read");
+        if (bad == 2) return omr::fail(ctx, OMR_INTERNAL, "zarr: chunk file of the wrong size");
+        return OMR_OK;
     }
-    const bool blosc = im->comp == kBlosc;                 // its tables go up behind the bytes, from T->pin_tab
-    const size_t m = coded.size();
-    // staging: [bytes][offsets u64 m][dst offsets u64 m][lengths u32 m][expected u32 m][places] | [status i32 m]
-    const size_t o_off = align_up(in_bytes, 256), o_dst = o_off + 8 * m, o_len = o_dst + 8 * m, o_exp = o_len + 4 * m;
-    const size_t o_place = align_up(o_exp + 4 * m, 16), up_bytes = o_place + (blosc ? 0 : places.size() * sizeof(TiffPlace));
-    const size_t o_status = align_up(up_bytes, 256), total = o_status + 4 * m;
-    ZarrPipe* T = get_zarr_pipe(ctx);
-    if (total > T->in_cap) {
-        if (T->pin) OMR_HIP(ctx, hipHostFree(T->pin));
-        T->pin = nullptr;
-        const size_t keep = T->in_cap;
-        T->in_cap = 0;
-        omr_status st = grow_device(ctx, T->d_in, T->in_cap, std::max(total, keep + keep / 2));
-        if (st) return st;
-        const hipError_t e = hipHostMalloc(&T->pin, T->in_cap, hipHostMallocDefault);
-        if (e != hipSuccess) {
-            T->in_cap = 0;                               // both are made again on the next call
-            return omr::hip_fail(ctx, e, "hipHostMalloc(zarr staging)");
-        }
+    bool read(const std::vector<omr::SegKey>&, const std::vector<omr::SegBytes>& segs, uint8_t* pin, size_t) override {
+        std::atomic<bool> io_error{false};
+        omr::parallel_for((int)segs.size(), threaded(segs.size()), [&](int k) {
+            const omr::SegBytes& u = segs[(size_t)k];
+            if (!u.cnt) return;
+            const int fd = ::open(paths[(size_t)k].c_str(), O_RDONLY | O_CLOEXEC);
+            if (fd < 0) {
+                io_error = true;
+                return;
+            }
+            size_t got = 0;
+            while (got < u.cnt) {                              // a file that shrank since the stat is an error
+                const ssize_t r = ::pread(fd, pin + u.in_off + got, (size_t)u.cnt - got, (off_t)got);
+                if (r < 0 && errno == EINTR) continue;
+                if (r <= 0) break;
+                got += (size_t)r;
+            }
+            ::close(fd);
+            if (got != u.cnt) io_error = true;
+        });
+        return !io_error;
     }
-    omr_status st = grow_device(ctx, T->d_scratch, T->scratch_cap, scratch_bytes);
-    if (st) return st;
-    uint8_t* pin = static_cast<uint8_t*>(T->pin);
-    uint8_t* din = static_cast<uint8_t*>(T->d_in);
-    uint8_t* dscr = static_cast<uint8_t*>(T->d_scratch);
-    std::atomic<bool> io_error{false};
-    parallel_for((int)chunks.size(), threaded, [&](int k) {
-        const UniqueChunk& u = chunks[(size_t)k];
-        if (!u.cnt) return;
-        const int fd = ::open(u.path.c_str(), O_RDONLY | O_CLOEXEC);
-        if (fd < 0) {
-            io_error = true;
-            return;
-        }
-        size_t got = 0;
-        while (got < u.cnt) {                              // a file that shrank since the stat is an error
-            const ssize_t r = ::pread(fd, pin + u.in_off + got, (size_t)u.cnt - got, (off_t)got);
-            if (r < 0 && errno == EINTR) continue;
-            if (r <= 0) break;
-            got += (size_t)r;
-        }
-        ::close(fd);
-        if (got != u.cnt) io_error = true;
-    });
-    if (io_error) return omr::fail(ctx, OMR_INTERNAL, "zarr: chunk read failed");
-    if (blosc) return finish_blosc(ctx, T, chunks, places, place_chunk, expected, in_bytes, max_rows, im->bpp, im->inner);
-    uint64_t* h_off = reinterpret_cast<uint64_t*>(pin + o_off);
-    uint64_t* h_dst = reinterpret_cast<uint64_t*>(pin + o_dst);
-    uint32_t* h_len = reinterpret_cast<uint32_t*>(pin + o_len);
-    uint32_t* h_exp = reinterpret_cast<uint32_t*>(pin + o_exp);
-    for (size_t j = 0; j < m; ++j) {
-        const UniqueChunk& u = chunks[(size_t)coded[j]];
-        h_off[j] = u.in_off;
-        h_dst[j] = u.scratch_off;
-        h_len[j] = (uint32_t)u.cnt;
-        h_exp[j] = expected;
-    }
-    TiffPlace* h_place = reinterpret_cast<TiffPlace*>(pin + o_place);
-    for (size_t k = 0; k < places.size(); ++k) {
-        const UniqueChunk& u = chunks[(size_t)place_chunk[k]];
-        places[k].src = !u.cnt ? nullptr : im->comp != kNone ? dscr + u.scratch_off : din + u.in_off;
-        h_place[k] = places[k];
-    }
-    OMR_HIP(ctx, hipMemcpyAsync(din, pin, up_bytes, hipMemcpyHostToDevice, ctx->stream));
-    if (im->comp == kZstd) {
-        if (!omr::launch_zstd_decode) return omr::fail(ctx, OMR_DEVICE, "zarr: built without the Zstandard kernel");
-        st = omr::launch_zstd_decode(ctx, din, reinterpret_cast<const uint64_t*>(din + o_off),
-                                     reinterpret_cast<const uint32_t*>(din + o_len), reinterpret_cast<const uint32_t*>(din + o_exp),
-                                     nullptr, (int32_t)m, dscr, reinterpret_cast<const uint64_t*>(din + o_dst),
-                                     reinterpret_cast<int32_t*>(din + o_status), &T->d_lit, &T->lit_cap);
-    } else {
-        st = omr::launch_inflate(ctx, din, reinterpret_cast<const uint64_t*>(din + o_off),
-                                 reinterpret_cast<const uint32_t*>(din + o_len), reinterpret_cast<const uint32_t*>(din + o_exp),
-                                 (int32_t)m, dscr, reinterpret_cast<const uint64_t*>(din + o_dst),
-                                 reinterpret_cast<int32_t*>(din + o_status));
-    }
-    if (st) return st;
-    st = omr::launch_tiff_place(ctx, reinterpret_cast<const TiffPlace*>(din + o_place), (int32_t)places.size(), max_rows,
-                                im->bpp, 1, false);
-    if (st) return st;
-    if (m) OMR_HIP(ctx, hipMemcpyAsync(pin + o_status, din + o_status, 4 * m, hipMemcpyDeviceToHost, ctx->stream));
-    OMR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const int32_t* h_status = reinterpret_cast<const int32_t*>(pin + o_status);
-    for (size_t j = 0; j < m; ++j)
-        if (h_status[j] != OMR_OK)
-            return omr::fail(ctx, OMR_INTERNAL, im->comp == kZstd ? "zarr: corrupt zstd chunk" : "zarr: corrupt zlib chunk");
-    return OMR_OK;
-}
+};
 
 }  // namespace
 
-namespace omr {
-omr_status zarr_zstd_literals(Ctx* ctx, void*** lit, size_t** lit_cap) {
-    ZarrPipe* T = get_zarr_pipe(ctx);
-    *lit = &T->d_lit;
-    *lit_cap = &T->lit_cap;
-    return OMR_OK;
-}
-}  // namespace omr
 
 using namespace omr;
 
@@ -1099,18 +812,8 @@ omr_status omr_zarr_image_read_regions_device(omr_ctx* ctx, const omr_zarr_image
     for (int32_t i = 0; i < n; ++i)
         if (!region_in_bounds(img, L, reqs[i].z, reqs[i].c, reqs[i].t, reqs[i].x, reqs[i].y, width, height))
             return fail(ctx, OMR_INVALID_ARGUMENT, "zarr: region " + std::to_string(i) + " outside the image");
-    if (n == 0 || width == 0 || height == 0) return OMR_OK;
-    OMR_HIP(ctx, hipSetDevice(ctx->device));
-    // groups of requests within the staging budgets (a request's chunks counted without sharing)
-    const size_t chunk_dec = align_up((size_t)L.cw * L.ch * img->bpp, 16);
-    const size_t per_req = (size_t)((width - 1) / L.cw + 2) * (size_t)((height - 1) / L.ch + 2) * chunk_dec;
-    const int32_t G = (int32_t)std::max<size_t>(1, std::min<size_t>((size_t)n, std::min(kGroupInBytes, kGroupScratchBytes) / per_req));
-    for (int32_t r0 = 0; r0 < n; r0 += G) {
-        const omr_status st = read_group(ctx, img, level, reqs, r0, std::min(n, r0 + G), width, height,
-                                         static_cast<uint8_t*>(d_dst), region_stride_bytes);
-        if (st) return st;
-    }
-    return OMR_OK;
+    ZarrSource src(img, level);
+    return read_regions(ctx, src, reqs, n, width, height, d_dst, region_stride_bytes);
 }
 
 omr_status omr_render_zarr_tiles(omr_ctx* ctx, const omr_zarr_image* img, int32_t level, const omr_quantum_def* qdef,
@@ -1122,51 +825,11 @@ omr_status omr_render_zarr_tiles(omr_ctx* ctx, const omr_zarr_image* img, int32_
     if (size_c != img->sc) return fail(ctx, OMR_INVALID_ARGUMENT, "channel bindings do not match the image's sizeC");
     if (width <= 0 || height <= 0) return fail(ctx, OMR_INVALID_ARGUMENT, "bad tile size");
     if (level < 0 || level >= (int32_t)img->levels.size()) return fail(ctx, OMR_INVALID_ARGUMENT, "zarr: no such level");
-    if (n == 0) return OMR_OK;
-    // the rendered channels, compacted: [tile][active channel][h][w] with their bindings in order
-    std::vector<int32_t> act;
-    std::vector<omr_channel_binding> bind;
-    for (int c = 0; c < size_c; ++c)
-        if (channels[c].active) {
-            if (qdef->model == OMR_MODEL_GREYSCALE && !act.empty()) break;   // first active only
-            act.push_back(c);
-            bind.push_back(channels[c]);
-        }
-    const int na = (int)act.size();
-    if (act.empty()) bind.assign(channels, channels + size_c);   // nothing to read: the render's own answer
-    OMR_HIP(ctx, hipSetDevice(ctx->device));
-    ZarrPipe* T = get_zarr_pipe(ctx);
-    const size_t plane_al = align_up((size_t)width * height * img->bpp, 16);   // K2's vector path: 16-byte strides
-    const size_t tile_out = (size_t)width * height * 4;
-    const int32_t G = (int32_t)std::max<size_t>(1, std::min<size_t>((size_t)n, kRenderGroupBytes / (plane_al * std::max(na, 1))));
-    omr_status st = grow_device(ctx, T->d_regions, T->regions_cap, std::max<size_t>(16, plane_al * na * (size_t)G));
-    if (st) return st;
-    if (!out_on_device) {
-        st = grow_device(ctx, T->d_out, T->out_cap, tile_out * (size_t)G);
-        if (st) return st;
-    }
-    std::vector<omr_raw_tile_request> rr;
-    for (int32_t t0 = 0; t0 < n; t0 += G) {
-        const int32_t cnt = std::min(G, n - t0);
-        rr.clear();
-        for (int32_t i = 0; i < cnt; ++i)
-            for (int a = 0; a < na; ++a) rr.push_back({reqs[t0 + i].z, act[(size_t)a], reqs[t0 + i].t, reqs[t0 + i].x, reqs[t0 + i].y});
-        st = omr_zarr_image_read_regions_device(ctx, img, level, rr.data(), cnt * na, width, height, T->d_regions,
-                                                (int64_t)plane_al);
-        if (st) return st;
-        uint32_t* dout = out_on_device ? argb_out + (size_t)t0 * width * height : static_cast<uint32_t*>(T->d_out);
-        st = omr_render_batch_strided_device(ctx, qdef, bind.data(), (int32_t)bind.size(), T->d_regions, (int64_t)(plane_al * na),
-                                             (int64_t)plane_al, cnt, 0, img->pt, img->big, width, height, flip_h, flip_v,
-                                             dout, nullptr);
-        if (st) return st;
-        if (!out_on_device) {
-            st = omr_ctx_synchronize(ctx);
-            if (st) return st;
-            OMR_HIP(ctx, hipMemcpy(reinterpret_cast<uint8_t*>(argb_out) + (size_t)t0 * tile_out, dout,
-                                   tile_out * (size_t)cnt, hipMemcpyDeviceToHost));
-        }
-    }
-    return out_on_device ? omr_ctx_synchronize(ctx) : OMR_OK;
+    return render_tiles(ctx, ZarrSource(img, level),
+                        [&](const omr_raw_tile_request* rr, int32_t count, void* d_dst, int64_t stride) {
+                            return omr_zarr_image_read_regions_device(ctx, img, level, rr, count, width, height, d_dst, stride);
+                        },
+                        qdef, channels, size_c, reqs, n, width, height, flip_h, flip_v, argb_out, out_on_device);
 }
 
 }  // extern "C"

@@ -43,7 +43,7 @@
 //    readlane broadcasts of lane 0's results and ballots;
 //  - a bad frame sets status[i] = OMR_INTERNAL and ends that frame only; what was accepted before
 //    may have been stored (inside the slot).
-#include "omr_internal.h"
+#include "omr_segread.h"
 #include "omr_wave.h"
 
 namespace omr {
@@ -809,13 +809,11 @@ __global__ void __launch_bounds__(64) k_zstd_decode(const uint8_t* __restrict__ 
 
 }  // namespace
 
-omr_status launch_zstd_decode(Ctx* ctx, const uint8_t* d_src, const uint64_t* d_offsets, const uint32_t* d_lengths,
-                              const uint32_t* d_expected, const uint8_t* d_raw, int32_t n, uint8_t* d_dst,
-                              const uint64_t* d_dst_offsets, int32_t* d_status, void** lit, size_t* lit_cap) {
-    if (n <= 0) return OMR_OK;
+omr_status launch_zstd_decode(Ctx* ctx, const StreamTable& t, void** lit, size_t* lit_cap) {
+    if (t.n <= 0) return OMR_OK;
     // 11 KiB of LDS per wave would admit 14 workgroups per CU; 8 keep the literal buffers (128 KiB
     // each) at 256 MiB for a full grid
-    const int blocks = std::min(n, std::max(1, ctx->cu_count) * 8);
+    const int blocks = std::min(t.n, std::max(1, ctx->cu_count) * 8);
     const size_t need = (size_t)blocks * kZBlockMax;
     if (need > *lit_cap) {
         if (*lit) OMR_HIP(ctx, hipFree(*lit));
@@ -825,8 +823,8 @@ omr_status launch_zstd_decode(Ctx* ctx, const uint8_t* d_src, const uint64_t* d_
         *lit_cap = need;
     }
     KernelTimer timer(ctx, kKindZstdDecode, true);
-    omr_launch(k_zstd_decode, dim3((unsigned)blocks), dim3(64), 0u, ctx->stream, d_src, d_offsets, d_lengths, d_expected,
-               d_raw, (int)n, d_dst, d_dst_offsets, d_status, static_cast<uint8_t*>(*lit));
+    omr_launch(k_zstd_decode, dim3((unsigned)blocks), dim3(64), 0u, ctx->stream, t.src, t.offsets, t.lengths, t.expected,
+               t.raw, (int)t.n, t.dst, t.dst_offsets, t.status, static_cast<uint8_t*>(*lit));
     OMR_HIP(ctx, hipGetLastError());
     return OMR_OK;
 }
@@ -844,10 +842,7 @@ extern "C" omr_status omr_zstd_decode_batch_device(omr_ctx* ctx, const uint8_t* 
     if (!d_src || !d_offsets || !d_lengths || !d_expected || !d_dst || !d_dst_offsets || !d_status)
         return fail(ctx, OMR_INVALID_ARGUMENT, "zstd: null argument");
     OMR_HIP(ctx, hipSetDevice(ctx->device));
-    void** lit = nullptr;
-    size_t* lit_cap = nullptr;
-    const omr_status st = zarr_zstd_literals(ctx, &lit, &lit_cap);
-    if (st) return st;
-    return launch_zstd_decode(ctx, d_src, d_offsets, d_lengths, d_expected, nullptr, n, d_dst, d_dst_offsets, d_status, lit,
-                              lit_cap);
+    SegPipe* T = seg_pipe(ctx, SegKind::zarr);             // its literal buffer serves this entry too
+    return launch_zstd_decode(ctx, {d_src, d_offsets, d_lengths, d_expected, nullptr, n, d_dst, d_dst_offsets, d_status},
+                              &T->d_lit, &T->lit_cap);
 }

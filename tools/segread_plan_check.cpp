@@ -1,0 +1,174 @@
+// segread_plan_check.cpp — the planner of the readers' device route (plan_regions, group_size and
+// read_bytes_per_request in csrc/omr_segread.h) under AddressSanitizer and UBSan, as a stand-alone
+// CPU program that links nothing of the library.  For tiled and stripped levels with ragged edges
+// the segments are filled with samples that encode (plane, y, x), every planned placement is
+// applied by a plain host loop (what K13b does on the device), and every destination sample must
+// be the brute-force answer and be written exactly once; the bytes between the regions must stay
+// untouched, the unique-segment list must name every segment once, and a placement must read the
+// plane of its own request.  The segment buffers are exactly as large as the front-ends' rule makes
+// them (tiles whole, the last strip short), so a placement that reaches past one is caught.
+// Built and run by `make -C omero-ms-image-region_amd segread-plan-check`.
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <set>
+#include <tuple>
+#include <vector>
+
+#include "omr_segread.h"
+
+static int g_fail = 0;
+#define CHECK(c) do { if (!(c)) { std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #c); ++g_fail; } } while (0)
+
+using omr::SegGeom;
+using omr::SegPlan;
+typedef omr_raw_tile_request Req;   // {z, c, t, x, y}
+
+constexpr int32_t kW = 40, kH = 20, kSZ = 2, kSC = 3;
+static int64_t plane_of(const Req& r) { return ((int64_t)r.t * kSC + r.c) * kSZ + r.z; }
+
+// Byte j of the sample at (x, y) of a plane.
+static uint8_t sample_byte(int64_t plane, int32_t y, int32_t x, int j) {
+    const uint64_t v = ((uint64_t)plane * 1000003u + (uint64_t)y * 1009u + (uint64_t)x) * 0x9E3779B97F4A7C15ull + 1;
+    return (uint8_t)(v >> (8 * (j & 7)) ^ v >> 56);
+}
+
+// One level of kW x kH samples: tiles of seg_w x seg_h, or strips when seg_w == kW.
+struct Case {
+    SegGeom g;
+    bool tiled;
+    int32_t rows(int32_t sy) const { return tiled ? g.seg_h : std::min(g.seg_h, kH - sy * g.seg_h); }   // the front-ends' rule
+};
+
+static Case make_case(int32_t seg_w, int32_t seg_h, int32_t bpp, bool tiled) {
+    Case c;
+    c.g.seg_w = seg_w; c.g.seg_h = seg_h; c.g.bpp = bpp;
+    c.g.across = (kW + seg_w - 1) / seg_w;
+    c.g.down = (kH + seg_h - 1) / seg_h;
+    c.tiled = tiled;
+    return c;
+}
+
+// reqs[r0, r1) of width x height planned and applied; `missing`: a segment that reads as zeros.
+static void run(const Case& c, const std::vector<Req>& reqs, int32_t r0, int32_t r1, int32_t width, int32_t height,
+                const std::tuple<int64_t, int32_t, int32_t>* missing = nullptr) {
+    const SegGeom& g = c.g;
+    const size_t bpp = (size_t)g.bpp;
+    const int64_t stride = ((int64_t)width * height + 3) * g.bpp;          // three samples of padding behind a region
+    std::vector<uint8_t> dst((size_t)stride * reqs.size(), 0xAB);
+    std::vector<int> written((size_t)(stride / g.bpp) * reqs.size(), 0);
+    const SegPlan P = omr::plan_regions(g, reqs.data(), r0, r1, width, height, dst.data(), stride, plane_of);
+
+    // the unique segments: each once, inside the level, their buffers as the front-end sizes them
+    std::set<std::tuple<int64_t, int32_t, int32_t>> seen;
+    std::vector<std::vector<uint8_t>> bufs(P.segs.size());
+    for (size_t k = 0; k < P.segs.size(); ++k) {
+        const omr::SegKey& s = P.segs[k];
+        CHECK(s.sx >= 0 && s.sx < g.across && s.sy >= 0 && s.sy < g.down);
+        CHECK(seen.insert(std::make_tuple(s.plane, s.sx, s.sy)).second);
+        if (missing && *missing == std::make_tuple(s.plane, s.sx, s.sy)) continue;
+        const int32_t rows = c.rows(s.sy);
+        bufs[k].assign((size_t)rows * g.seg_w * bpp, 0xEE);                  // 0xEE: behind the level's edge
+        for (int32_t y = 0; y < rows; ++y)
+            for (int32_t x = 0; x < g.seg_w; ++x) {
+                const int32_t gx = s.sx * g.seg_w + x, gy = s.sy * g.seg_h + y;
+                if (gx >= kW || gy >= kH) continue;
+                for (size_t j = 0; j < bpp; ++j) bufs[k][((size_t)y * g.seg_w + x) * bpp + j] = sample_byte(s.plane, gy, gx, (int)j);
+            }
+    }
+
+    // the placements, as K13b applies them
+    CHECK(P.places.size() == P.place_seg.size());
+    int32_t tallest = 0;
+    for (size_t k = 0; k < P.places.size(); ++k) {
+        const omr::TiffPlace& p = P.places[k];
+        CHECK(p.src == nullptr);
+        CHECK(P.place_seg[k] >= 0 && (size_t)P.place_seg[k] < P.segs.size());
+        CHECK(p.seg_w == g.seg_w && p.dst_pitch == width);
+        CHECK(0 <= p.x0 && p.x0 < p.x1 && p.x1 <= g.seg_w && 0 <= p.y0 && p.y0 < p.y1 && p.y1 <= g.seg_h);
+        tallest = std::max(tallest, p.y1 - p.y0);
+        const size_t at = (size_t)(p.dst - dst.data());
+        CHECK(p.dst >= dst.data() && at < dst.size() && at % bpp == 0);
+        const size_t region = at / (size_t)stride;
+        CHECK(region >= (size_t)r0 && region < (size_t)r1);
+        const omr::SegKey& s = P.segs[(size_t)P.place_seg[k]];
+        CHECK(s.plane == plane_of(reqs[region]));                           // no two planes share an entry
+        const std::vector<uint8_t>& src = bufs[(size_t)P.place_seg[k]];
+        for (int32_t y = p.y0; y < p.y1; ++y)
+            for (int32_t x = p.x0; x < p.x1; ++x) {
+                const size_t d = at + ((size_t)(y - p.y0) * p.dst_pitch + (x - p.x0)) * bpp;
+                if (d + bpp > dst.size()) { CHECK(!"placement past the destination"); continue; }
+                if (src.empty()) std::memset(&dst[d], 0, bpp);
+                else std::memcpy(&dst[d], &src[((size_t)y * p.seg_w + x) * bpp], bpp);
+                ++written[d / bpp];
+            }
+    }
+    CHECK(tallest == P.max_rows);
+
+    // every destination sample: the brute-force answer, written exactly once; nothing else touched
+    for (size_t i = 0; i < reqs.size(); ++i) {
+        const bool planned = (int32_t)i >= r0 && (int32_t)i < r1;
+        const Req& r = reqs[i];
+        for (int64_t e = 0; e < stride / g.bpp; ++e) {
+            const size_t d = (size_t)i * (size_t)stride + (size_t)e * bpp;
+            const bool inside = planned && e < (int64_t)width * height;
+            CHECK(written[d / bpp] == (inside ? 1 : 0));
+            for (size_t j = 0; j < bpp; ++j) {
+                uint8_t want = 0xAB;
+                if (inside) {
+                    const int32_t gx = r.x + (int32_t)(e % width), gy = r.y + (int32_t)(e / width);
+                    const auto seg = std::make_tuple(plane_of(r), gx / g.seg_w, gy / g.seg_h);
+                    want = missing && *missing == seg ? 0 : sample_byte(plane_of(r), gy, gx, (int)j);
+                }
+                CHECK(dst[d + j] == want);
+            }
+        }
+    }
+}
+
+static void geometry(const Case& c) {
+    const Req a{0, 0, 0, 0, 0};
+    run(c, {a}, 0, 1, 1, 1);                                            // 1 x 1 at (0, 0)
+    run(c, {{0, 0, 0, 39, 19}}, 0, 1, 1, 1);                            // and at (39, 19)
+    run(c, {a}, 0, 1, kW, kH);                                          // the full level
+    run(c, {{1, 2, 1, 15, 7}}, 0, 1, 17, 9);                            // unaligned, 3 x 3 tiles
+    run(c, {{0, 1, 0, 2, 1}, {0, 1, 0, 5, 3}}, 0, 2, 9, 4);             // two requests overlapping in one segment
+    run(c, {{0, 0, 0, 15, 7}, {1, 2, 1, 15, 7}}, 0, 2, 17, 9);          // the same region on two (z, c, t)
+    run(c, {a, {0, 1, 0, 3, 2}, {1, 1, 1, 20, 11}, a}, 1, 3, 12, 9);    // a group in the middle of the requests
+    const auto gone = std::make_tuple(plane_of({1, 2, 1, 0, 0}), c.g.across > 1 ? 1 : 0, 1);
+    run(c, {{1, 2, 1, 15, 7}}, 0, 1, 17, 9, &gone);                     // a segment that reads as zeros
+    run(c, {a}, 0, 1, 0, 5);                                            // empty regions plan nothing
+    CHECK(omr::plan_regions(c.g, &a, 0, 1, 0, 5, nullptr, 0, plane_of).places.empty());
+    CHECK(omr::plan_regions(c.g, &a, 0, 0, 4, 4, nullptr, 0, plane_of).places.empty());
+}
+
+int main() {
+    for (int32_t bpp : {1, 2, 8}) {
+        geometry(make_case(16, 8, bpp, true));                            // tiles: both edges ragged
+        geometry(make_case(kW, 8, bpp, false));                           // strips: the last one has 4 rows
+    }
+    // the unique list is in first-touch order and shared between the requests of a group
+    {
+        const Case c = make_case(16, 8, 2, true);
+        const std::vector<Req> reqs = {{0, 1, 0, 2, 1}, {0, 1, 0, 5, 3}, {0, 2, 0, 5, 3}};
+        std::vector<uint8_t> dst(3 * 80);
+        const SegPlan P = omr::plan_regions(c.g, reqs.data(), 0, 3, 9, 4, dst.data(), 80, plane_of);
+        CHECK(P.segs.size() == 2 && P.places.size() == 3);
+        CHECK(P.place_seg == (std::vector<int32_t>{0, 0, 1}));
+        CHECK(P.segs[0].plane == plane_of(reqs[0]) && P.segs[1].plane == plane_of(reqs[2]));
+    }
+    // group sizes at their boundaries
+    const size_t budget = std::min(omr::kGroupInBytes, omr::kGroupScratchBytes);
+    CHECK(omr::group_size(0, budget, 4096) == 1);
+    CHECK(omr::group_size(1, budget, 4096) == 1);
+    CHECK(omr::group_size(1000, budget, budget + 1) == 1);                // a request larger than the budget
+    CHECK(omr::group_size(1000, budget, budget) == 1);
+    CHECK(omr::group_size(1000, budget, budget / 128) == 128);            // divides the budget exactly
+    CHECK(omr::group_size(1000, budget, budget / 128 + 1) == 127);
+    CHECK(omr::group_size(100, budget, budget / 128) == 100);             // never more than the requests
+    CHECK(omr::group_size(7, omr::kRenderGroupBytes, omr::kRenderGroupBytes / 4) == 4);
+    CHECK(omr::read_bytes_per_request(make_case(16, 8, 2, true).g, 17, 9) == 3u * 3u * 256u);
+    CHECK(omr::read_bytes_per_request(make_case(kW, 8, 1, false).g, 1, 1) == 2u * 2u * 320u);
+    std::printf(g_fail ? "segread_plan_check: %d check(s) failed\n" : "segread_plan_check: ok\n", g_fail);
+    return g_fail ? 1 : 0;
+}

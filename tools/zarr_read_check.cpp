@@ -17,31 +17,7 @@
 #include <string>
 #include <vector>
 
-#include "omr_internal.h"
-
-// what omr_zarr.cpp takes from the rest of the library (the device route is not run here)
-namespace omr {
-int bytes_per_pixel(int32_t t) {
-    switch (t) {
-    case OMR_PIXELS_INT8: case OMR_PIXELS_UINT8: return 1;
-    case OMR_PIXELS_INT16: case OMR_PIXELS_UINT16: return 2;
-    case OMR_PIXELS_INT32: case OMR_PIXELS_UINT32: case OMR_PIXELS_FLOAT: return 4;
-    case OMR_PIXELS_DOUBLE: return 8;
-    default: return 0;
-    }
-}
-omr_status fail(Ctx*, omr_status s, const std::string&) { return s; }
-omr_status hip_fail(Ctx*, hipError_t, const char*) { return OMR_DEVICE; }
-omr_status launch_inflate(Ctx*, const uint8_t*, const uint64_t*, const uint32_t*, const uint32_t*, int32_t, uint8_t*,
-                          const uint64_t*, int32_t*) { return OMR_DEVICE; }
-omr_status launch_tiff_place(Ctx*, const TiffPlace*, int32_t, int32_t, int32_t, int32_t, bool) { return OMR_DEVICE; }
-}  // namespace omr
-extern "C" omr_status omr_ctx_synchronize(omr_ctx*) { return OMR_DEVICE; }
-extern "C" omr_status omr_render_batch_strided_device(omr_ctx*, const omr_quantum_def*, const omr_channel_binding*, int32_t,
-                                                      const void*, int64_t, int64_t, int32_t, int64_t, int32_t, int32_t,
-                                                      int32_t, int32_t, int32_t, int32_t, uint32_t*, int32_t*) {
-    return OMR_DEVICE;
-}
+#include "read_check_stubs.h"
 
 static int g_fail = 0;
 #define CHECK(c) do { if (!(c)) { std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #c); ++g_fail; } } while (0)
