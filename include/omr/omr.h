@@ -1024,7 +1024,8 @@ omr_status omr_update_settings(const omr_image_region_ctx* ctx, int32_t size_c, 
  * 2, fewer IFDs than Z*C*T, planes that disagree, a segment above 256 MiB decoded); OMR_INTERNAL
  * for a corrupt file (an offset or count past the end of the file, an IFD chain that loops, a
  * count whose product overflows).  The file is read with pread, every offset bounds-checked.
- * Read-only; safe to share between contexts and threads.
+ * Read-only; safe to share between contexts and threads.  Deflate, zstd, Predictor 3 and chunky
+ * multi-sample files open through omr_tiff_image_open_ex below.
  */
 typedef struct omr_tiff_image omr_tiff_image;
 typedef struct omr_tiff_info {
@@ -1032,13 +1033,57 @@ typedef struct omr_tiff_info {
     int32_t pixel_type;                                /* OMR_PIXELS_* */
     int32_t big_endian;                                /* the file's byte order ("MM": 1) */
     int32_t n_levels;                                  /* 1 + SubIFDs per plane */
-    int32_t compression, predictor;                    /* TIFF tag values: 1 / 5, 1 / 2 */
+    int32_t compression, predictor;                    /* TIFF tag values: 1 / 5, 1 / 2; open_ex: also 8 / 50000 (32946 reads 8), 3 */
     int32_t tiled;                                     /* level 0: 1 tiles, 0 strips */
     int32_t segment_width, segment_height;             /* level 0: tile size, or size_x and RowsPerStrip */
     int32_t big_tiff;
 } omr_tiff_info;
 omr_status omr_tiff_image_open(const char* path, int32_t size_z, int32_t size_c, int32_t size_t_,
                                const char* dimension_order, omr_tiff_image** out);
+/*
+ * omr_tiff_image_open with the set of further forms the caller accepts; omr_tiff_image_open(...) is
+ * open_ex with opt == NULL, which means accept = 0 and refuses them all as before.
+ * OMR_INVALID_ARGUMENT: unknown bits in accept, a struct_size smaller than the struct, a form the
+ * file uses whose bit is not set.
+ *
+ * DEFLATE and ZSTD: every segment is one zlib stream (Compression 8, or 32946, reported as 8) or one
+ * Zstandard frame (50000), decoded on the host by omr_inflate_host / omr_zstd_decode_host and on the
+ * device by K14a / K16a (kernel timing kinds 32 / 35 in place of 30).  Their rule is the strict one of the Zarr
+ * reader, not LZW's rule of cutting an overrunning string: a segment must decode to exactly its
+ * size, through the Adler-32 or the frame's end, and anything else is OMR_INTERNAL on that segment.
+ * A compressed segment stays below 512 MiB.  Pinned against libtiff's own Deflate and zstd strips
+ * (tests/golden/tiff_codecs.npz: 8- and 16-bit, Predictor 1 and 2, a short last strip).
+ *
+ * PREDICTOR3: the floating-point predictor, float and double samples, one sample per pixel
+ * (libtiff's fpAcc): the running byte sum (mod 256) over a segment row's n * B bytes gives B planes
+ * of n bytes, the most significant byte of every sample first in either file byte order; sample x
+ * is the planes' bytes at x.  float32 little-endian is pinned against libtiff; double and the
+ * big-endian forms rest on the project's own writer.
+ *
+ * SAMPLES: SamplesPerPixel 2..4 with PlanarConfiguration 1 (chunky, as brightfield RGB slides are
+ * written).  size_c stays the channel count as OMERO sees it (3 for an RGB image) and must be a
+ * multiple of SamplesPerPixel; the file holds Z * (C / spp) * T IFDs and channel c is sample c % spp
+ * of the IFD of channel c / spp, in the caller's dimension order; info.size_c is the caller's.
+ * ExtraSamples are ordinary channels.  All samples of a pixel have the same BitsPerSample and
+ * SampleFormat; Predictor 2 runs per component, spp samples apart.  A read returns the one
+ * requested sample; on the device two channels of one pixel share the segment, which is read and
+ * decoded once per group.  Refused: Photometric 6 (YCbCr), PlanarConfiguration 2, more than 4
+ * samples, Predictor 3.  The segment limit of 256 MiB decoded counts all samples.  8-bit RGB is
+ * pinned against libtiff; 16-bit, 4 samples and big-endian rest on the project's own writer.
+ */
+#define OMR_TIFF_ACCEPT_DEFLATE    1u   /* Compression 8 and 32946: one zlib stream per segment   */
+#define OMR_TIFF_ACCEPT_ZSTD       2u   /* Compression 50000: one Zstandard frame per segment     */
+#define OMR_TIFF_ACCEPT_PREDICTOR3 4u   /* floating-point predictor, float and double samples     */
+#define OMR_TIFF_ACCEPT_SAMPLES    8u   /* SamplesPerPixel 2..4, PlanarConfiguration 1 (chunky)   */
+typedef struct omr_tiff_open_options {
+    uint32_t struct_size;                              /* sizeof(omr_tiff_open_options) */
+    uint32_t accept;                                   /* OMR_TIFF_ACCEPT_* bits */
+} omr_tiff_open_options;
+omr_status omr_tiff_image_open_ex(const char* path, int32_t size_z, int32_t size_c, int32_t size_t_,
+                                  const char* dimension_order, const omr_tiff_open_options* opt,
+                                  omr_tiff_image** out);
+/* SamplesPerPixel of the open image (1 unless opened with OMR_TIFF_ACCEPT_SAMPLES); negative status for NULL. */
+int32_t    omr_tiff_image_samples_per_pixel(const omr_tiff_image* img);
 void       omr_tiff_image_close(omr_tiff_image* img);
 omr_status omr_tiff_image_info(const omr_tiff_image* img, omr_tiff_info* info);
 /* (width, height) per level as stored in the file (not size >> k): up to cap_pairs pairs into
@@ -1052,7 +1097,10 @@ int32_t    omr_tiff_image_level_sizes(const omr_tiff_image* img, int32_t* sizes_
  * (10 bits once the next free entry is 511, 11 at 1023, 12 at 2047).  Decoding ends at EOI or once
  * the segment's size (tile_w * tile_h * bpp, or rows_in_strip * W * bpp) is produced; a string
  * that overruns it is cut.  OMR_INTERNAL: fewer bytes than that, a code above the next free entry,
- * an old-style LSB-first stream, an I/O error.
+ * an old-style LSB-first stream, an I/O error.  Deflate and zstd segments (open_ex) go through
+ * omr_inflate_host / omr_zstd_decode_host by the strict rule stated there: exactly the segment's
+ * size, nothing cut.  Predictor 3 and the per-component Predictor 2 are undone here, and for a
+ * chunky image the rows hold the one sample of channel c.
  */
 omr_status omr_tiff_image_get_tile(const omr_tiff_image* img, int32_t level, int32_t z, int32_t c, int32_t t,
                                    int32_t x, int32_t y, int32_t w, int32_t h, void* dst, size_t cap);

@@ -296,12 +296,15 @@ bool pyramid_levels_valid(int64_t w, int64_t h, int64_t n_levels);
 
 // K13 (omr_tiffread.hip).  One placement: the rectangle [x0, x1) x [y0, y1) of a decoded (or stored)
 // segment whose rows are seg_w samples apart, into dst (the address of sample (x0, y0)) with rows
-// dst_pitch samples apart; src == nullptr reads as zeros (a segment with byte count 0).
+// dst_pitch samples apart; src == nullptr reads as zeros (a segment with byte count 0).  A segment
+// of chunky pixels holds spp samples per pixel (seg_w, x0 and x1 count pixels): the placement takes
+// sample `sample` of each, and the destination holds that one sample per pixel.
 struct TiffPlace {
     const uint8_t* src;
     uint8_t* dst;
     int32_t seg_w, dst_pitch;
     int32_t x0, x1, y0, y1;
+    int32_t spp, sample;
 };
 // The argument of the stream decoders (K13a, K14a, K15a, K16a), all device memory: stream i is
 // lengths[i] bytes at src + offsets[i] and decodes to exactly expected[i] bytes at dst +
@@ -321,9 +324,11 @@ struct StreamTable {
 // K13a: LZW streams (omr_lzw_decode_batch_device after its argument check).
 omr_status launch_lzw_decode(Ctx* ctx, const StreamTable& t);
 // K13b: n placements (a device table) of samples bps bytes wide, none taller than max_rows; swap:
-// the file's byte order is not the host's (it matters to predictor 2 only).
+// the file's byte order is not the host's (it matters to predictors 2 and 3 only); spp: the samples
+// per pixel of every placement's segment (1: the placements' own spp and sample are not read).
+// Predictor 3 (float and double samples, spp 1) goes to k_tiff_place_fp.
 omr_status launch_tiff_place(Ctx* ctx, const TiffPlace* d_places, int32_t n, int32_t max_rows, int32_t bps,
-                             int32_t predictor, bool swap);
+                             int32_t predictor, bool swap, int32_t spp);
 // K14a (omr_inflate.hip): zlib streams (omr_inflate_batch_device after its argument check).
 omr_status launch_inflate(Ctx* ctx, const StreamTable& t);
 

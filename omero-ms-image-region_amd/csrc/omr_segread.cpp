@@ -123,7 +123,8 @@ omr_status finish_blosc(Ctx* ctx, SegPipe* T, const SegSource& S, const SegPlan&
 omr_status read_group(Ctx* ctx, SegSource& S, const omr_raw_tile_request* reqs, int32_t r0, int32_t r1, int32_t width,
                       int32_t height, uint8_t* d_dst, int64_t stride) {
     SegPlan plan = plan_regions(S.geom, reqs, r0, r1, width, height, d_dst, stride,
-                                [&](const omr_raw_tile_request& r) { return S.plane_of(r); });
+                                [&](const omr_raw_tile_request& r) { return S.plane_of(r); },
+                                [&](const omr_raw_tile_request& r) { return S.sample_of(r); });
     if (plan.places.empty()) return OMR_OK;
     std::vector<SegBytes> segs(plan.segs.size());
     omr_status st = S.sizes(ctx, plan.segs, segs);
@@ -179,7 +180,7 @@ omr_status read_group(Ctx* ctx, SegSource& S, const omr_raw_tile_request* reqs, 
     }
     if (st) return st;
     st = launch_tiff_place(ctx, reinterpret_cast<const TiffPlace*>(din + t.o_place), (int32_t)plan.places.size(),
-                           plan.max_rows, S.geom.bpp, S.predictor, S.swap);
+                           plan.max_rows, S.geom.bpp, S.predictor, S.swap, S.geom.spp);
     if (st) return st;
     return scan_statuses(ctx, S, t, pin, din, codec);
 }

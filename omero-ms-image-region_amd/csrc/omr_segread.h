@@ -67,9 +67,10 @@ void parallel_for(int n, bool threaded, const F& job) {
 
 // One level: segments of seg_w x seg_h samples (a strip: seg_w = the level's width), `across` per
 // segment row, samples of bpp bytes.  Segments are stored whole but for the rows of a last strip,
-// which no region inside the level reaches.
+// which no region inside the level reaches.  spp: samples per pixel of a chunky TIFF segment
+// (seg_w counts pixels; a segment row is seg_w * spp samples); a region takes one of them.
 struct SegGeom {
-    int32_t seg_w = 0, seg_h = 0, across = 0, down = 0, bpp = 0;
+    int32_t seg_w = 0, seg_h = 0, across = 0, down = 0, bpp = 0, spp = 1;
 };
 struct SegKey {
     int64_t plane;
@@ -83,10 +84,12 @@ struct SegPlan {
 };
 
 // The regions reqs[r0, r1) of width x height samples (inside the level), region i to
-// dst + i * stride bytes with rows `width` samples apart; plane_of(request) numbers the planes.
-template <typename PlaneOf>
+// dst + i * stride bytes with rows `width` samples apart; plane_of(request) numbers the planes (the
+// IFDs of a TIFF: the channels of one chunky pixel share a plane, and so its segments) and
+// sample_of(request) in [0, g.spp) picks the request's sample out of each pixel.
+template <typename PlaneOf, typename SampleOf>
 SegPlan plan_regions(const SegGeom& g, const omr_raw_tile_request* reqs, int32_t r0, int32_t r1, int32_t width,
-                     int32_t height, uint8_t* dst, int64_t stride, const PlaneOf& plane_of) {
+                     int32_t height, uint8_t* dst, int64_t stride, const PlaneOf& plane_of, const SampleOf& sample_of) {
     SegPlan P;
     if (width <= 0 || height <= 0) return P;
     std::unordered_map<uint64_t, int32_t> index;      // plane * segments + k -> unique segment
@@ -94,6 +97,7 @@ SegPlan plan_regions(const SegGeom& g, const omr_raw_tile_request* reqs, int32_t
     for (int32_t i = r0; i < r1; ++i) {
         const omr_raw_tile_request& r = reqs[i];
         const int64_t plane = plane_of(r);
+        const int32_t sample = (int32_t)sample_of(r);
         for (int32_t sy = r.y / g.seg_h; sy <= (r.y + height - 1) / g.seg_h; ++sy)
             for (int32_t sx = r.x / g.seg_w; sx <= (r.x + width - 1) / g.seg_w; ++sx) {
                 const uint64_t key = (uint64_t)plane * per_plane + (uint64_t)sy * g.across + sx;
@@ -111,12 +115,20 @@ SegPlan plan_regions(const SegGeom& g, const omr_raw_tile_request* reqs, int32_t
                 p.seg_w = g.seg_w;
                 p.dst_pitch = width;
                 p.x0 = X0 - ox; p.x1 = X1 - ox; p.y0 = Y0 - oy; p.y1 = Y1 - oy;
+                p.spp = g.spp;
+                p.sample = sample;
                 P.max_rows = std::max(P.max_rows, Y1 - Y0);
                 P.places.push_back(p);
                 P.place_seg.push_back(it->second);
             }
     }
     return P;
+}
+// One sample per pixel.
+template <typename PlaneOf>
+SegPlan plan_regions(const SegGeom& g, const omr_raw_tile_request* reqs, int32_t r0, int32_t r1, int32_t width,
+                     int32_t height, uint8_t* dst, int64_t stride, const PlaneOf& plane_of) {
+    return plan_regions(g, reqs, r0, r1, width, height, dst, stride, plane_of, [](const omr_raw_tile_request&) { return 0; });
 }
 
 // Requests per group: as many of the n as fit the budget at per_req bytes each, and at least one.
@@ -125,7 +137,7 @@ inline int32_t group_size(int32_t n, size_t budget, size_t per_req) {
 }
 // The staging a read request can need: its segments counted whole and without sharing.
 inline size_t read_bytes_per_request(const SegGeom& g, int32_t width, int32_t height) {
-    const size_t seg_dec = (((size_t)g.seg_w * g.seg_h * g.bpp) + 15) / 16 * 16;
+    const size_t seg_dec = (((size_t)g.seg_w * g.seg_h * g.bpp * g.spp) + 15) / 16 * 16;
     return (size_t)((width - 1) / g.seg_w + 2) * (size_t)((height - 1) / g.seg_h + 2) * seg_dec;
 }
 
@@ -186,6 +198,7 @@ struct SegSource {
     bool big = false;
     virtual ~SegSource() = default;
     virtual int64_t plane_of(const omr_raw_tile_request& r) const = 0;
+    virtual int32_t sample_of(const omr_raw_tile_request&) const { return 0; }   // in [0, geom.spp)
     // cnt and expected of every segment of the group (a failure sets the context's message itself).
     virtual omr_status sizes(Ctx* ctx, const std::vector<SegKey>& keys, std::vector<SegBytes>& out) = 0;
     // cnt bytes of every segment to pin + in_off; in_bytes: their sum.  false: an I/O error.

@@ -6,7 +6,10 @@
 // serial LZW decoder of the host route (omr_tiff_image_get_tile: the reference of the tests and
 // the route of single reads) and what the device route needs to know of a TIFF (TiffSource): a
 // segment's offset and byte count from the IFD tables, the rows of a short last strip, and the
-// pread of the segments' bytes from the one file.  The device route itself -- staging, planning,
+// pread of the segments' bytes from the one file.  omr_tiff_image_open_ex widens what a file may
+// use: Deflate and Zstandard segments (decoded on the host by omr_inflate_host and
+// omr_zstd_decode_host, on the device by K14a and K16a), the floating-point predictor and chunky
+// pixels of 2..4 samples, of which a read takes one.  The device route itself -- staging, planning,
 // K13a's and K13b's launches (omr_tiffread.hip), the tile renderer -- is omr_segread.cpp, shared
 // with the Zarr reader; this file calls no HIP function.
 #include "omr_segread.h"
@@ -48,6 +51,7 @@ struct omr_tiff_image {
     int32_t sz = 0, sc = 0, st = 0;
     int64_t stride_z = 0, stride_c = 0, stride_t = 0;   // plane index = z*stride_z + c*stride_c + t*stride_t
     int32_t pt = 0, bpp = 0, compression = 1, predictor = 1;
+    int32_t spp = 1;                                    // samples per pixel (chunky): channel c is sample c % spp
     std::vector<Level> levels;
     std::vector<std::vector<Segments>> segs;   // [plane][level]
     ~omr_tiff_image() {
@@ -76,7 +80,9 @@ bool read_full(int fd, void* dst, size_t n, uint64_t off) {
 
 struct Ifd {
     uint64_t w = 0, h = 0, bps = 1, comp = 1, fill = 1, spp = 1, rps = 0xFFFFFFFFull, pred = 1, tw = 0, th = 0, fmt = 1;
+    uint64_t photometric = 1, planar = 1;
     bool has_tw = false, has_th = false;
+    bool mixed = false;            // BitsPerSample or SampleFormat differ between the samples of a pixel
     std::vector<uint64_t> strip_off, strip_cnt, tile_off, tile_cnt, sub;
 };
 
@@ -121,12 +127,14 @@ struct Parser {
         for (uint64_t k = 0; k < count; ++k) out[(size_t)k] = u(src + k * ts, ts);
         return OMR_OK;
     }
-    omr_status scalar(const uint8_t* e, uint64_t& v) const {
+    omr_status scalar(const uint8_t* e, uint64_t& v, bool* mixed = nullptr) const {
         std::vector<uint64_t> vals;
         const omr_status st = values(e, vals);
         if (st) return st;
         if (vals.empty()) return OMR_INTERNAL;
         v = vals[0];
+        if (mixed)
+            for (uint64_t o : vals) *mixed = *mixed || o != v;
         return OMR_OK;
     }
     // Entry count and the offset of the next IFD; with `ifd`, the tags too.
@@ -149,20 +157,22 @@ struct Parser {
             switch ((uint32_t)u(e, 2)) {
             case 256: st = scalar(e, ifd->w); break;
             case 257: st = scalar(e, ifd->h); break;
-            case 258: st = scalar(e, ifd->bps); break;
+            case 258: st = scalar(e, ifd->bps, &ifd->mixed); break;
             case 259: st = scalar(e, ifd->comp); break;
+            case 262: st = scalar(e, ifd->photometric); break;
             case 266: st = scalar(e, ifd->fill); break;
             case 273: st = values(e, ifd->strip_off); break;
             case 277: st = scalar(e, ifd->spp); break;
             case 278: st = scalar(e, ifd->rps); break;
             case 279: st = values(e, ifd->strip_cnt); break;
+            case 284: st = scalar(e, ifd->planar); break;
             case 317: st = scalar(e, ifd->pred); break;
             case 322: st = scalar(e, ifd->tw); ifd->has_tw = true; break;
             case 323: st = scalar(e, ifd->th); ifd->has_th = true; break;
             case 324: st = values(e, ifd->tile_off); break;
             case 325: st = values(e, ifd->tile_cnt); break;
             case 330: st = values(e, ifd->sub); break;
-            case 339: st = scalar(e, ifd->fmt); break;
+            case 339: st = scalar(e, ifd->fmt, &ifd->mixed); break;
             default: break;
             }
             if (st) return st;
@@ -184,17 +194,38 @@ inline int32_t rows_in_segment(const Level& L, int32_t sy) {
 }
 
 // One IFD into the image: geometry, format and the segment table, all checked.
-omr_status take_ifd(const Parser& P, const Ifd& f, Level& L, Segments& S, int32_t& pt, int32_t& comp, int32_t& pred) {
-    if (f.spp != 1 || f.fill != 1) return OMR_INVALID_ARGUMENT;
-    if (f.comp != 1 && f.comp != 5) return OMR_INVALID_ARGUMENT;
-    if (f.pred != 1 && f.pred != 2) return OMR_INVALID_ARGUMENT;
+// accept: the OMR_TIFF_ACCEPT_* bits of the open; a feature the file uses without its bit is refused.
+omr_status take_ifd(const Parser& P, const Ifd& f, uint32_t accept, Level& L, Segments& S, int32_t& pt, int32_t& comp,
+                    int32_t& pred, int32_t& spp) {
+    if (f.fill != 1) return OMR_INVALID_ARGUMENT;
+    if (f.spp != 1) {
+        if (!(accept & OMR_TIFF_ACCEPT_SAMPLES) || f.spp < 1 || f.spp > 4) return OMR_INVALID_ARGUMENT;
+        if (f.planar != 1 || f.photometric == 6 || f.mixed) return OMR_INVALID_ARGUMENT;
+    }
+    switch (f.comp) {
+    case 1: case 5: comp = (int32_t)f.comp; break;
+    case 8: case 32946:
+        if (!(accept & OMR_TIFF_ACCEPT_DEFLATE)) return OMR_INVALID_ARGUMENT;
+        comp = 8;
+        break;
+    case 50000:
+        if (!(accept & OMR_TIFF_ACCEPT_ZSTD)) return OMR_INVALID_ARGUMENT;
+        comp = 50000;
+        break;
+    default: return OMR_INVALID_ARGUMENT;
+    }
+    if (f.pred == 3) {                                   // float and double, one sample per pixel
+        if (!(accept & OMR_TIFF_ACCEPT_PREDICTOR3) || f.fmt != 3 || f.spp != 1) return OMR_INVALID_ARGUMENT;
+    } else if (f.pred != 1 && f.pred != 2) {
+        return OMR_INVALID_ARGUMENT;
+    }
     pt = pixel_type_of(f.bps, f.fmt);
     if (pt < 0) return OMR_INVALID_ARGUMENT;
     if (f.pred == 2 && f.bps == 64) return OMR_INVALID_ARGUMENT;
     if (f.w < 1 || f.h < 1 || f.w > 0x7FFFFFFFull || f.h > 0x7FFFFFFFull) return OMR_INVALID_ARGUMENT;
-    comp = (int32_t)f.comp;
     pred = (int32_t)f.pred;
-    const uint64_t bpp = f.bps / 8;
+    spp = (int32_t)f.spp;
+    const uint64_t bpp = f.bps / 8 * f.spp;              // bytes per pixel, all samples
     L.w = (int32_t)f.w;
     L.h = (int32_t)f.h;
     const std::vector<uint64_t>*off, *cnt;
@@ -310,20 +341,36 @@ T swap_bytes(T v) {
     return v;
 }
 
-// Undo predictor 2 on `rows` rows of `w` samples: running sums in the sample's own width.
+// Undo predictor 2 on `rows` rows of `w` pixels of spp samples: running sums per component (spp
+// samples apart) in the sample's own width.
 template <typename T>
-void unpredict(uint8_t* buf, int64_t rows, int64_t w, bool swap) {
+void unpredict(uint8_t* buf, int64_t rows, int64_t w, int64_t spp, bool swap) {
     for (int64_t r = 0; r < rows; ++r) {
-        uint8_t* row = buf + (size_t)(r * w) * sizeof(T);
-        T acc = 0;
-        for (int64_t x = 0; x < w; ++x) {
+        uint8_t* row = buf + (size_t)(r * w * spp) * sizeof(T);
+        T acc[4] = {0, 0, 0, 0};
+        for (int64_t x = 0; x < w * spp; ++x) {
             T v;
             std::memcpy(&v, row + x * sizeof(T), sizeof(T));
             if (swap) v = swap_bytes(v);
-            acc = (T)(acc + v);
-            v = swap ? swap_bytes(acc) : acc;
+            T& a = acc[x % spp];
+            a = (T)(a + v);
+            v = swap ? swap_bytes(a) : a;
             std::memcpy(row + x * sizeof(T), &v, sizeof(T));
         }
+    }
+}
+
+// Undo predictor 3 (libtiff's fpAcc) on `rows` rows of `w` samples of B bytes: the running byte sum
+// over the row's w * B bytes gives B planes of w bytes, the most significant first; sample x is
+// their bytes at x, put back in the file's byte order.
+void unpredict_fp(uint8_t* buf, int64_t rows, int64_t w, int64_t B, bool big, std::vector<uint8_t>& tmp) {
+    tmp.resize((size_t)(w * B));
+    for (int64_t r = 0; r < rows; ++r) {
+        uint8_t* row = buf + (size_t)(r * w * B);
+        uint8_t acc = 0;
+        for (int64_t k = 0; k < w * B; ++k) tmp[(size_t)k] = acc = (uint8_t)(acc + row[k]);
+        for (int64_t x = 0; x < w; ++x)
+            for (int64_t b = 0; b < B; ++b) row[x * B + (big ? b : B - 1 - b)] = tmp[(size_t)(b * w + x)];
     }
 }
 
@@ -334,8 +381,26 @@ bool host_little_endian() {
     return b == 1;
 }
 
+// The IFD of channel c: the spp channels of one chunky pixel share it.
 int64_t plane_index(const omr_tiff_image* im, int32_t z, int32_t c, int32_t t) {
-    return z * im->stride_z + c * im->stride_c + t * im->stride_t;
+    return z * im->stride_z + (c / im->spp) * im->stride_c + t * im->stride_t;
+}
+
+// "XY" and a permutation of Z, C, T: the first of the three varies fastest along the IFD chain,
+// which holds c_planes = size_c / spp IFDs per (z, t).
+bool set_strides(omr_tiff_image* im, const char* order, int32_t c_planes) {
+    if (std::strlen(order) != 5 || order[0] != 'X' || order[1] != 'Y') return false;
+    im->stride_z = im->stride_c = im->stride_t = 0;
+    int64_t stride = 1;
+    for (int k = 2; k < 5; ++k) {
+        switch (order[k]) {
+        case 'Z': if (im->stride_z) return false; im->stride_z = stride; stride *= im->sz; break;
+        case 'C': if (im->stride_c) return false; im->stride_c = stride; stride *= c_planes; break;
+        case 'T': if (im->stride_t) return false; im->stride_t = stride; stride *= im->st; break;
+        default: return false;
+        }
+    }
+    return true;
 }
 
 bool region_in_bounds(const omr_tiff_image* im, const Level& L, int32_t z, int32_t c, int32_t t, int32_t x, int32_t y,
@@ -344,12 +409,14 @@ bool region_in_bounds(const omr_tiff_image* im, const Level& L, int32_t z, int32
            h >= 0 && (int64_t)x + w <= L.w && (int64_t)y + h <= L.h;
 }
 
-// Segment (sx, sy) of a plane, decoded and with the predictor undone: rows * seg_w samples.
+// Segment (sx, sy) of a plane, decoded and with the predictor undone: rows * seg_w pixels of spp
+// samples.  A Deflate or zstd segment must decode to exactly that (omr_inflate_host,
+// omr_zstd_decode_host); an LZW string that overruns it is cut.
 omr_status load_segment(const omr_tiff_image* im, const Level& L, const Segments& S, int32_t sx, int32_t sy,
                         std::vector<uint8_t>& comp, std::vector<uint8_t>& out) {
     const size_t k = (size_t)sy * L.across + sx;
     const int32_t rows = rows_in_segment(L, sy);
-    const size_t expected = (size_t)rows * L.seg_w * im->bpp;
+    const size_t expected = (size_t)rows * L.seg_w * im->bpp * im->spp;
     out.assign(expected, 0);
     const uint64_t cnt = S.cnt[k];
     if (cnt == 0) return OMR_OK;
@@ -358,13 +425,22 @@ omr_status load_segment(const omr_tiff_image* im, const Level& L, const Segments
     } else {
         comp.resize((size_t)cnt);
         if (!read_full(im->fd, comp.data(), (size_t)cnt, S.off[k])) return OMR_INTERNAL;
-        if (!lzw_decode(comp.data(), (size_t)cnt, out.data(), expected)) return OMR_INTERNAL;
+        bool ok;
+        switch (im->compression) {
+        case 5: ok = lzw_decode(comp.data(), (size_t)cnt, out.data(), expected); break;
+        case 8: ok = omr_inflate_host(comp.data(), (size_t)cnt, out.data(), expected) == OMR_OK; break;
+        case 50000: ok = omr_zstd_decode_host(comp.data(), (size_t)cnt, out.data(), expected) == OMR_OK; break;
+        default: ok = false; break;
+        }
+        if (!ok) return OMR_INTERNAL;
     }
     if (im->predictor == 2) {
         const bool swap = im->big == host_little_endian();
-        if (im->bpp == 1) unpredict<uint8_t>(out.data(), rows, L.seg_w, false);
-        else if (im->bpp == 2) unpredict<uint16_t>(out.data(), rows, L.seg_w, swap);
-        else if (im->bpp == 4) unpredict<uint32_t>(out.data(), rows, L.seg_w, swap);
+        if (im->bpp == 1) unpredict<uint8_t>(out.data(), rows, L.seg_w, im->spp, false);
+        else if (im->bpp == 2) unpredict<uint16_t>(out.data(), rows, L.seg_w, im->spp, swap);
+        else if (im->bpp == 4) unpredict<uint32_t>(out.data(), rows, L.seg_w, im->spp, swap);
+    } else if (im->predictor == 3) {
+        unpredict_fp(out.data(), rows, L.seg_w, im->bpp, im->big, comp);
     }
     return OMR_OK;
 }
@@ -380,7 +456,13 @@ struct TiffSource final : omr::SegSource {
         tag = "tiff";
         noun = "segment";
         geom.seg_w = L.seg_w; geom.seg_h = L.seg_h; geom.across = L.across; geom.down = L.down; geom.bpp = im->bpp;
-        codec = im->compression == 5 ? omr::SegCodec::lzw : omr::SegCodec::none;
+        geom.spp = im->spp;
+        switch (im->compression) {                        // K13a, K14a, K16a
+        case 5: codec = omr::SegCodec::lzw; break;
+        case 8: codec = omr::SegCodec::zlib; break;
+        case 50000: codec = omr::SegCodec::zstd; break;
+        default: codec = omr::SegCodec::none; break;
+        }
         predictor = im->predictor;
         swap = im->big == host_little_endian();
         pt = im->pt; big = im->big;
@@ -388,9 +470,11 @@ struct TiffSource final : omr::SegSource {
     const Segments& table(const omr::SegKey& k) const { return im->segs[(size_t)k.plane][level]; }
     size_t slot(const omr::SegKey& k) const { return (size_t)k.sy * geom.across + k.sx; }
     int64_t plane_of(const omr_raw_tile_request& r) const override { return plane_index(im, r.z, r.c, r.t); }
+    int32_t sample_of(const omr_raw_tile_request& r) const override { return r.c % im->spp; }
     omr_status sizes(omr::Ctx*, const std::vector<omr::SegKey>& keys, std::vector<omr::SegBytes>& out) override {
         for (size_t k = 0; k < keys.size(); ++k) {
-            out[k].expected = (uint32_t)((size_t)rows_in_segment(im->levels[level], keys[k].sy) * geom.seg_w * geom.bpp);
+            out[k].expected =
+                (uint32_t)((size_t)rows_in_segment(im->levels[level], keys[k].sy) * geom.seg_w * geom.bpp * geom.spp);
             out[k].cnt = table(keys[k]).cnt[slot(keys[k])];
             if (out[k].cnt && codec == omr::SegCodec::none) out[k].cnt = out[k].expected;   // the stored bytes we need
         }
@@ -415,27 +499,28 @@ extern "C" {
 
 omr_status omr_tiff_image_open(const char* path, int32_t size_z, int32_t size_c, int32_t size_t_,
                                const char* dimension_order, omr_tiff_image** out) {
+    return omr_tiff_image_open_ex(path, size_z, size_c, size_t_, dimension_order, nullptr, out);
+}
+
+omr_status omr_tiff_image_open_ex(const char* path, int32_t size_z, int32_t size_c, int32_t size_t_,
+                                  const char* dimension_order, const omr_tiff_open_options* opt, omr_tiff_image** out) {
     if (!out) return OMR_INVALID_ARGUMENT;
     *out = nullptr;
+    uint32_t accept = 0;
+    if (opt) {
+        if (opt->struct_size < sizeof(omr_tiff_open_options)) return OMR_INVALID_ARGUMENT;
+        accept = opt->accept;
+        if (accept & ~(OMR_TIFF_ACCEPT_DEFLATE | OMR_TIFF_ACCEPT_ZSTD | OMR_TIFF_ACCEPT_PREDICTOR3 | OMR_TIFF_ACCEPT_SAMPLES))
+            return OMR_INVALID_ARGUMENT;
+    }
     if (!path || !dimension_order || size_z <= 0 || size_c <= 0 || size_t_ <= 0) return OMR_INVALID_ARGUMENT;
     int64_t n_planes = size_z;
     if (__builtin_mul_overflow(n_planes, (int64_t)size_c, &n_planes) ||
         __builtin_mul_overflow(n_planes, (int64_t)size_t_, &n_planes) || n_planes > (int64_t)kMaxIfds)
         return OMR_INVALID_ARGUMENT;
-    // "XY" and a permutation of Z, C, T: the first of the three varies fastest along the IFD chain
-    if (std::strlen(dimension_order) != 5 || dimension_order[0] != 'X' || dimension_order[1] != 'Y')
-        return OMR_INVALID_ARGUMENT;
     std::unique_ptr<omr_tiff_image> im(new omr_tiff_image);
     im->sz = size_z; im->sc = size_c; im->st = size_t_;
-    int64_t stride = 1;
-    for (int k = 2; k < 5; ++k) {
-        switch (dimension_order[k]) {
-        case 'Z': if (im->stride_z) return OMR_INVALID_ARGUMENT; im->stride_z = stride; stride *= size_z; break;
-        case 'C': if (im->stride_c) return OMR_INVALID_ARGUMENT; im->stride_c = stride; stride *= size_c; break;
-        case 'T': if (im->stride_t) return OMR_INVALID_ARGUMENT; im->stride_t = stride; stride *= size_t_; break;
-        default: return OMR_INVALID_ARGUMENT;
-        }
-    }
+    if (!set_strides(im.get(), dimension_order, size_c)) return OMR_INVALID_ARGUMENT;   // again below, once spp is known
     im->fd = ::open(path, O_RDONLY | O_CLOEXEC);
     if (im->fd < 0) return errno == ENOENT ? OMR_NOT_FOUND : OMR_INVALID_ARGUMENT;
     struct stat sb;
@@ -488,16 +573,22 @@ omr_status omr_tiff_image_open(const char* path, int32_t size_z, int32_t size_c,
                 st = P.read_ifd(main.sub[k - 1], &sub, ignored);
                 if (st) return st;
             }
-            int32_t pt = 0, comp = 0, pred = 0;
-            st = take_ifd(P, k ? sub : main, lv[k], sg[k], pt, comp, pred);
+            int32_t pt = 0, comp = 0, pred = 0, spp = 1;
+            st = take_ifd(P, k ? sub : main, accept, lv[k], sg[k], pt, comp, pred, spp);
             if (st) return st;
             if (first) {
                 im->pt = pt;
                 im->bpp = bytes_per_pixel(pt);
                 im->compression = comp;
                 im->predictor = pred;
+                im->spp = spp;
                 first = false;
-            } else if (pt != im->pt || comp != im->compression || pred != im->predictor) {
+                if (spp > 1) {                           // the chain holds Z * (C / spp) * T IFDs
+                    if (size_c % spp) return OMR_INVALID_ARGUMENT;
+                    n_planes = n_planes / size_c * (size_c / spp);
+                    (void)set_strides(im.get(), dimension_order, size_c / spp);
+                }
+            } else if (pt != im->pt || comp != im->compression || pred != im->predictor || spp != im->spp) {
                 return OMR_INVALID_ARGUMENT;             // planes or levels that disagree
             }
         }
@@ -513,6 +604,8 @@ omr_status omr_tiff_image_open(const char* path, int32_t size_z, int32_t size_c,
 }
 
 void omr_tiff_image_close(omr_tiff_image* img) { delete img; }
+
+int32_t omr_tiff_image_samples_per_pixel(const omr_tiff_image* img) { return img ? img->spp : -(int32_t)OMR_INVALID_ARGUMENT; }
 
 omr_status omr_tiff_image_info(const omr_tiff_image* img, omr_tiff_info* info) {
     if (!img || !info) return OMR_INVALID_ARGUMENT;
@@ -556,7 +649,7 @@ omr_status omr_tiff_image_get_tile(const omr_tiff_image* img, int32_t level, int
     const Segments& S = img->segs[(size_t)plane_index(img, z, c, t)][(size_t)level];
     std::vector<uint8_t> comp, seg;
     uint8_t* out = static_cast<uint8_t*>(dst);
-    const size_t bpp = (size_t)img->bpp;
+    const size_t bpp = (size_t)img->bpp, spp = (size_t)img->spp, sample = (size_t)(c % img->spp);
     for (int32_t sy = y / L.seg_h; sy <= (y + h - 1) / L.seg_h; ++sy)
         for (int32_t sx = x / L.seg_w; sx <= (x + w - 1) / L.seg_w; ++sx) {
             const omr_status st = load_segment(img, L, S, sx, sy, comp, seg);
@@ -564,9 +657,13 @@ omr_status omr_tiff_image_get_tile(const omr_tiff_image* img, int32_t level, int
             const int32_t ox = sx * L.seg_w, oy = sy * L.seg_h;
             const int32_t X0 = std::max(x, ox), X1 = std::min(x + w, ox + L.seg_w);
             const int32_t Y0 = std::max(y, oy), Y1 = std::min(y + h, oy + L.seg_h);
-            for (int32_t yy = Y0; yy < Y1; ++yy)
-                std::memcpy(out + ((size_t)(yy - y) * w + (X0 - x)) * bpp,
-                            seg.data() + ((size_t)(yy - oy) * L.seg_w + (X0 - ox)) * bpp, (size_t)(X1 - X0) * bpp);
+            for (int32_t yy = Y0; yy < Y1; ++yy) {
+                uint8_t* d = out + ((size_t)(yy - y) * w + (X0 - x)) * bpp;
+                const uint8_t* s = seg.data() + (((size_t)(yy - oy) * L.seg_w + (X0 - ox)) * spp + sample) * bpp;
+                if (spp == 1) std::memcpy(d, s, (size_t)(X1 - X0) * bpp);
+                else                                        // the one sample out of each chunky pixel
+                    for (int32_t xx = 0; xx < X1 - X0; ++xx) std::memcpy(d + (size_t)xx * bpp, s + (size_t)xx * spp * bpp, bpp);
+            }
         }
     return OMR_OK;
 }

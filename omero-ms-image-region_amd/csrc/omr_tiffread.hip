@@ -1,8 +1,10 @@
 // omr_tiffread.hip — K13: the device half of the tiled TIFF reader (omr_tiffread.cpp).
 //
 // K13a k_lzw_decode: one wave per TIFF LZW segment (a tile or a strip), many segments per launch.
-// K13b k_tiff_place<BPS, PRED, SWAP>: one wave per segment row: undo the horizontal predictor with
-//      a wave prefix sum, crop to the requested region and store into the destination at its pitch.
+// K13b k_tiff_place<BPS, PRED, SWAP, CHUNKY>: one wave per segment row: undo the horizontal predictor
+//      with a wave prefix sum, crop to the requested region and store into the destination at its
+//      pitch; CHUNKY takes one sample out of each interleaved pixel.  k_tiff_place_fp<BPS, BE> does
+//      the same for the floating-point predictor (Predictor 3).
 //
 // TIFF LZW (TIFF 6.0 §13, as libtiff writes and reads it): codes packed MSB first, 9 bits at the
 // start, 256 = Clear, 257 = EOI, first entry 258; "early change": the reader takes 10 bits once its
@@ -248,21 +250,27 @@ __device__ __forceinline__ uint32_t bswap_s(uint32_t v) { return __builtin_bswap
 // from column 0 and stores from x0 on.  Every load is inside the segment (x < x1 <= seg_w, y < y1 <=
 // the segment's rows) and every store inside the placement's rectangle, which the host clipped to
 // the region and the image.
-template <int BPS, int PRED, bool SWAP>
+// CHUNKY: the segment holds P.spp samples per pixel and the placement takes sample P.sample of each
+// (0 <= sample < spp, set by the planner): pixel x of a row is sample x * spp + sample of its seg_w *
+// spp samples, so the same bounds hold (x < x1 <= seg_w gives x * spp + sample < seg_w * spp), and
+// predictor 2 runs per component, spp samples apart, which is the scan over this one component.
+// Without CHUNKY neither field is read and the kernel is what it was for one sample per pixel.
+template <int BPS, int PRED, bool SWAP, bool CHUNKY>
 __global__ void __launch_bounds__(256) k_tiff_place(const TiffPlace* __restrict__ places) {
     typedef typename SampleOf<BPS>::T T;
     const TiffPlace P = places[blockIdx.y];
     const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
     const int rows = P.y1 - P.y0;
+    const int spp = CHUNKY ? P.spp : 1, sample = CHUNKY ? P.sample : 0;
     for (int r = (int)blockIdx.x * 4 + wave; r < rows; r += (int)gridDim.x * 4) {
-        const T* srow = P.src ? reinterpret_cast<const T*>(P.src) + (int64_t)(P.y0 + r) * P.seg_w : nullptr;
+        const T* srow = P.src ? reinterpret_cast<const T*>(P.src) + (int64_t)(P.y0 + r) * P.seg_w * spp + sample : nullptr;
         T* drow = reinterpret_cast<T*>(P.dst) + (int64_t)r * P.dst_pitch;
         if constexpr (PRED == 2 && BPS < 8) {
             uint32_t carry = 0;
             for (int xb = 0; xb < P.x1; xb += 64) {
                 const int x = xb + lane;
                 T v = 0;
-                if (srow && x < P.x1) v = srow[x];
+                if (srow && x < P.x1) v = srow[(int64_t)x * spp];
                 if (SWAP) v = bswap_s(v);
                 uint32_t sum = wave_incl_scan((uint32_t)v, lane) + carry;
                 carry = __shfl(sum, 63);
@@ -271,19 +279,79 @@ __global__ void __launch_bounds__(256) k_tiff_place(const TiffPlace* __restrict_
                 if (x >= P.x0 && x < P.x1) drow[x - P.x0] = o;
             }
         } else {
-            for (int x = P.x0 + lane; x < P.x1; x += 64) drow[x - P.x0] = srow ? srow[x] : (T)0;
+            for (int x = P.x0 + lane; x < P.x1; x += 64) drow[x - P.x0] = srow ? srow[(int64_t)x * spp] : (T)0;
         }
     }
 }
 
-template <int BPS>
+// K13b for the floating-point predictor (Predictor 3, libtiff's fpAcc; one sample per pixel): the
+// grid of k_tiff_place, one wave per segment row.  A row of n = seg_w samples of BPS bytes is stored
+// as BPS planes of n bytes, the most significant byte of every sample first (in either byte order
+// of the file), and the n * BPS bytes are running differences (mod 256) across the whole row, planes
+// included.  So byte x of plane b is the sum of the row's bytes up to b * n + x: the totals of the
+// planes in front (pass 1: over all n columns, whatever the crop) plus a wave scan along the plane
+// (pass 2: in steps of 64 columns up to x1, the carry of each plane kept mod 256).  The lane puts
+// its BPS bytes together in the file's byte order (BE: plane b is byte b of the sample) and stores.
+// No LDS, and no limit on n.
+// Bounds: a load reads byte b * n + x of the row with b < BPS and x < n (pass 1) or x < x1 <= n
+// (pass 2), inside the row's n * BPS bytes, and the row y0 + r < y1 is one of the segment's rows;
+// a store goes to column x - x0 with x0 <= x < x1 of row r < y1 - y0: inside the placement's
+// rectangle, as in k_tiff_place.  The loops' bounds are per-placement scalars, so every shuffle
+// runs with all 64 lanes.
+template <int BPS, bool BE>
+__global__ void __launch_bounds__(256) k_tiff_place_fp(const TiffPlace* __restrict__ places) {
+    typedef typename SampleOf<BPS>::T T;
+    const TiffPlace P = places[blockIdx.y];
+    const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
+    const int rows = P.y1 - P.y0;
+    const int n = P.seg_w;
+    for (int r = (int)blockIdx.x * 4 + wave; r < rows; r += (int)gridDim.x * 4) {
+        T* drow = reinterpret_cast<T*>(P.dst) + (int64_t)r * P.dst_pitch;
+        if (!P.src) {
+            for (int x = P.x0 + lane; x < P.x1; x += 64) drow[x - P.x0] = (T)0;
+            continue;
+        }
+        const uint8_t* srow = P.src + (int64_t)(P.y0 + r) * n * BPS;
+        uint32_t carry[BPS];                                // into plane b: the bytes in front of it, mod 256
+        carry[0] = 0;
+#pragma unroll
+        for (int b = 0; b + 1 < BPS; ++b) {
+            const uint8_t* plane = srow + (int64_t)b * n;
+            uint32_t t = 0;
+            for (int x = lane; x < n; x += 64) t += plane[x];
+            t = __shfl(wave_incl_scan(t, lane), 63);
+            carry[b + 1] = (carry[b] + t) & 255u;
+        }
+        for (int xb = 0; xb < P.x1; xb += 64) {
+            const int x = xb + lane;
+            T o = 0;
+#pragma unroll
+            for (int b = 0; b < BPS; ++b) {
+                uint32_t v = 0;
+                if (x < P.x1) v = srow[(int64_t)b * n + x];
+                const uint32_t sum = wave_incl_scan(v, lane) + carry[b];
+                carry[b] = __shfl(sum, 63) & 255u;
+                o |= (T)(sum & 255u) << (8 * (BE ? b : BPS - 1 - b));
+            }
+            if (x >= P.x0 && x < P.x1) drow[x - P.x0] = o;
+        }
+    }
+}
+
+template <int BPS, bool CHUNKY>
 void launch_place_bps(const dim3& g, hipStream_t s, const TiffPlace* d_places, int pred, bool swap) {
     if (pred == 2) {
-        if (swap) omr_launch(k_tiff_place<BPS, 2, true>, g, dim3(256), 0u, s, d_places);
-        else omr_launch(k_tiff_place<BPS, 2, false>, g, dim3(256), 0u, s, d_places);
+        if (swap) omr_launch(k_tiff_place<BPS, 2, true, CHUNKY>, g, dim3(256), 0u, s, d_places);
+        else omr_launch(k_tiff_place<BPS, 2, false, CHUNKY>, g, dim3(256), 0u, s, d_places);
     } else {
-        omr_launch(k_tiff_place<BPS, 1, false>, g, dim3(256), 0u, s, d_places);
+        omr_launch(k_tiff_place<BPS, 1, false, CHUNKY>, g, dim3(256), 0u, s, d_places);
     }
+}
+
+template <int BPS>
+void launch_place_fp(const dim3& g, hipStream_t s, const TiffPlace* d_places, bool big) {
+    if (big) omr_launch(k_tiff_place_fp<BPS, true>, g, dim3(256), 0u, s, d_places);
+    else omr_launch(k_tiff_place_fp<BPS, false>, g, dim3(256), 0u, s, d_places);
 }
 
 }  // namespace
@@ -300,18 +368,35 @@ omr_status launch_lzw_decode(Ctx* ctx, const StreamTable& t) {
 }
 
 omr_status launch_tiff_place(Ctx* ctx, const TiffPlace* d_places, int32_t n, int32_t max_rows, int32_t bps,
-                             int32_t predictor, bool swap) {
+                             int32_t predictor, bool swap, int32_t spp) {
     if (n <= 0 || max_rows <= 0) return OMR_OK;
     if (predictor == 2 && bps == 8) return fail(ctx, OMR_INVALID_ARGUMENT, "tiff: predictor 2 with 64-bit samples");
+    if (predictor == 3 && ((bps != 4 && bps != 8) || spp != 1))
+        return fail(ctx, OMR_INVALID_ARGUMENT, "tiff: predictor 3 needs float or double samples, one per pixel");
+    if (spp < 1) return fail(ctx, OMR_INVALID_ARGUMENT, "tiff: bad samples per pixel");
+    const bool host_little = [] { const uint16_t one = 1; uint8_t b; std::memcpy(&b, &one, 1); return b == 1; }();
     KernelTimer timer(ctx, kKindTiffPlace, true);
     for (int32_t p0 = 0; p0 < n; p0 += 65535) {           // grid y limit
         const dim3 g((unsigned)std::min(64, (max_rows + 3) / 4), (unsigned)std::min(65535, n - p0));
-        switch (bps) {
-        case 1: launch_place_bps<1>(g, ctx->stream, d_places + p0, predictor, false); break;
-        case 2: launch_place_bps<2>(g, ctx->stream, d_places + p0, predictor, swap); break;
-        case 4: launch_place_bps<4>(g, ctx->stream, d_places + p0, predictor, swap); break;
-        case 8: launch_place_bps<8>(g, ctx->stream, d_places + p0, 1, false); break;
-        default: return fail(ctx, OMR_INVALID_ARGUMENT, "tiff: bad sample width");
+        if (predictor == 3) {                              // swap: the file's order is the other one
+            if (bps == 4) launch_place_fp<4>(g, ctx->stream, d_places + p0, swap == host_little);
+            else launch_place_fp<8>(g, ctx->stream, d_places + p0, swap == host_little);
+        } else if (spp == 1) {
+            switch (bps) {
+            case 1: launch_place_bps<1, false>(g, ctx->stream, d_places + p0, predictor, false); break;
+            case 2: launch_place_bps<2, false>(g, ctx->stream, d_places + p0, predictor, swap); break;
+            case 4: launch_place_bps<4, false>(g, ctx->stream, d_places + p0, predictor, swap); break;
+            case 8: launch_place_bps<8, false>(g, ctx->stream, d_places + p0, 1, false); break;
+            default: return fail(ctx, OMR_INVALID_ARGUMENT, "tiff: bad sample width");
+            }
+        } else {
+            switch (bps) {
+            case 1: launch_place_bps<1, true>(g, ctx->stream, d_places + p0, predictor, false); break;
+            case 2: launch_place_bps<2, true>(g, ctx->stream, d_places + p0, predictor, swap); break;
+            case 4: launch_place_bps<4, true>(g, ctx->stream, d_places + p0, predictor, swap); break;
+            case 8: launch_place_bps<8, true>(g, ctx->stream, d_places + p0, 1, false); break;
+            default: return fail(ctx, OMR_INVALID_ARGUMENT, "tiff: bad sample width");
+            }
         }
     }
     OMR_HIP(ctx, hipGetLastError());

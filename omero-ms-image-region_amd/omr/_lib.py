@@ -108,6 +108,13 @@ class TiffInfo(ctypes.Structure):
         "predictor", "tiled", "segment_width", "segment_height", "big_tiff")]
 
 
+TIFF_ACCEPT = {"deflate": 1, "zstd": 2, "predictor3": 4, "samples": 8}    # OMR_TIFF_ACCEPT_*
+
+
+class TiffOpenOptions(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("accept", ctypes.c_uint32)]
+
+
 class ZarrInfo(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in (
         "size_x", "size_y", "size_z", "size_c", "size_t", "pixel_type", "big_endian", "n_levels", "compression",
@@ -301,6 +308,9 @@ _SIGS = {
     "omr_pixel_buffer_tile_tiff": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _sz,
                                           ctypes.POINTER(_sz)]),
     "omr_tiff_image_open": (_i32, [ctypes.c_char_p, _i32, _i32, _i32, ctypes.c_char_p, ctypes.POINTER(_vp)]),
+    "omr_tiff_image_open_ex": (_i32, [ctypes.c_char_p, _i32, _i32, _i32, ctypes.c_char_p, ctypes.POINTER(TiffOpenOptions),
+                                      ctypes.POINTER(_vp)]),
+    "omr_tiff_image_samples_per_pixel": (_i32, [_vp]),
     "omr_tiff_image_close": (None, [_vp]),
     "omr_tiff_image_info": (_i32, [_vp, ctypes.POINTER(TiffInfo)]),
     "omr_tiff_image_level_sizes": (_i32, [_vp, ctypes.POINTER(_i32), _i32]),

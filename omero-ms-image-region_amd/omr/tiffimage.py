@@ -4,10 +4,13 @@ makes the test and probe files.
 The second backend of pixelsService.getPixelBuffer beside the ROMIO file (pixbuf.PixelBuffer):
 pyramidal OME-TIFF as raw2ometiff writes it, one IFD per plane and the lower resolutions in
 SubIFDs.  Reads go through libomr.so: get_tile on the host (plain serial LZW decoder), read_regions
-and render_tiles with the LZW segments decoded on the GPU (omr_tiffread.hip).
+and render_tiles with the LZW segments decoded on the GPU (omr_tiffread.hip).  With accept=...
+(omr_tiff_image_open_ex) also Deflate and zstd segments, the floating-point predictor and chunky
+pixels of several samples (RGB), each channel one sample.
 """
 import ctypes
 import struct
+import zlib
 
 import numpy as np
 
@@ -80,29 +83,55 @@ class _LzwJob:
         return lzw_encode(raw, self.early_clear, self.eoi)
 
 
-def _predict(seg):
-    """Horizontal differencing (Predictor 2) of a [rows][cols] array, in the sample's own width."""
+def _predict(seg, k=1):
+    """Horizontal differencing (Predictor 2) of a [rows][cols] array, in the sample's own width;
+    with k interleaved samples per pixel, per component: k columns apart."""
     u = np.ascontiguousarray(seg.astype(seg.dtype.newbyteorder("="))).view("u%d" % seg.dtype.itemsize)
     d = u.copy()
-    d[:, 1:] = u[:, 1:] - u[:, :-1]
+    d[:, k:] = u[:, k:] - u[:, :-k]
     return d
+
+
+def _predict_fp(seg):
+    """The floating-point predictor (Predictor 3, libtiff's fpDiff) of a [rows][cols] float array:
+    each row as byte planes, the most significant byte of every sample first (whatever the file's
+    byte order), then byte differences (mod 256) along the whole row.  Returns [rows][cols * B] u1."""
+    rows, cols = seg.shape
+    b = np.ascontiguousarray(seg.astype(seg.dtype.newbyteorder(">"))).view("u1").reshape(rows, cols, seg.dtype.itemsize)
+    b = np.ascontiguousarray(b.transpose(0, 2, 1)).reshape(rows, -1)
+    d = b.copy()
+    d[:, 1:] = b[:, 1:] - b[:, :-1]
+    return d
+
+
+def _zstd_job(raw):
+    from .zarrimage import zstd_encode
+    return zstd_encode(raw)
 
 
 def write_tiled_tiff(path, planes, levels=(), tile=(256, 256), rows_per_strip=None, byteorder="<", bigtiff=False,
                      compression=1, predictor=1, early_clear=0, eoi=True, dimension_order="XYZCT",
-                     skip_zero_segments=False, tag_overrides=None, mapper=map):
+                     skip_zero_segments=False, tag_overrides=None, mapper=map, samples_per_pixel=1, encoder=None):
     """Write a [t][c][z][y][x] array as a TIFF with one IFD per plane (in `dimension_order`), and
     `levels` (arrays of the same [t][c][z] with their own [y][x]) as SubIFDs of each plane.
-    tile = (w, h), or rows_per_strip = n for strips; byteorder "<" (II) or ">" (MM); compression 1
-    or 5 (LZW, lzw_encode with early_clear / eoi); predictor 1 or 2 (integer samples up to 32 bits);
+    tile = (w, h), or rows_per_strip = n for strips; byteorder "<" (II) or ">" (MM); compression 1,
+    5 (LZW, lzw_encode with early_clear / eoi), 8 or 32946 (Deflate: zlib.compress) or 50000
+    (omr.zstd_encode); predictor 1, 2 (integer samples up to 32 bits) or 3 (float32 and float64,
+    one sample per pixel); samples_per_pixel = k > 1: every k consecutive channels are interleaved
+    into one chunky IFD (tags 277 = k, 284 = 1, Photometric 2 from three samples on, the others
+    ExtraSamples), predictor 2 then k samples apart, and the chain holds c / k IFDs per (z, t);
     skip_zero_segments: an all-zero segment is written with byte count 0; tag_overrides = {tag:
     value} replaces the value written for a SHORT tag (to make files a reader must reject); mapper:
-    a map() that encodes the LZW segments of one image, e.g. a multiprocessing pool's for big files.
+    a map() that encodes the segments of one image, e.g. a multiprocessing pool's for big files;
+    encoder: a function bytes -> bytes in place of the codec's own (libzstd's, say, for 50000).
     Returns {"ifds": [offset per plane], "subifds": [[offsets] per plane]}."""
     planes = np.asarray(planes)
     assert planes.ndim == 5, "planes must be [t][c][z][y][x]"
     levels = [np.asarray(lv) for lv in levels]
     st, sc, sz = planes.shape[:3]
+    spp = int(samples_per_pixel)
+    assert 1 <= spp and sc % spp == 0, "samples_per_pixel must divide the channel count"
+    assert predictor != 3 or (planes.dtype.kind == "f" and spp == 1), "predictor 3: float samples, one per pixel"
     for lv in levels:
         assert lv.ndim == 5 and lv.shape[:3] == planes.shape[:3] and lv.dtype == planes.dtype
     assert dimension_order in DIMENSION_ORDERS
@@ -120,7 +149,7 @@ def write_tiled_tiff(path, planes, levels=(), tile=(256, 256), rows_per_strip=No
 
     def segments(img):
         """(offsets, counts, geometry tags) of one image; the data goes into buf."""
-        h, w = img.shape
+        h, w = img.shape[:2]
         if rows_per_strip is None:
             tw, th = tile
             boxes = [(x, y, tw, th) for y in range(0, h, th) for x in range(0, w, tw)]
@@ -128,18 +157,24 @@ def write_tiled_tiff(path, planes, levels=(), tile=(256, 256), rows_per_strip=No
             boxes = [(0, y, w, min(rows_per_strip, h - y)) for y in range(0, h, rows_per_strip)]
         raws = []
         for (x, y, bw, bh) in boxes:
-            seg = np.zeros((bh, bw), dtype=fdt)
+            seg = np.zeros((bh, bw) + img.shape[2:], dtype=fdt)
             part = img[y:y + bh, x:x + bw]
             seg[:part.shape[0], :part.shape[1]] = part
             if skip_zero_segments and not part.any():
                 raws.append(None)
                 continue
+            seg = seg.reshape(bh, -1)                    # chunky: bw * spp samples per row
             if predictor == 2:
-                seg = _predict(seg).astype(np.dtype("u%d" % dt.itemsize).newbyteorder(bo) if dt.itemsize > 1 else "u1")
+                seg = _predict(seg, spp).astype(np.dtype("u%d" % dt.itemsize).newbyteorder(bo) if dt.itemsize > 1 else "u1")
+            elif predictor == 3:
+                seg = _predict_fp(seg)
             raws.append(seg.tobytes())
-        if compression == 5:
+        job = {5: _LzwJob(early_clear, eoi), 8: zlib.compress, 32946: zlib.compress, 50000: _zstd_job}.get(compression)
+        if encoder is not None and job is not None:
+            job = encoder
+        if job is not None:
             todo = [r for r in raws if r is not None]
-            done = iter(list(mapper(_LzwJob(early_clear, eoi), todo)))
+            done = iter(list(mapper(job, todo)))
             raws = [None if r is None else next(done) for r in raws]
         offs, cnts = [], []
         for raw in raws:
@@ -159,9 +194,12 @@ def write_tiled_tiff(path, planes, levels=(), tile=(256, 256), rows_per_strip=No
         return geom
 
     def ifd_entries(img, n_sub):
-        h, w = img.shape
-        ent = [(256, "I", [w]), (257, "I", [h]), (258, "H", [8 * dt.itemsize]), (259, "H", [compression]),
-               (262, "H", [1]), (277, "H", [1]), (284, "H", [1]), (339, "H", [kind])]
+        h, w = img.shape[:2]
+        ent = [(256, "I", [w]), (257, "I", [h]), (258, "H", [8 * dt.itemsize] * spp), (259, "H", [compression]),
+               (262, "H", [2 if spp >= 3 else 1]), (277, "H", [spp]), (284, "H", [1]), (339, "H", [kind] * spp)]
+        n_extra = spp - 3 if spp >= 3 else spp - 1
+        if n_extra:
+            ent.append((338, "H", [0] * n_extra))        # ExtraSamples: unspecified data
         if predictor != 1 or 317 in tag_overrides:
             ent.append((317, "H", [predictor]))
         if 266 in tag_overrides:
@@ -202,11 +240,16 @@ def write_tiled_tiff(path, planes, levels=(), tile=(256, 256), rows_per_strip=No
         return at, where
 
     # plane order along the chain: the first letter behind XY varies fastest
-    sizes = {"Z": sz, "C": sc, "T": st}
+    sizes = {"Z": sz, "C": sc // spp, "T": st}
     order = dimension_order[2:]
     result = {"ifds": [], "subifds": []}
     prev_next = 8 if bigtiff else 4                         # where the offset of the next main IFD goes
-    n_planes = sz * sc * st
+    n_planes = sz * (sc // spp) * st
+
+    def image_of(a, t, c, z):
+        """The pixels of IFD (t, c, z): [y][x], or [y][x][spp] of the channels c * spp .. interleaved."""
+        return a[t, c, z] if spp == 1 else np.moveaxis(a[t, c * spp:(c + 1) * spp, z], 0, -1)
+
     for k in range(n_planes):
         idx, r = {}, k
         for letter in order:
@@ -215,9 +258,9 @@ def write_tiled_tiff(path, planes, levels=(), tile=(256, 256), rows_per_strip=No
         t, c, z = idx["T"], idx["C"], idx["Z"]
         subs = []
         for lv in levels:
-            at, _ = emit_ifd(ifd_entries(lv[t, c, z], 0))
+            at, _ = emit_ifd(ifd_entries(image_of(lv, t, c, z), 0))
             subs.append(at)
-        at, where = emit_ifd(ifd_entries(planes[t, c, z], len(subs)))
+        at, where = emit_ifd(ifd_entries(image_of(planes, t, c, z), len(subs)))
         if subs:
             struct.pack_into(bo + ofmt * len(subs), buf, where[330], *subs)
         struct.pack_into(bo + ofmt, buf, prev_next, at)
@@ -234,10 +277,24 @@ class TiffImage:
     """An open tiled TIFF / OME-TIFF (omr_tiff_image).  The caller gives Z, C, T and the dimension
     order as for PixelBuffer; OME-XML is not parsed."""
 
-    def __init__(self, path, size_z=1, size_c=1, size_t=1, dimension_order="XYZCT"):
+    def __init__(self, path, size_z=1, size_c=1, size_t=1, dimension_order="XYZCT", accept=()):
+        """accept: the further forms a file may use, any of "deflate", "zstd", "predictor3" and
+        "samples" (omr_tiff_image_open_ex); empty: the plain open, which refuses them all.  size_c
+        counts every sample of a chunky image as a channel (3 for an RGB image)."""
         h = ctypes.c_void_p()
-        st = lib.omr_tiff_image_open(str(path).encode(), int(size_z), int(size_c), int(size_t),
-                                     str(dimension_order).encode(), ctypes.byref(h))
+        accept = (accept,) if isinstance(accept, str) else tuple(accept)
+        if not accept:
+            st = lib.omr_tiff_image_open(str(path).encode(), int(size_z), int(size_c), int(size_t),
+                                         str(dimension_order).encode(), ctypes.byref(h))
+        else:
+            bits = 0
+            for name in accept:
+                if name not in _lib.TIFF_ACCEPT:
+                    raise _lib.OmrError(_lib.INVALID_ARGUMENT, f"unknown TIFF form {name!r}")
+                bits |= _lib.TIFF_ACCEPT[name]
+            opt = _lib.TiffOpenOptions(ctypes.sizeof(_lib.TiffOpenOptions), bits)
+            st = lib.omr_tiff_image_open_ex(str(path).encode(), int(size_z), int(size_c), int(size_t),
+                                            str(dimension_order).encode(), ctypes.byref(opt), ctypes.byref(h))
         if st != _lib.OK:
             raise _lib.OmrError(st, f"cannot open TIFF image {path}")
         self.h = h
@@ -247,6 +304,7 @@ class TiffImage:
         self.size_x, self.size_y = i.size_x, i.size_y
         self.size_z, self.size_c, self.size_t = i.size_z, i.size_c, i.size_t
         self.pixel_type = i.pixel_type
+        self.samples_per_pixel = int(lib.omr_tiff_image_samples_per_pixel(self.h))
         self.big_endian = bool(i.big_endian)
         self.dtype = np.dtype((">" if self.big_endian else "<") + _NP_NAMES[self.pixel_type])
         sizes = (ctypes.c_int32 * (2 * i.n_levels))()

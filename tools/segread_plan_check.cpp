@@ -7,6 +7,9 @@
 // untouched, the unique-segment list must name every segment once, and a placement must read the
 // plane of its own request.  The segment buffers are exactly as large as the front-ends' rule makes
 // them (tiles whole, the last strip short), so a placement that reaches past one is caught.
+// The same runs again on chunky segments of three samples per pixel: the three channels are the
+// samples of one plane, a placement takes its request's sample out of every pixel, and requests for
+// the channels of the same pixels share their segments.
 // Built and run by `make -C omero-ms-image-region_amd segread-plan-check`.
 #include <cstdint>
 #include <cstdio>
@@ -25,11 +28,13 @@ using omr::SegPlan;
 typedef omr_raw_tile_request Req;   // {z, c, t, x, y}
 
 constexpr int32_t kW = 40, kH = 20, kSZ = 2, kSC = 3;
-static int64_t plane_of(const Req& r) { return ((int64_t)r.t * kSC + r.c) * kSZ + r.z; }
+static int32_t g_spp = 1;           // samples per pixel of the case at hand: 1, or kSC (one plane per (z, t))
+static int64_t plane_of(const Req& r) { return ((int64_t)r.t * (kSC / g_spp) + r.c / g_spp) * kSZ + r.z; }
+static int32_t sample_of(const Req& r) { return r.c % g_spp; }
 
-// Byte j of the sample at (x, y) of a plane.
-static uint8_t sample_byte(int64_t plane, int32_t y, int32_t x, int j) {
-    const uint64_t v = ((uint64_t)plane * 1000003u + (uint64_t)y * 1009u + (uint64_t)x) * 0x9E3779B97F4A7C15ull + 1;
+// Byte j of sample `sample` of the pixel at (x, y) of a plane.
+static uint8_t sample_byte(int64_t plane, int32_t sample, int32_t y, int32_t x, int j) {
+    const uint64_t v = (((uint64_t)plane * 4u + (uint64_t)sample) * 1000003u + (uint64_t)y * 1009u + (uint64_t)x) * 0x9E3779B97F4A7C15ull + 1;
     return (uint8_t)(v >> (8 * (j & 7)) ^ v >> 56);
 }
 
@@ -40,9 +45,9 @@ struct Case {
     int32_t rows(int32_t sy) const { return tiled ? g.seg_h : std::min(g.seg_h, kH - sy * g.seg_h); }   // the front-ends' rule
 };
 
-static Case make_case(int32_t seg_w, int32_t seg_h, int32_t bpp, bool tiled) {
+static Case make_case(int32_t seg_w, int32_t seg_h, int32_t bpp, bool tiled, int32_t spp = 1) {
     Case c;
-    c.g.seg_w = seg_w; c.g.seg_h = seg_h; c.g.bpp = bpp;
+    c.g.seg_w = seg_w; c.g.seg_h = seg_h; c.g.bpp = bpp; c.g.spp = spp;
     c.g.across = (kW + seg_w - 1) / seg_w;
     c.g.down = (kH + seg_h - 1) / seg_h;
     c.tiled = tiled;
@@ -53,11 +58,12 @@ static Case make_case(int32_t seg_w, int32_t seg_h, int32_t bpp, bool tiled) {
 static void run(const Case& c, const std::vector<Req>& reqs, int32_t r0, int32_t r1, int32_t width, int32_t height,
                 const std::tuple<int64_t, int32_t, int32_t>* missing = nullptr) {
     const SegGeom& g = c.g;
-    const size_t bpp = (size_t)g.bpp;
+    g_spp = g.spp;
+    const size_t bpp = (size_t)g.bpp, spp = (size_t)g.spp;
     const int64_t stride = ((int64_t)width * height + 3) * g.bpp;          // three samples of padding behind a region
     std::vector<uint8_t> dst((size_t)stride * reqs.size(), 0xAB);
     std::vector<int> written((size_t)(stride / g.bpp) * reqs.size(), 0);
-    const SegPlan P = omr::plan_regions(g, reqs.data(), r0, r1, width, height, dst.data(), stride, plane_of);
+    const SegPlan P = omr::plan_regions(g, reqs.data(), r0, r1, width, height, dst.data(), stride, plane_of, sample_of);
 
     // the unique segments: each once, inside the level, their buffers as the front-end sizes them
     std::set<std::tuple<int64_t, int32_t, int32_t>> seen;
@@ -68,12 +74,14 @@ static void run(const Case& c, const std::vector<Req>& reqs, int32_t r0, int32_t
         CHECK(seen.insert(std::make_tuple(s.plane, s.sx, s.sy)).second);
         if (missing && *missing == std::make_tuple(s.plane, s.sx, s.sy)) continue;
         const int32_t rows = c.rows(s.sy);
-        bufs[k].assign((size_t)rows * g.seg_w * bpp, 0xEE);                  // 0xEE: behind the level's edge
+        bufs[k].assign((size_t)rows * g.seg_w * spp * bpp, 0xEE);            // 0xEE: behind the level's edge
         for (int32_t y = 0; y < rows; ++y)
             for (int32_t x = 0; x < g.seg_w; ++x) {
                 const int32_t gx = s.sx * g.seg_w + x, gy = s.sy * g.seg_h + y;
                 if (gx >= kW || gy >= kH) continue;
-                for (size_t j = 0; j < bpp; ++j) bufs[k][((size_t)y * g.seg_w + x) * bpp + j] = sample_byte(s.plane, gy, gx, (int)j);
+                for (size_t q = 0; q < spp; ++q)
+                    for (size_t j = 0; j < bpp; ++j)
+                        bufs[k][(((size_t)y * g.seg_w + x) * spp + q) * bpp + j] = sample_byte(s.plane, (int32_t)q, gy, gx, (int)j);
             }
     }
 
@@ -93,13 +101,14 @@ static void run(const Case& c, const std::vector<Req>& reqs, int32_t r0, int32_t
         CHECK(region >= (size_t)r0 && region < (size_t)r1);
         const omr::SegKey& s = P.segs[(size_t)P.place_seg[k]];
         CHECK(s.plane == plane_of(reqs[region]));                           // no two planes share an entry
+        CHECK(p.spp == g.spp && p.sample == sample_of(reqs[region]));
         const std::vector<uint8_t>& src = bufs[(size_t)P.place_seg[k]];
         for (int32_t y = p.y0; y < p.y1; ++y)
             for (int32_t x = p.x0; x < p.x1; ++x) {
                 const size_t d = at + ((size_t)(y - p.y0) * p.dst_pitch + (x - p.x0)) * bpp;
                 if (d + bpp > dst.size()) { CHECK(!"placement past the destination"); continue; }
                 if (src.empty()) std::memset(&dst[d], 0, bpp);
-                else std::memcpy(&dst[d], &src[((size_t)y * p.seg_w + x) * bpp], bpp);
+                else std::memcpy(&dst[d], &src[(((size_t)y * p.seg_w + x) * (size_t)p.spp + (size_t)p.sample) * bpp], bpp);
                 ++written[d / bpp];
             }
     }
@@ -118,7 +127,7 @@ static void run(const Case& c, const std::vector<Req>& reqs, int32_t r0, int32_t
                 if (inside) {
                     const int32_t gx = r.x + (int32_t)(e % width), gy = r.y + (int32_t)(e / width);
                     const auto seg = std::make_tuple(plane_of(r), gx / g.seg_w, gy / g.seg_h);
-                    want = missing && *missing == seg ? 0 : sample_byte(plane_of(r), gy, gx, (int)j);
+                    want = missing && *missing == seg ? 0 : sample_byte(plane_of(r), sample_of(r), gy, gx, (int)j);
                 }
                 CHECK(dst[d + j] == want);
             }
@@ -127,6 +136,7 @@ static void run(const Case& c, const std::vector<Req>& reqs, int32_t r0, int32_t
 }
 
 static void geometry(const Case& c) {
+    g_spp = c.g.spp;
     const Req a{0, 0, 0, 0, 0};
     run(c, {a}, 0, 1, 1, 1);                                            // 1 x 1 at (0, 0)
     run(c, {{0, 0, 0, 39, 19}}, 0, 1, 1, 1);                            // and at (39, 19)
@@ -146,6 +156,22 @@ int main() {
     for (int32_t bpp : {1, 2, 8}) {
         geometry(make_case(16, 8, bpp, true));                            // tiles: both edges ragged
         geometry(make_case(kW, 8, bpp, false));                           // strips: the last one has 4 rows
+        geometry(make_case(16, 8, bpp, true, kSC));                       // the same, three samples per pixel
+        geometry(make_case(kW, 8, bpp, false, kSC));
+    }
+    // the three channels of the same pixels: one plane, so one entry per segment, and a placement per sample
+    {
+        const Case c = make_case(16, 8, 2, true, kSC);
+        g_spp = kSC;
+        const std::vector<Req> reqs = {{1, 0, 1, 2, 1}, {1, 1, 1, 2, 1}, {1, 2, 1, 2, 1}, {0, 2, 1, 2, 1}};
+        run(c, reqs, 0, 4, 20, 9);
+        std::vector<uint8_t> dst(4 * 80);
+        const SegPlan P = omr::plan_regions(c.g, reqs.data(), 0, 4, 9, 4, dst.data(), 80, plane_of, sample_of);
+        CHECK(P.segs.size() == 2 && P.places.size() == 4);
+        CHECK(P.place_seg == (std::vector<int32_t>{0, 0, 0, 1}));
+        CHECK(P.places[0].sample == 0 && P.places[1].sample == 1 && P.places[2].sample == 2 && P.places[3].sample == 2);
+        CHECK(omr::read_bytes_per_request(c.g, 17, 9) == 3u * 3u * 768u);
+        g_spp = 1;
     }
     // the unique list is in first-touch order and shared between the requests of a group
     {

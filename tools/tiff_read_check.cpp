@@ -5,6 +5,12 @@
 // stream that ends early -- and after that byte by byte at random; every damaged file must be
 // answered with a status, never with a read or write out of bounds.  The decoder's output buffers
 // are exactly as large as the segment, so a byte written past one is caught.
+// With a directory as its argument (written by tests/tiff_codec_cases.py dump(), in a Python that
+// never sees this program) the forms of omr_tiff_image_open_ex follow: good files of libtiff and of
+// the project's writer with Deflate and zstd segments, Predictor 3 and chunky pixels are read
+// through open_ex / get_tile and compared with their pixels, refused without their accept bits,
+// then truncated and damaged at random like the LZW file.  The program links the inflate and zstd
+// host decoders (omr_zarr.cpp, omr_blosc.cpp, omr_zstd.cpp) beside omr_tiffread.cpp.
 // Built and run by `make -C omero-ms-image-region_amd tiff-read-check`.
 #include <unistd.h>
 
@@ -177,7 +183,124 @@ static omr_status run(const std::vector<uint8_t>& f, const Built* expect = nullp
     return first;
 }
 
-int main() {
+static std::vector<uint8_t> slurp(const std::string& path) {
+    std::vector<uint8_t> out;
+    std::FILE* fp = std::fopen(path.c_str(), "rb");
+    if (!fp) {
+        std::printf("cannot read %s\n", path.c_str());
+        std::exit(2);
+    }
+    uint8_t buf[65536];
+    size_t n;
+    while ((n = std::fread(buf, 1, sizeof buf, fp)) > 0) out.insert(out.end(), buf, buf + n);
+    std::fclose(fp);
+    return out;
+}
+
+// One file of the new forms through open_ex and, when that works, every channel of level 0 whole,
+// in a crop and in its last pixel, and level 1 whole; `px`: the pixels a good file must give.
+static omr_status run_ex(const std::vector<uint8_t>& f, int size_c, uint32_t accept, const std::vector<uint8_t>* px = nullptr) {
+    put_file(f);
+    omr_tiff_image* img = nullptr;
+    const omr_tiff_open_options opt = {(uint32_t)sizeof(omr_tiff_open_options), accept};
+    omr_status st = omr_tiff_image_open_ex(g_path.c_str(), 1, size_c, 1, "XYZCT", &opt, &img);
+    if (st) {
+        CHECK(img == nullptr);
+        return st;
+    }
+    omr_tiff_info info;
+    CHECK(omr_tiff_image_info(img, &info) == OMR_OK);
+    const int32_t spp = omr_tiff_image_samples_per_pixel(img);
+    CHECK(spp >= 1 && spp <= 4 && size_c % spp == 0);
+    int32_t sizes[4] = {0, 0, 0, 0};
+    const int32_t levels = omr_tiff_image_level_sizes(img, sizes, 2);
+    CHECK(levels >= 1);
+    omr_status first = OMR_OK;
+    const size_t bpp = (size_t)omr::bytes_per_pixel(info.pixel_type);
+    if (sizes[0] <= 4096 && sizes[1] <= 4096 && info.segment_width <= 4096 && info.segment_height <= 4096) {
+        for (int c = 0; c < size_c; ++c) {
+            const size_t plane = (size_t)sizes[0] * sizes[1] * bpp;
+            std::vector<uint8_t> out(plane);                 // exactly: ASan guards the rest
+            st = omr_tiff_image_get_tile(img, 0, 0, c, 0, 0, 0, sizes[0], sizes[1], out.data(), out.size());
+            if (st && !first) first = st;
+            if (px) CHECK(!st && px->size() >= plane * (c + 1) && std::memcmp(out.data(), px->data() + plane * c, plane) == 0);
+            if (sizes[0] > 9 && sizes[1] > 9) {
+                std::vector<uint8_t> crop((size_t)(sizes[0] - 8) * (sizes[1] - 9) * bpp);
+                st = omr_tiff_image_get_tile(img, 0, 0, c, 0, 5, 7, sizes[0] - 8, sizes[1] - 9, crop.data(), crop.size());
+                if (st && !first) first = st;
+                if (px && !st)
+                    for (int y = 0; y < sizes[1] - 9; ++y)
+                        CHECK(std::memcmp(&crop[(size_t)y * (sizes[0] - 8) * bpp],
+                                          px->data() + plane * c + ((size_t)(y + 7) * sizes[0] + 5) * bpp,
+                                          (size_t)(sizes[0] - 8) * bpp) == 0);
+            }
+            std::vector<uint8_t> one(bpp);
+            st = omr_tiff_image_get_tile(img, 0, 0, c, 0, sizes[0] - 1, sizes[1] - 1, 1, 1, one.data(), one.size());
+            if (st && !first) first = st;
+            if (levels > 1 && sizes[2] <= 4096 && sizes[3] <= 4096) {
+                std::vector<uint8_t> low((size_t)sizes[2] * sizes[3] * bpp);
+                st = omr_tiff_image_get_tile(img, 1, 0, c, 0, 0, 0, sizes[2], sizes[3], low.data(), low.size());
+                if (st && !first) first = st;
+            }
+        }
+    }
+    omr_tiff_image_close(img);
+    return first;
+}
+
+// The files of the directory: good, refused without their bits, truncated, damaged at random.
+static void new_forms(const std::string& dir) {
+    std::FILE* mf = std::fopen((dir + "/manifest.txt").c_str(), "r");
+    if (!mf) {
+        std::printf("cannot read %s/manifest.txt\n", dir.c_str());
+        std::exit(2);
+    }
+    char name[256];
+    int size_c, accept, bpp, files = 0, still = 0, tried = 0;
+    uint64_t rng = 0xD1B54A32D192ED03ull;
+    auto next = [&] {
+        rng ^= rng << 13; rng ^= rng >> 7; rng ^= rng << 17;
+        return rng;
+    };
+    while (std::fscanf(mf, "%255s %d %d %d", name, &size_c, &accept, &bpp) == 4) {
+        ++files;
+        const std::vector<uint8_t> good = slurp(dir + "/" + name + ".tif"), px = slurp(dir + "/" + name + ".px");
+        CHECK(run_ex(good, size_c, (uint32_t)accept, &px) == OMR_OK);
+        CHECK(run_ex(good, size_c, 15u, &px) == OMR_OK);
+        CHECK(run_ex(good, size_c, 0u) == OMR_INVALID_ARGUMENT);
+        for (uint32_t bit = 1; bit <= 8; bit <<= 1)
+            if ((uint32_t)accept & bit) CHECK(run_ex(good, size_c, 15u & ~bit) == OMR_INVALID_ARGUMENT);
+        CHECK(run_ex(good, size_c, 16u) == OMR_INVALID_ARGUMENT);
+        {
+            put_file(good);
+            omr_tiff_image* img = nullptr;
+            const omr_tiff_open_options small = {4, (uint32_t)accept};
+            CHECK(omr_tiff_image_open_ex(g_path.c_str(), 1, size_c, 1, "XYZCT", &small, &img) == OMR_INVALID_ARGUMENT && !img);
+            CHECK(omr_tiff_image_open(g_path.c_str(), 1, size_c, 1, "XYZCT", &img) == OMR_INVALID_ARGUMENT && !img);
+        }
+        std::vector<uint8_t> f;
+        for (int k = 1; k <= 12; ++k) {                     // truncated: a status, never a bad access
+            f.assign(good.begin(), good.begin() + good.size() * k / 13);
+            CHECK(run_ex(f, size_c, 15u) != OMR_OK);
+        }
+        for (int it = 0; it < 250; ++it) {                  // most of the file is segment data: the decoders' input
+            f = good;
+            const int hits = 1 + (int)(next() % 3);
+            for (int k = 0; k < hits; ++k) {
+                const size_t at = next() % f.size();
+                f[at] = next() % 3 ? (uint8_t)next() : (uint8_t)(f[at] ^ (1u << (next() % 8)));
+            }
+            if (it % 9 == 0) f.resize(1 + next() % f.size());
+            ++tried;
+            still += run_ex(f, size_c, 15u) == OMR_OK;
+        }
+    }
+    std::fclose(mf);
+    CHECK(files >= 10);
+    std::printf("tiff_read_check: %d files of the new forms; %d of %d damaged ones still read\n", files, still, tried);
+}
+
+int main(int argc, char** argv) {
     char tmpl[] = "/tmp/tiff_read_check_XXXXXX";
     const int fd = mkstemp(tmpl);
     if (fd < 0) return 2;
@@ -277,6 +400,7 @@ int main() {
         opened += run(f) == OMR_OK;
     }
     std::printf("tiff_read_check: %d of 3000 damaged files still read\n", opened);
+    if (argc > 1) new_forms(argv[1]);
     ::unlink(g_path.c_str());
     std::printf(g_fail ? "tiff_read_check: %d check(s) failed\n" : "tiff_read_check: ok\n", g_fail);
     return g_fail ? 1 : 0;

@@ -9,12 +9,23 @@ The same pixels are served from
   lzw_p2_256   LZW + predictor 2, 256 x 256 tiles      TiffImage.render_tiles (K13a + K13b + K2)
   lzw_p2_512   LZW + predictor 2, 512 x 512 tiles      "
   raw_256      uncompressed 256 x 256 tiles            " (K13b + K2; K13a is skipped)
+  deflate_p2_256  Deflate (zlib level 6) + predictor 2, 256 x 256 tiles   " (K14a + K13b + K2), opened with accept
+  zstd_p2_256     zstd (libzstd level 3) + predictor 2, 256 x 256 tiles   " (K16a + K13b + K2); skipped without libzstd.so.1
   romio        a ROMIO file                            Context.render_pixel_buffer_tiles
 
-each into device memory.  Per pass: wall time, requests/s, and the kernel times of
-omr_ctx_kernel_timings (kind 30 K13a, 31 K13b, 2 K2) with the decoded GB/s they give.  CPU figures
-for the same segments: the library's host decoder (omr_lzw_decode_host) on 16 threads, and
-Pillow / libtiff decoding the same file frame by frame on one thread.
+each into device memory, and the RGB variant of the run: bits 4..11 of the first three channels as
+an 8-bit image (noisy low bits, as hard for the coders as the 16-bit files), the 32 positions once
+each (a group of the renderer holds 85 such requests, so repeats would share their segments and be
+decoded once) with red / green / blue bindings, served from
+
+  rgb_lzw_planes_256  three IFDs per plane position, LZW + predictor 2        (K13a + K13b + K2)
+  rgb_deflate_256     one chunky IFD of three samples, Deflate + predictor 2  (K14a + K13b strided + K2):
+                      every segment is read and inflated once and placed three times
+
+Per pass: wall time, requests/s, and the kernel times of omr_ctx_kernel_timings (kind 30 K13a, 32
+K14a, 35 K16a, 31 K13b, 2 K2) with the decoded GB/s they give.  CPU figures for the same segments:
+the library's host decoder (omr_lzw_decode_host, omr_inflate_host, omr_zstd_decode_host) on 16
+threads, and Pillow / libtiff decoding the same file frame by frame on one thread.
 
     python3 tools/tiff_read_probe.py --json profiles/k13/tiff_read_probe.json
     python3 tools/tiff_read_probe.py --cpu-only        (files and the CPU figures, no GPU)
@@ -77,18 +88,43 @@ def segment_table(path, n_planes):
     return out
 
 
-def cpu_figures(path, tile, n_planes, decoded_bytes):
+def libzstd():
+    """libzstd.so.1 through ctypes, or None: the project's own zstd_encode stores noisy tiles raw."""
+    import ctypes
+    try:
+        z = ctypes.CDLL("libzstd.so.1")
+    except OSError:
+        return None
+    z.ZSTD_compressBound.restype = ctypes.c_size_t
+    z.ZSTD_compressBound.argtypes = [ctypes.c_size_t]
+    z.ZSTD_compress.restype = ctypes.c_size_t
+    z.ZSTD_compress.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int]
+    z.ZSTD_isError.argtypes = [ctypes.c_size_t]
+    return z
+
+
+def zstd_level3(raw):
+    import ctypes
+    z = libzstd()
+    cap = z.ZSTD_compressBound(len(raw))
+    out = ctypes.create_string_buffer(cap)
+    n = z.ZSTD_compress(out, cap, raw, len(raw), 3)
+    assert not z.ZSTD_isError(n)
+    return out.raw[:n]
+
+
+def cpu_figures(path, expected, n_planes, decoded_bytes, decoder="omr_lzw_decode_host"):
     from omr import _lib
     segs = segment_table(path, n_planes)
     with open(path, "rb") as f:
         blob = np.frombuffer(f.read(), dtype=np.uint8)
-    expected = tile * tile * 2
     outs = [np.empty(expected, dtype=np.uint8) for _ in range(16)]
+    decode = getattr(_lib.lib, decoder)
 
     def work(k):
         out = outs[k]
         for off, cnt in segs[k::16]:
-            st = _lib.lib.omr_lzw_decode_host(blob.ctypes.data + off, cnt, out.ctypes.data, expected)
+            st = decode(blob.ctypes.data + off, cnt, out.ctypes.data, expected)
             assert st == 0
     t0 = time.perf_counter()
     with ThreadPoolExecutor(16) as ex:
@@ -126,6 +162,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--procs", type=int, default=15, help="processes that LZW-encode the probe's files")
     ap.add_argument("--cpu-only", action="store_true")
+    ap.add_argument("--only", default=None, help="comma-separated run keys (romio and rgb_lzw_planes_256 are the references)")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
 
@@ -141,17 +178,36 @@ def main():
     t0 = time.perf_counter()
     with multiprocessing.Pool(args.procs) as pool:               # before the GPU is opened
         mapper = lambda f, xs: pool.map(f, xs, chunksize=4)      # noqa: E731
-        for key, tile, comp in (("lzw_p2_256", 256, 5), ("lzw_p2_512", 512, 5), ("raw_256", 256, 1)):
+        rgb = np.ascontiguousarray((pixels[:, :3] >> 4).astype(np.uint8))
+        wanted = lambda key: args.only is None or key in args.only.split(",")  # noqa: E731
+        variants = [("lzw_p2_256", 256, 5, pixels, 1, None), ("lzw_p2_512", 512, 5, pixels, 1, None),
+                    ("raw_256", 256, 1, pixels, 1, None), ("deflate_p2_256", 256, 8, pixels, 1, None),
+                    ("zstd_p2_256", 256, 50000, pixels, 1, zstd_level3),
+                    ("rgb_lzw_planes_256", 256, 5, rgb, 1, None), ("rgb_deflate_256", 256, 8, rgb, 3, None)]
+        for key, tile, comp, px, spp, encoder in variants:
+            if not wanted(key):
+                continue
+            if comp == 50000 and libzstd() is None:
+                result["files"][key] = "not measured: no libzstd.so.1 to write the file with"
+                continue
             paths[key] = os.path.join(tmp, key + ".tif")
-            omr.write_tiled_tiff(paths[key], pixels, tile=(tile, tile), compression=comp, predictor=2 if comp == 5 else 1,
-                                 mapper=mapper)
+            omr.write_tiled_tiff(paths[key], px, tile=(tile, tile), compression=comp, predictor=1 if comp == 1 else 2,
+                                 mapper=mapper, samples_per_pixel=spp, encoder=encoder)
             size = os.path.getsize(paths[key])
-            result["files"][key] = {"tile": tile, "file_bytes": size, "compression_ratio": raw_bytes / size}
-    paths["romio"] = os.path.join(tmp, "romio.raw")
-    omr.write_romio(paths["romio"], pixels, _lib.PIXELS_UINT16)
+            result["files"][key] = {"tile": tile, "file_bytes": size, "compression_ratio": px.nbytes / size}
+    if wanted("romio"):
+        paths["romio"] = os.path.join(tmp, "romio.raw")
+        omr.write_romio(paths["romio"], pixels, _lib.PIXELS_UINT16)
     result["files_written_s"] = time.perf_counter() - t0
-    for key, tile in (("lzw_p2_256", 256), ("lzw_p2_512", 512)):
-        result["files"][key]["cpu"] = cpu_figures(paths[key], tile, CH, raw_bytes)
+    for key, expected, planes, nbytes, decoder in (
+            ("lzw_p2_256", 256 * 256 * 2, CH, raw_bytes, "omr_lzw_decode_host"),
+            ("lzw_p2_512", 512 * 512 * 2, CH, raw_bytes, "omr_lzw_decode_host"),
+            ("deflate_p2_256", 256 * 256 * 2, CH, raw_bytes, "omr_inflate_host"),
+            ("zstd_p2_256", 256 * 256 * 2, CH, raw_bytes, "omr_zstd_decode_host"),
+            ("rgb_lzw_planes_256", 256 * 256, 3, rgb.nbytes, "omr_lzw_decode_host"),
+            ("rgb_deflate_256", 256 * 256 * 3, 1, rgb.nbytes, "omr_inflate_host")):
+        if key in paths:
+            result["files"][key]["cpu"] = cpu_figures(paths[key], expected, planes, nbytes, decoder)
     print(json.dumps(result["files"], indent=1), flush=True)
 
     if not args.cpu_only:
@@ -160,18 +216,30 @@ def main():
         from omr.synthetic import c2_channels
         q, chans = make_qdef("rgb"), c2_channels(CH)
         binds = make_bindings(chans)
+        rgb_chans = [dict(c, rgba=col, input_start=0.0, input_end=255.0, global_min=0.0, global_max=255.0)
+                     for c, col in zip(c2_channels(3), ((255, 0, 0, 255), (0, 255, 0, 255), (0, 0, 255, 255)))]
+        rgb_binds = make_bindings(rgb_chans)
         positions = [(0, 0, k * SIDE, r * SIDE) for r in range(args.rows) for k in range(args.cols)]
         reqs = [positions[i % len(positions)] for i in range(args.requests)]
-        region_bytes = args.requests * CH * SIDE * SIDE * 2
         out = torch.empty((args.requests, SIDE, SIDE), dtype=torch.int32, device="cuda:0")
-        ref = None
+        ref = rgb_ref = None
+        accepts = {"deflate_p2_256": ("deflate",), "zstd_p2_256": ("zstd",), "rgb_deflate_256": ("deflate", "samples")}
         with omr.Context(0) as ctx:
-            for key in ("romio", "lzw_p2_256", "lzw_p2_512", "raw_256"):
+            for key in ("romio", "lzw_p2_256", "lzw_p2_512", "raw_256", "deflate_p2_256", "zstd_p2_256",
+                        "rgb_lzw_planes_256", "rgb_deflate_256"):
+                if key not in paths:
+                    continue
+                is_rgb = key.startswith("rgb_")
+                n_req = len(positions) if is_rgb else args.requests
+                region_bytes = n_req * (3 * SIDE * SIDE if is_rgb else CH * SIDE * SIDE * 2)
                 if key == "romio":
                     src = omr.PixelBuffer(paths[key], W, H, 1, CH, 1, _lib.PIXELS_UINT16)
                     call = lambda: ctx.render_pixel_buffer_tiles(q, chans, src, reqs, SIDE, SIDE, out=out, bindings=binds)  # noqa: E731
+                elif is_rgb:
+                    src = omr.TiffImage(paths[key], 1, 3, 1, accept=accepts.get(key, ()))
+                    call = lambda: src.render_tiles(ctx, q, rgb_chans, 0, positions, SIDE, SIDE, out=out, bindings=rgb_binds)  # noqa: E731
                 else:
-                    src = omr.TiffImage(paths[key], 1, CH, 1)
+                    src = omr.TiffImage(paths[key], 1, CH, 1, accept=accepts.get(key, ()))
                     call = lambda: src.render_tiles(ctx, q, chans, 0, reqs, SIDE, SIDE, out=out, bindings=binds)  # noqa: E731
                 walls, kinds = [], {}
                 ctx.enable_kernel_timing(True)
@@ -190,12 +258,19 @@ def main():
                             kinds.setdefault(("pass", kind), []).append(ms)
                 ctx.enable_kernel_timing(False)
                 got = out[:32].cpu().numpy()
-                if ref is None:
-                    ref = got
-                run = {"wall_s": series(walls), "requests_per_s": args.requests / statistics.median(walls),
-                       "region_gb_per_s_wall": region_bytes / statistics.median(walls) / 1e9,
-                       "equals_romio": bool(np.array_equal(got, ref))}
-                for name, kind in (("k13a_lzw_decode", 30), ("k13b_place", 31), ("k2_render", 2)):
+                if is_rgb:
+                    if rgb_ref is None:
+                        rgb_ref = got
+                    same = {"equals_rgb_lzw_planes": bool(np.array_equal(got, rgb_ref))}
+                else:
+                    if ref is None:
+                        ref = got
+                    same = {"equals_romio": bool(np.array_equal(got, ref))}
+                run = {"requests": n_req, "wall_s": series(walls), "requests_per_s": n_req / statistics.median(walls),
+                       "region_gb_per_s_wall": region_bytes / statistics.median(walls) / 1e9}
+                run.update(same)
+                for name, kind in (("k13a_lzw_decode", 30), ("k14a_inflate", 32), ("k16a_zstd_decode", 35),
+                                   ("k13b_place", 31), ("k2_render", 2)):
                     v = kinds.get(("pass", kind))
                     if v:
                         run[name + "_ms_per_pass"] = series(v)
@@ -203,9 +278,11 @@ def main():
                 result["runs"][key] = run
                 src.close()
                 print(key, json.dumps(run), flush=True)
-        base = result["runs"]["romio"]["requests_per_s"]
-        for key in ("lzw_p2_256", "lzw_p2_512", "raw_256"):
-            result["runs"][key]["requests_per_s_vs_romio"] = result["runs"][key]["requests_per_s"] / base
+        if "romio" in result["runs"]:
+            base = result["runs"]["romio"]["requests_per_s"]
+            for key in ("lzw_p2_256", "lzw_p2_512", "raw_256", "deflate_p2_256", "zstd_p2_256"):
+                if key in result["runs"]:
+                    result["runs"][key]["requests_per_s_vs_romio"] = result["runs"][key]["requests_per_s"] / base
     for p in paths.values():
         os.unlink(p)
     os.rmdir(tmp)
