@@ -129,7 +129,9 @@ void*       omr_ctx_get_stream(omr_ctx* ctx);
  * omr_zarr_image_read_regions_device; 33 = LZ4 decode: omr_lz4_decode_batch_device and, with 34 =
  * Blosc place, omr_zarr_image_read_regions_device on a Blosc image; 35 = Zstandard decode:
  * omr_zstd_decode_batch_device and, with 34 or 31, omr_zarr_image_read_regions_device on a
- * Blosc-Zstd or zstd image).
+ * Blosc-Zstd or zstd image; 36 = JPEG entropy decode, 37 = JPEG IDCT and 38 = JPEG upsample /
+ * colour / store: omr_jpeg_decode_batch_device and, in front of 31,
+ * omr_tiff_image_read_regions_device on a JPEG image).
  */
 omr_status  omr_ctx_enable_kernel_timing(omr_ctx* ctx, int32_t enable);
 int32_t     omr_ctx_kernel_timings(omr_ctx* ctx, float* ms_out, int32_t* kind_out, int32_t cap);
@@ -1067,7 +1069,7 @@ omr_status omr_tiff_image_open(const char* path, int32_t size_z, int32_t size_c,
  * ExtraSamples are ordinary channels.  All samples of a pixel have the same BitsPerSample and
  * SampleFormat; Predictor 2 runs per component, spp samples apart.  A read returns the one
  * requested sample; on the device two channels of one pixel share the segment, which is read and
- * decoded once per group.  Refused: Photometric 6 (YCbCr), PlanarConfiguration 2, more than 4
+ * decoded once per group.  Refused: Photometric 6 (YCbCr, but for JPEG segments: OMR_TIFF_ACCEPT_JPEG), PlanarConfiguration 2, more than 4
  * samples, Predictor 3.  The segment limit of 256 MiB decoded counts all samples.  8-bit RGB is
  * pinned against libtiff; 16-bit, 4 samples and big-endian rest on the project's own writer.
  */
@@ -1349,6 +1351,85 @@ omr_status omr_blosc_decode_host_ex(const uint8_t* src, size_t length, uint8_t* 
 omr_status omr_zstd_decode_batch_device(omr_ctx* ctx, const uint8_t* d_src, const uint64_t* d_offsets,
                                         const uint32_t* d_lengths, const uint32_t* d_expected, int32_t n,
                                         uint8_t* d_dst, const uint64_t* d_dst_offsets, int32_t* d_status);
+
+/* ---- K17: JPEG-compressed TIFF segments (Compression 7) ---------------------------------------
+ *
+ * OMR_TIFF_ACCEPT_JPEG in omr_tiff_image_open_ex admits Compression 7 ("new-style" JPEG: every
+ * segment one interchange or abbreviated stream, the shared tables in tag 347, JPEGTables, read at
+ * open and bounded to 64 KiB); omr_tiff_image_open and Compression 6 keep refusing.  Accepted:
+ * BitsPerSample 8, SampleFormat 1, Predictor 1, tiles or strips, and SamplesPerPixel 1 with
+ * Photometric 0 or 1, or SamplesPerPixel 3 (which needs OMR_TIFF_ACCEPT_SAMPLES as well) with
+ * Photometric 2 (the components are R, G, B) or 6 (YCbCr -> RGB on decode, as libtiff's
+ * JPEGCOLORMODE_RGB).  The frame header, not the YCbCrSubSampling tag, decides the sampling.
+ * The image then behaves as a chunky 8-bit one: get_tile, read_regions_device and
+ * omr_render_tiff_tiles return the one sample of channel c, and a segment is decoded once per call.
+ *
+ * The decoder: baseline sequential DCT (SOF0), 8 bits, Huffman, all components in one interleaved
+ * scan, luma sampled 1x1, 2x1 or 2x2 over 1x1 chroma; DQT with 8-bit entries, up to 4 + 4 + 4
+ * tables, several per marker segment; a segment's own DQT / DHT override tag 347's for that segment;
+ * DRI with RST0..7 in order; APPn and COM skipped (JFIF and Adobe markers do not matter: the
+ * TIFF's Photometric decides the colour); fill FF bytes before a marker.  Arithmetic as
+ * libjpeg(-turbo)'s defaults, byte for byte: the islow IDCT, the "fancy" triangle upsampling (plain
+ * replication where the chroma is at most two samples wide), jdcolor's 16-bit YCbCr conversion
+ * (tests/golden/tiff_jpeg.npz pins them against libtiff and libjpeg-turbo).
+ * OMR_INVALID_ARGUMENT, the reason naming the form: SOF1/2/3/5+ (extended, progressive, lossless,
+ * hierarchical, arithmetic), 12-bit samples, 16-bit quantisation entries, DNL, more than one scan,
+ * four components, any other sampling.  OMR_INTERNAL (damage; stricter than libjpeg, which pads
+ * with zeros and warns): a stream cut short, bits missing at the end of a restart interval, a code
+ * that is not in the table, a coefficient index past 63, a DC category above 11, an AC category
+ * above 10, a DC value outside [-2048, 2047], a missing, surplus or out-of-order RST, no EOI,
+ * frame dimensions other than the segment's (the rows of a last strip), a table referenced but
+ * never defined.
+ */
+#define OMR_TIFF_ACCEPT_JPEG 16u   /* Compression 7: one baseline JPEG stream per segment */
+/*
+ * The host decoder alone (get_tile's): tables (NULL or a JPEGTables stream: SOI, DQT / DHT, EOI)
+ * and one segment's stream, whose frame must be width x height with `samples` (1 or 3) components;
+ * chunky width * height * samples bytes to dst (at most 256 MiB), with ycbcr != 0 converted to RGB.
+ * why (optional, why_cap bytes): the reason of a failure as text.
+ */
+omr_status omr_jpeg_decode_host(const uint8_t* tables, size_t tables_length, const uint8_t* src, size_t length,
+                                int32_t width, int32_t height, int32_t samples, int32_t ycbcr, uint8_t* dst,
+                                char* why, size_t why_cap);
+/*
+ * Decodes a good stream's entropy-coded data (its size and component count from its own frame
+ * header) and sets bit f of *forms for every form met.  The tests use it to prove that their
+ * fixture reaches every branch.
+ */
+enum {
+    OMR_JPEG_FORM_EOB_EARLY = 0,   /* EOB before coefficient 63 */
+    OMR_JPEG_FORM_FULL_BLOCK,      /* a block that reaches coefficient 63 */
+    OMR_JPEG_FORM_ZRL,
+    OMR_JPEG_FORM_LONG_CODE,       /* a code of 12 bits or more */
+    OMR_JPEG_FORM_DC_CAT9,         /* a DC category >= 9 */
+    OMR_JPEG_FORM_STUFFED_FF,      /* FF 00 */
+    OMR_JPEG_FORM_RESTART,         /* a restart marker */
+    OMR_JPEG_FORM_PAD_BITS,        /* pad bits before a marker */
+    OMR_JPEG_FORM_TABLE_OVERRIDE,  /* a table of the segment that overrides one of JPEGTables */
+    OMR_JPEG_FORM_MULTI_TABLE,     /* several tables in one DQT or DHT */
+    OMR_JPEG_FORM_COM,
+    OMR_JPEG_FORM_FILL_BYTES,      /* FF fill bytes before a marker */
+    OMR_JPEG_FORM_TABLES_STREAM,   /* decoded with a JPEGTables stream */
+    OMR_JPEG_FORM_COUNT
+};
+omr_status omr_jpeg_stream_forms(const uint8_t* tables, size_t tables_length, const uint8_t* src, size_t length,
+                                 uint32_t* forms);
+/*
+ * K17 alone: n streams in HOST memory (the headers are parsed and the restart intervals listed on
+ * the host, as in omr_tiff_image_read_regions_device), stream i = lengths[i] bytes at src +
+ * offsets[i] with a frame of widths[i] x heights[i] and `samples` components, all sharing `tables`
+ * (may be NULL), decoded on the device into d_dst + dst_offsets[i] as chunky widths[i] * heights[i] *
+ * samples bytes (nothing is written behind them).  offsets, lengths, widths, heights, dst_offsets
+ * and status are host arrays; status[i] = OMR_OK, OMR_INVALID_ARGUMENT or OMR_INTERNAL by the rule of
+ * omr_jpeg_decode_host, one stream's failure leaving the others alone.  Synchronous.
+ * omr_ctx_kernel_timings reports kinds 36 (K17a, entropy decode), 37 (K17b, IDCT) and 38 (K17c,
+ * upsample, colour and store); omr_tiff_image_read_regions_device on a JPEG image reports them in
+ * front of 31.
+ */
+omr_status omr_jpeg_decode_batch_device(omr_ctx* ctx, const uint8_t* tables, size_t tables_length, const uint8_t* src,
+                                        const uint64_t* offsets, const uint32_t* lengths, const int32_t* widths,
+                                        const int32_t* heights, int32_t n, int32_t samples, int32_t ycbcr,
+                                        uint8_t* d_dst, const uint64_t* dst_offsets, int32_t* status);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,404 @@
+// omr_jpegdec.hip — K17, device half: baseline JPEG segments decoded on the GPU.
+//
+// The host (jpeg_prepare, omr_jpegdec.cpp) has parsed every segment's header, built its lookup
+// tables and listed its restart intervals; jpeg_decode_group here puts that into one descriptor
+// table, and three kernels do the rest:
+//
+//   K17a  k_jpeg_entropy  one wave (a workgroup of 64 threads) per restart interval.  The symbol
+//         chain is serial, so the decode runs wave-uniform (every value that steers it goes through
+//         readfirstlane); the lanes load the Huffman tables into LDS, refill the bit window -- 64 raw
+//         bytes per load, the stuffed 00 behind an FF dropped by a ballot / prefix-count compaction
+//         into a 256-byte LDS ring -- and each keeps one coefficient of the current block in a
+//         register: lane n holds natural index n, which zeroes the block, places a decoded value
+//         (the lane whose own zigzag position is the decoded one takes it) and stores the finished block
+//         as one 128-byte row of int16.  The coefficients are stored quantised: times a table entry
+//         of up to 255 they would not fit 16 bits; K17b multiplies.
+//   K17b  k_jpeg_idct     one lane per 8 x 8 block: dequantise, islow IDCT, 8 stores of 8 bytes
+//         into the component's plane.
+//   K17c  k_jpeg_pixels   one lane per output pixel: the planes' samples, the chroma upsampled by
+//         libjpeg's triangle filter, YCbCr -> RGB, and the chunky store.
+//
+// Bounds.  K17a reads src only inside [iv.src_off, iv.src_off + iv.len), which the host laid inside
+// the segment's uploaded bytes (ring_fill compares every byte's position with len; the byte before
+// position p is read only for p > 0).  The ring holds at most 3 + 64 unread bytes of its 256.  A
+// Huffman lookup reads lut[peek >> 7] (9 bits), maxcode[10..16] and vals[idx] with idx checked
+// against [0, 255]: all inside the table's LDS copy whatever the table holds.  The block index is
+// computed from the MCU number, which runs over [first_mcu, first_mcu + n_mcu), inside the
+// segment's mcux * mcuy by jpeg_prepare: a block of another interval, let alone another segment, is
+// never written, however the entropy-coded bytes are damaged -- they steer only which value lands
+// at which of the block's own 64 places (the zigzag index is checked against 63 before it is used)
+// and when the interval gives up.  A damaged interval writes OMR_INTERNAL to its segment's status
+// and stops.  K17b and K17c take every size from the host's descriptors and none from the stream:
+// block t < jpeg_total_blocks reads its own 64 coefficients and writes its own 8 x 8 samples of a
+// plane that is whole blocks wide and tall; pixel p < w * h reads plane samples at (x, y), x < w <=
+// 8 * mcux * hs, and chroma samples up to column ceil(w / 2) - 1 and row ceil(h / 2) - 1, and writes
+// ncomp bytes at dst_off + p * ncomp, inside the w * h * ncomp bytes the segment owns.  After a
+// damaged interval they run over coefficients that were never written: any bytes give defined
+// arithmetic (omr_jpegdec.h) and the call fails on the status.
+#include "omr_jpegdec.h"
+#include "omr_segread.h"
+#include "omr_wave.h"
+
+namespace omr {
+namespace {
+
+constexpr int kKindJpegEntropy = 36;   // omr_ctx_kernel_timings kinds (omr.h)
+constexpr int kKindJpegIdct = 37;
+constexpr int kKindJpegPixels = 38;
+
+__device__ const uint8_t d_zigzag[64] = OMR_JPEG_ZIGZAG;   // zigzag position -> natural index
+
+struct DBits {               // all members wave-uniform
+    const uint8_t* src;      // the interval
+    uint32_t len;
+    uint32_t raw;            // next raw byte
+    uint32_t wr, rd;         // bytes put into and taken out of the ring (rd in steps of 4)
+    uint64_t acc;
+    int nbits, fake;
+};
+
+// 64 raw bytes, FF 00 -> FF, behind the ring's last byte.
+__device__ __forceinline__ void ring_fill(DBits& B, uint32_t* ring, int lane) {
+    const uint32_t p = B.raw + (uint32_t)lane;
+    const bool in = p < B.len;
+    const uint32_t b = in ? B.src[p] : 0u;
+    const uint32_t prev = (in && p > 0u) ? B.src[p - 1u] : 0u;
+    const bool keep = in && !(b == 0u && prev == 0xFFu);
+    const uint64_t mask = __ballot(keep);
+    const uint32_t idx = (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
+    if (keep) reinterpret_cast<uint8_t*>(ring)[(B.wr + idx) & 255u] = (uint8_t)b;
+    B.wr += (uint32_t)__popcll(mask);
+    B.raw = min(B.len, B.raw + 64u);
+    __syncthreads();                                       // one wave: the ring's stores before its loads
+}
+
+// 32 more bits into the window (nbits <= 32); behind the interval's end zeros, counted in fake.
+__device__ __forceinline__ void refill(DBits& B, uint32_t* ring, int lane) {
+    int avail = (int)(B.wr - B.rd);
+    while (avail < 4 && B.raw < B.len) {
+        ring_fill(B, ring, lane);
+        avail = (int)(B.wr - B.rd);
+    }
+    uint32_t v = __builtin_bswap32(uni(ring[(B.rd & 255u) >> 2]));
+    if (avail < 4) {
+        const int a = max(avail, 0);
+        v = a ? v & (0xFFFFFFFFu << (8 * (4 - a))) : 0u;
+        B.fake += 8 * (4 - a);
+    }
+    B.acc |= (uint64_t)v << (32 - B.nbits);
+    B.nbits += 32;
+    B.rd += 4u;
+}
+
+__device__ __forceinline__ bool take(DBits& B, uint32_t* ring, int lane, int n, uint32_t& v) {   // n in [0, 16]
+    if (B.nbits <= 32) refill(B, ring, lane);
+    if (B.nbits - B.fake < n) return false;
+    v = n ? (uint32_t)(B.acc >> (64 - n)) : 0u;
+    B.acc = n ? B.acc << n : B.acc;
+    B.nbits -= n;
+    return true;
+}
+
+// One symbol of the table at H (LDS); -1: no such code, or the interval ends inside it.
+__device__ __forceinline__ int symbol(DBits& B, uint32_t* ring, int lane, const JpegHuff* H) {
+    if (B.nbits <= 32) refill(B, ring, lane);
+    const uint32_t peek = (uint32_t)(B.acc >> 48);
+    int len = 0, sym = 0;
+    const uint32_t e = uni(H->lut[peek >> 7]);
+    if (e) {
+        len = (int)(e >> 8);
+        sym = (int)(e & 255u);
+    } else {
+        for (int l = 10; l <= 16; ++l) {
+            const int32_t code = (int32_t)(peek >> (16 - l));
+            if (code <= (int32_t)uni((uint32_t)H->maxcode[l])) {
+                const int32_t idx = code + (int32_t)uni((uint32_t)H->valoff[l]);
+                if (idx < 0 || idx > 255) return -1;
+                len = l;
+                sym = (int)uni(H->vals[idx]);
+                break;
+            }
+        }
+        if (!len) return -1;
+    }
+    if (B.nbits - B.fake < len) return -1;
+    B.acc <<= len;
+    B.nbits -= len;
+    return sym;
+}
+
+__device__ __forceinline__ int32_t extend(uint32_t v, int s) {
+    return v < (1u << (s - 1)) ? (int32_t)v - (1 << s) + 1 : (int32_t)v;
+}
+
+// K17a.  The bounds argument is at the head of this file.
+__global__ void __launch_bounds__(64) k_jpeg_entropy(const uint8_t* __restrict__ src, const JpegSegDesc* __restrict__ segs,
+                                                     const JpegIvDesc* __restrict__ ivs,
+                                                     const JpegTables* __restrict__ tables, uint8_t* __restrict__ ws,
+                                                     int32_t* __restrict__ status) {
+    __shared__ uint32_t s_huff[3 * kJpegHuffBytes / 4];
+    __shared__ uint32_t s_ring[64];
+    const int lane = (int)threadIdx.x;
+    const JpegIvDesc iv = ivs[blockIdx.x];
+    const uint32_t seg = uni(iv.seg);
+    const JpegSegDesc S = segs[seg];
+    const int32_t ncomp = (int32_t)uni((uint32_t)S.ncomp), hs = (int32_t)uni((uint32_t)S.hs), vs = (int32_t)uni((uint32_t)S.vs);
+    const int32_t mcux = (int32_t)uni((uint32_t)S.mcux), mcuy = (int32_t)uni((uint32_t)S.mcuy);
+    {
+        const uint32_t* g = reinterpret_cast<const uint32_t*>(tables + uni((uint32_t)S.tables));
+        const int n = ncomp * (int)(kJpegHuffBytes / 4);
+        for (int i = lane; i < n; i += 64) s_huff[i] = g[i];
+    }
+    __syncthreads();
+    const JpegHuff* huff = reinterpret_cast<const JpegHuff*>(s_huff);
+    int myk = 0;                                           // the zigzag position of this lane's natural index: no load per coefficient
+    for (int k = 0; k < 64; ++k)
+        if ((int)d_zigzag[k] == lane) myk = k;
+    int16_t* coef = reinterpret_cast<int16_t*>(ws + S.coef_off);
+    DBits B;
+    B.src = src + iv.src_off;
+    B.len = uni(iv.len);
+    B.raw = B.wr = B.rd = 0u;
+    B.acc = 0;
+    B.nbits = B.fake = 0;
+    int32_t pred[3] = {0, 0, 0};
+    const uint32_t m0 = uni(iv.first_mcu), m1 = m0 + uni(iv.n_mcu);
+    bool good = true;
+    for (uint32_t m = m0; m < m1 && good; ++m) {
+        const int32_t mx = (int32_t)(m % (uint32_t)mcux), my = (int32_t)(m / (uint32_t)mcux);
+        for (int c = 0; c < ncomp && good; ++c) {
+            const int32_t H = c == 0 ? hs : 1, V = c == 0 ? vs : 1;
+            const int32_t base = jpeg_comp_base(c, hs, vs, mcux, mcuy), bw = mcux * H;
+            const JpegHuff* dc = huff + 2 * c;
+            const JpegHuff* ac = dc + 1;
+            for (int32_t by = 0; by < V && good; ++by)
+                for (int32_t bx = 0; bx < H && good; ++bx) {
+                    const int32_t block = base + (my * V + by) * bw + mx * H + bx;
+                    int s = symbol(B, s_ring, lane, dc);
+                    uint32_t v = 0;
+                    if (s < 0 || s > 11 || !take(B, s_ring, lane, s, v)) { good = false; break; }
+                    pred[c] += s ? extend(v, s) : 0;
+                    if (pred[c] < -2048 || pred[c] > 2047) { good = false; break; }
+                    int32_t mine = lane == 0 ? pred[c] : 0;      // this lane's coefficient: natural index `lane`
+                    int k = 1;
+                    while (k < 64) {
+                        const int rs = symbol(B, s_ring, lane, ac);
+                        if (rs < 0) { good = false; break; }
+                        const int r = rs >> 4;
+                        s = rs & 15;
+                        if (s == 0) {
+                            if (r != 15) break;
+                            k += 16;
+                            if (k > 63) { good = false; break; }
+                            continue;
+                        }
+                        k += r;
+                        if (k > 63 || s > 10 || !take(B, s_ring, lane, s, v)) { good = false; break; }
+                        if (myk == k) mine = extend(v, s);
+                        ++k;
+                    }
+                    if (!good) break;
+                    coef[(size_t)64 * (size_t)block + (size_t)lane] = (int16_t)mine;
+                }
+        }
+    }
+    if (!good && lane == 0) status[seg] = OMR_INTERNAL;
+}
+
+// K17b: block t of segment blockIdx.y (+ k * gridDim.y).
+__global__ void __launch_bounds__(64) k_jpeg_idct(const JpegSegDesc* __restrict__ segs, int32_t n_seg,
+                                                  const JpegTables* __restrict__ tables, uint8_t* __restrict__ ws) {
+    const int32_t t = (int32_t)(blockIdx.x * 64u + threadIdx.x);
+    for (int32_t seg = (int32_t)blockIdx.y; seg < n_seg; seg += (int32_t)gridDim.y) {
+        const JpegSegDesc S = segs[seg];
+        const int32_t hs = S.ncomp == 1 ? 1 : S.hs, vs = S.ncomp == 1 ? 1 : S.vs;
+        if (t >= jpeg_total_blocks(S.ncomp, hs, vs, S.mcux, S.mcuy)) continue;
+        const int32_t base1 = jpeg_comp_base(1, hs, vs, S.mcux, S.mcuy);
+        const int32_t c = t < base1 ? 0 : 1 + (t - base1) / (S.mcux * S.mcuy);
+        const int32_t base = jpeg_comp_base(c, hs, vs, S.mcux, S.mcuy), bw = S.mcux * (c == 0 ? hs : 1), b = t - base;
+        const size_t pitch = (size_t)8 * bw;
+        jpeg_idct_block(reinterpret_cast<const int16_t*>(ws + S.coef_off) + (size_t)64 * t, tables[S.tables].q[c],
+                        ws + S.plane_off + (size_t)64 * base + (size_t)(b / bw) * 8 * pitch + (size_t)(b % bw) * 8, pitch);
+    }
+}
+
+// K17c: pixel p of segment blockIdx.y (+ k * gridDim.y).
+__global__ void __launch_bounds__(256) k_jpeg_pixels(const JpegSegDesc* __restrict__ segs, int32_t n_seg,
+                                                     const uint8_t* __restrict__ ws, uint8_t* __restrict__ dst) {
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    for (int32_t seg = (int32_t)blockIdx.y; seg < n_seg; seg += (int32_t)gridDim.y) {
+        JpegSegDesc S = segs[seg];
+        if (p >= (int64_t)S.w * S.h) continue;
+        if (S.ncomp == 1) S.hs = S.vs = 1;
+        uint8_t o[3];
+        jpeg_pixel(S, ws + S.plane_off, (int32_t)(p % S.w), (int32_t)(p / S.w), o);
+        uint8_t* d = dst + S.dst_off + (uint64_t)p * (uint64_t)S.ncomp;
+        d[0] = o[0];
+        if (S.ncomp == 3) {
+            d[1] = o[1];
+            d[2] = o[2];
+        }
+    }
+}
+
+}  // namespace
+
+omr_status launch_jpeg_decode(Ctx* ctx, const uint8_t* src, const JpegSegDesc* segs, int32_t n_seg, const JpegIvDesc* ivs,
+                              int32_t n_iv, const JpegTables* tables, uint8_t* ws, uint8_t* dst, int32_t* status,
+                              int32_t max_blocks, int64_t max_pixels) {
+    if (n_seg <= 0) return OMR_OK;
+    const unsigned gy = (unsigned)std::min(n_seg, 65535);
+    if (n_iv > 0) {
+        KernelTimer timer(ctx, kKindJpegEntropy, true);
+        omr_launch(k_jpeg_entropy, dim3((unsigned)n_iv), dim3(64), 0u, ctx->stream, src, segs, ivs, tables, ws, status);
+        OMR_HIP(ctx, hipGetLastError());
+    }
+    {
+        KernelTimer timer(ctx, kKindJpegIdct, true);
+        omr_launch(k_jpeg_idct, dim3((unsigned)((max_blocks + 63) / 64), gy), dim3(64), 0u, ctx->stream, segs, n_seg, tables, ws);
+        OMR_HIP(ctx, hipGetLastError());
+    }
+    {
+        KernelTimer timer(ctx, kKindJpegPixels, true);
+        omr_launch(k_jpeg_pixels, dim3((unsigned)((max_pixels + 255) / 256), gy), dim3(256), 0u, ctx->stream, segs, n_seg,
+                   static_cast<const uint8_t*>(ws), dst);
+        OMR_HIP(ctx, hipGetLastError());
+    }
+    return OMR_OK;
+}
+
+// The descriptor table of one group: [JpegSegDesc m][JpegIvDesc k][JpegTables s] | [status i32 m]:
+// everything goes up in one copy (the statuses as OMR_OK), the statuses come back.
+omr_status jpeg_decode_group(Ctx* ctx, SegPipe* T, const std::vector<JpegJob>& jobs, const std::vector<JpegPlan>& plans,
+                             int32_t samples, bool ycc, const uint8_t* d_src, uint8_t* d_dst, std::vector<int32_t>& status) {
+    const size_t n = jobs.size();
+    status.assign(n, OMR_OK);
+    std::vector<int32_t> live;                             // the jobs that decode: parsed, and not empty
+    size_t n_iv = 0;
+    for (size_t k = 0; k < n; ++k)
+        if (jobs[k].parsed == OMR_OK) {
+            live.push_back((int32_t)k);
+            n_iv += plans[k].intervals.size();
+        } else {
+            status[k] = jobs[k].parsed;
+        }
+    const size_t m = live.size();
+    if (!m) return OMR_OK;
+    if (n_iv > 0x7FFFFFFFull) return fail(ctx, OMR_INVALID_ARGUMENT, "jpeg: too many restart intervals in one group");
+    std::vector<int32_t> table_of(m);
+    std::vector<int32_t> sets;                             // live indices whose table set is the first of its kind
+    for (size_t j = 0; j < m; ++j) {
+        const JpegTables& mine = plans[(size_t)live[j]].tables;
+        int32_t found = -1;
+        for (size_t s = 0; s < sets.size() && found < 0; ++s)
+            if (!std::memcmp(&plans[(size_t)live[(size_t)sets[s]]].tables, &mine, sizeof(JpegTables))) found = (int32_t)s;
+        if (found < 0) {
+            found = (int32_t)sets.size();
+            sets.push_back((int32_t)j);
+        }
+        table_of[j] = found;
+    }
+    const size_t o_iv = m * sizeof(JpegSegDesc), o_tab = o_iv + n_iv * sizeof(JpegIvDesc);
+    const size_t o_status = o_tab + sets.size() * sizeof(JpegTables), total = o_status + 4 * m;
+    omr_status st = grow_pinned(ctx, T->pin_tab, T->d_tab, T->tab_cap, total, "jpeg tables");
+    if (st) return st;
+    uint8_t* tab = static_cast<uint8_t*>(T->pin_tab);
+    uint8_t* dtab = static_cast<uint8_t*>(T->d_tab);
+    JpegSegDesc* hs = reinterpret_cast<JpegSegDesc*>(tab);
+    JpegIvDesc* hi = reinterpret_cast<JpegIvDesc*>(tab + o_iv);
+    size_t ws_bytes = 0, iv_at = 0;
+    int32_t max_blocks = 0;
+    int64_t max_pixels = 0;
+    for (size_t j = 0; j < m; ++j) {
+        const JpegJob& J = jobs[(size_t)live[j]];
+        const JpegPlan& P = plans[(size_t)live[j]];
+        JpegSegDesc& S = hs[j];
+        S.dst_off = J.dst_off;
+        S.coef_off = ws_bytes;
+        ws_bytes += jpeg_coef_bytes(P);
+        S.plane_off = ws_bytes;
+        ws_bytes += jpeg_plane_bytes(P);
+        S.w = P.w; S.h = P.h; S.ncomp = P.ncomp; S.hs = P.hs; S.vs = P.vs; S.ycc = ycc && samples == 3;
+        S.mcux = P.mcux; S.mcuy = P.mcuy;
+        S.tables = table_of[j];
+        S.pad = 0;
+        max_blocks = std::max(max_blocks, jpeg_total_blocks(P.ncomp, P.hs, P.vs, P.mcux, P.mcuy));
+        max_pixels = std::max(max_pixels, (int64_t)P.w * P.h);
+        for (const JpegInterval& iv : P.intervals)
+            hi[iv_at++] = {J.in_off + iv.off, (uint32_t)iv.len, (uint32_t)j, iv.first_mcu, iv.n_mcu};
+    }
+    for (size_t s = 0; s < sets.size(); ++s)
+        std::memcpy(tab + o_tab + s * sizeof(JpegTables), &plans[(size_t)live[(size_t)sets[s]]].tables, sizeof(JpegTables));
+    std::memset(tab + o_status, 0, 4 * m);                 // OMR_OK
+    st = grow_device(ctx, T->d_coef, T->coef_cap, ws_bytes);
+    if (st) return st;
+    OMR_HIP(ctx, hipMemcpyAsync(dtab, tab, total, hipMemcpyHostToDevice, ctx->stream));
+    st = launch_jpeg_decode(ctx, d_src, reinterpret_cast<const JpegSegDesc*>(dtab), (int32_t)m,
+                            reinterpret_cast<const JpegIvDesc*>(dtab + o_iv), (int32_t)n_iv,
+                            reinterpret_cast<const JpegTables*>(dtab + o_tab), static_cast<uint8_t*>(T->d_coef), d_dst,
+                            reinterpret_cast<int32_t*>(dtab + o_status), max_blocks, max_pixels);
+    if (st) return st;
+    T->jpeg_status_off = o_status;
+    T->jpeg_live = live;
+    return OMR_OK;
+}
+
+omr_status jpeg_group_statuses(Ctx* ctx, SegPipe* T, std::vector<int32_t>& status) {
+    const size_t m = T->jpeg_live.size();
+    uint8_t* tab = static_cast<uint8_t*>(T->pin_tab);
+    if (m) OMR_HIP(ctx, hipMemcpyAsync(tab + T->jpeg_status_off, static_cast<uint8_t*>(T->d_tab) + T->jpeg_status_off, 4 * m,
+                                       hipMemcpyDeviceToHost, ctx->stream));
+    OMR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const int32_t* h = reinterpret_cast<const int32_t*>(tab + T->jpeg_status_off);
+    for (size_t j = 0; j < m; ++j) status[(size_t)T->jpeg_live[j]] = h[j];
+    T->jpeg_live.clear();
+    return OMR_OK;
+}
+
+}  // namespace omr
+
+using namespace omr;
+
+extern "C" omr_status omr_jpeg_decode_batch_device(omr_ctx* ctx, const uint8_t* tables, size_t tables_length,
+                                                   const uint8_t* src, const uint64_t* offsets, const uint32_t* lengths,
+                                                   const int32_t* widths, const int32_t* heights, int32_t n, int32_t samples,
+                                                   int32_t ycbcr, uint8_t* d_dst, const uint64_t* dst_offsets,
+                                                   int32_t* status) {
+    if (!ctx) return OMR_INVALID_ARGUMENT;
+    if (n < 0) return fail(ctx, OMR_INVALID_ARGUMENT, "jpeg: negative stream count");
+    if (n == 0) return OMR_OK;
+    if (!src || !offsets || !lengths || !widths || !heights || !d_dst || !dst_offsets || !status || (!tables && tables_length))
+        return fail(ctx, OMR_INVALID_ARGUMENT, "jpeg: null argument");
+    if (samples != 1 && samples != 3) return fail(ctx, OMR_INVALID_ARGUMENT, "jpeg: samples must be 1 or 3");
+    OMR_HIP(ctx, hipSetDevice(ctx->device));
+    SegPipe* T = seg_pipe(ctx, SegKind::tiff);
+    std::vector<JpegJob> jobs((size_t)n);
+    std::vector<JpegPlan> plans((size_t)n);
+    size_t in_bytes = 0;
+    for (int32_t k = 0; k < n; ++k) {
+        JpegJob& J = jobs[(size_t)k];
+        J.dst_off = dst_offsets[k];
+        J.in_off = in_bytes;
+        if (widths[k] < 1 || heights[k] < 1 || widths[k] > 65535 || heights[k] > 65535 ||
+            (uint64_t)widths[k] * (uint64_t)heights[k] * (uint64_t)samples > ((uint64_t)256 << 20)) {
+            J.parsed = OMR_INVALID_ARGUMENT;
+            continue;
+        }
+        J.parsed = jpeg_prepare(tables, tables_length, src + offsets[k], lengths[k], widths[k], heights[k], samples,
+                                plans[(size_t)k], nullptr);
+        if (J.parsed == OMR_OK) in_bytes += align_up((size_t)lengths[k], 16);
+    }
+    omr_status st = grow_pinned(ctx, T->pin, T->d_in, T->in_cap, std::max<size_t>(in_bytes, 16), "jpeg staging");
+    if (st) return st;
+    uint8_t* pin = static_cast<uint8_t*>(T->pin);
+    for (int32_t k = 0; k < n; ++k)
+        if (jobs[(size_t)k].parsed == OMR_OK) std::memcpy(pin + jobs[(size_t)k].in_off, src + offsets[k], lengths[k]);
+    if (in_bytes) OMR_HIP(ctx, hipMemcpyAsync(T->d_in, pin, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    std::vector<int32_t> stv;
+    st = jpeg_decode_group(ctx, T, jobs, plans, samples, ycbcr != 0, static_cast<const uint8_t*>(T->d_in), d_dst, stv);
+    if (st) return st;
+    st = jpeg_group_statuses(ctx, T, stv);
+    if (st) return st;
+    for (int32_t k = 0; k < n; ++k) status[k] = stv[(size_t)k];
+    return OMR_OK;
+}

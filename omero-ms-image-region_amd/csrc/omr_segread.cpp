@@ -1,22 +1,21 @@
 // omr_segread.cpp — the device route of the TIFF and the Zarr reader (omr_segread.h): the staging
 // of a context and its growth, one group of regions from plan to status scan (the run stage with
 // the decoder of the source's codec: K13a, K14a or K16a, then K13b; Blosc chunks through their own
-// finish: container parsing, K15a and K16a side by side, K15b), the group loop and the tile
-// renderer.  Every HIP call of the two readers is in this file.
+// finish: container parsing, K15a and K16a side by side, K15b; JPEG segments through theirs: header
+// parsing, K17a .. K17c, K13b), the group loop and the tile renderer.  Every HIP call of the two
+// readers is in this file, but for the JPEG group's table upload and launches (omr_jpegdec.hip).
 #include "omr_segread.h"
+
+#include "omr_jpegdec.h"
 
 namespace omr {
 
 SegPipe::~SegPipe() {
     if (pin) (void)hipHostFree(pin);
     if (pin_tab) (void)hipHostFree(pin_tab);
-    for (void* p : {d_in, d_scratch, d_regions, d_out, d_tab, d_lit})
+    for (void* p : {d_in, d_scratch, d_regions, d_out, d_tab, d_lit, d_coef})
         if (p) (void)hipFree(p);
 }
-
-namespace {
-
-void free_seg_pipe(void* p) { delete static_cast<SegPipe*>(p); }
 
 omr_status grow_device(Ctx* c, void*& p, size_t& cap, size_t bytes) {
     if (bytes <= cap) return OMR_OK;
@@ -28,8 +27,6 @@ omr_status grow_device(Ctx* c, void*& p, size_t& cap, size_t bytes) {
     return OMR_OK;
 }
 
-// A pinned buffer and its device twin of at least `total` bytes (by half again when they grow);
-// what: "<tag> staging" | "<tag> tables", for the message.
 omr_status grow_pinned(Ctx* c, void*& pin, void*& dev, size_t& cap, size_t total, const std::string& what) {
     if (total <= cap) return OMR_OK;
     if (pin) OMR_HIP(c, hipHostFree(pin));
@@ -45,6 +42,10 @@ omr_status grow_pinned(Ctx* c, void*& pin, void*& dev, size_t& cap, size_t total
     }
     return OMR_OK;
 }
+
+namespace {
+
+void free_seg_pipe(void* p) { delete static_cast<SegPipe*>(p); }
 
 std::string said(const SegSource& S, const char* what) { return std::string(S.tag) + ": " + what; }
 
@@ -119,6 +120,58 @@ omr_status finish_blosc(Ctx* ctx, SegPipe* T, const SegSource& S, const SegPlan&
     return scan_statuses(ctx, S, t, tab, dtab, "blosc");
 }
 
+// The JPEG half of read_group, from the segments' bytes in pinned memory on (K17).  While they are
+// there the host parses every segment's header up to SOS, merges it with its IFD's JPEGTables,
+// builds the lookup tables and lists the restart intervals (jpeg_prepare; a segment it refuses ends
+// the call before any launch).  The bytes and the placements go up in the staging copy, the
+// descriptors (identical table sets once) behind them in a copy of their own; K17a .. K17c decode
+// into the segments' scratch as chunky bytes and K13b places them as it places a chunky Deflate segment.
+omr_status finish_jpeg(Ctx* ctx, SegPipe* T, SegSource& S, SegPlan& plan, const std::vector<SegBytes>& segs, size_t in_bytes) {
+    uint8_t* pin = static_cast<uint8_t*>(T->pin);
+    uint8_t* din = static_cast<uint8_t*>(T->d_in);
+    uint8_t* dscr = static_cast<uint8_t*>(T->d_scratch);
+    std::vector<int32_t> coded;
+    for (size_t k = 0; k < segs.size(); ++k)
+        if (segs[k].cnt) coded.push_back((int32_t)k);
+    const size_t m = coded.size();
+    std::vector<JpegJob> jobs(m);
+    std::vector<JpegPlan> plans(m);
+    std::vector<std::string> why(m);
+    const int32_t spp = S.geom.spp;
+    parallel_for((int)m, in_bytes > ((size_t)1 << 20), [&](int j) {
+        const SegBytes& u = segs[(size_t)coded[(size_t)j]];
+        size_t tl = 0;
+        const uint8_t* tb = S.jpeg_tables(plan.segs[(size_t)coded[(size_t)j]], &tl);
+        const int32_t rows = (int32_t)(u.expected / ((uint32_t)S.geom.seg_w * (uint32_t)spp));
+        jobs[(size_t)j].in_off = u.in_off;
+        jobs[(size_t)j].dst_off = u.scratch_off;
+        jobs[(size_t)j].parsed = jpeg_prepare(tb, tl, pin + u.in_off, (size_t)u.cnt, S.geom.seg_w, rows, spp,
+                                              plans[(size_t)j], &why[(size_t)j]);
+    });
+    for (size_t j = 0; j < m; ++j)
+        if (jobs[j].parsed == OMR_INVALID_ARGUMENT) return fail(ctx, OMR_INVALID_ARGUMENT, said(S, "unsupported JPEG segment: ") + why[j]);
+        else if (jobs[j].parsed) return fail(ctx, OMR_INTERNAL, said(S, "corrupt JPEG ") + S.noun + " (" + why[j] + ")");
+    const size_t place_at = align_up(in_bytes, 256), place_bytes = plan.places.size() * sizeof(TiffPlace);
+    TiffPlace* h_place = reinterpret_cast<TiffPlace*>(pin + place_at);
+    for (size_t k = 0; k < plan.places.size(); ++k) {
+        const SegBytes& u = segs[(size_t)plan.place_seg[k]];
+        plan.places[k].src = !u.cnt ? nullptr : dscr + u.scratch_off;
+        h_place[k] = plan.places[k];
+    }
+    OMR_HIP(ctx, hipMemcpyAsync(din, pin, place_at + place_bytes, hipMemcpyHostToDevice, ctx->stream));
+    std::vector<int32_t> status;
+    omr_status st = jpeg_decode_group(ctx, T, jobs, plans, spp, S.jpeg_ycc, din, dscr, status);
+    if (st) return st;
+    st = launch_tiff_place(ctx, reinterpret_cast<const TiffPlace*>(din + place_at), (int32_t)plan.places.size(), plan.max_rows,
+                           S.geom.bpp, 1, false, S.geom.spp);
+    if (st) return st;
+    st = jpeg_group_statuses(ctx, T, status);
+    if (st) return st;
+    for (int32_t s : status)
+        if (s != OMR_OK) return fail(ctx, OMR_INTERNAL, said(S, "corrupt JPEG ") + S.noun);
+    return OMR_OK;
+}
+
 // One group of regions: reqs[r0, r1).
 omr_status read_group(Ctx* ctx, SegSource& S, const omr_raw_tile_request* reqs, int32_t r0, int32_t r1, int32_t width,
                       int32_t height, uint8_t* d_dst, int64_t stride) {
@@ -156,6 +209,7 @@ omr_status read_group(Ctx* ctx, SegSource& S, const omr_raw_tile_request* reqs, 
     uint8_t* dscr = static_cast<uint8_t*>(T->d_scratch);
     if (!S.read(plan.segs, segs, pin, in_bytes)) return fail(ctx, OMR_INTERNAL, said(S, S.noun) + " read failed");
     if (blosc) return finish_blosc(ctx, T, S, plan, segs, in_bytes);
+    if (S.codec == SegCodec::jpeg) return finish_jpeg(ctx, T, S, plan, segs, in_bytes);
     for (size_t j = 0; j < m; ++j) {
         const SegBytes& u = segs[(size_t)coded[j]];
         t.off(pin)[j] = u.in_off;
@@ -200,7 +254,9 @@ omr_status read_regions(Ctx* ctx, SegSource& src, const omr_raw_tile_request* re
                         int32_t height, void* d_dst, int64_t region_stride_bytes) {
     if (n == 0 || width == 0 || height == 0) return OMR_OK;
     OMR_HIP(ctx, hipSetDevice(ctx->device));
-    const int32_t G = group_size(n, std::min(kGroupInBytes, kGroupScratchBytes), read_bytes_per_request(src.geom, width, height));
+    size_t per_req = read_bytes_per_request(src.geom, width, height);
+    if (src.codec == SegCodec::jpeg) per_req += jpeg_workspace_per_request(src.geom, width, height);   // K17's coefficients and planes
+    const int32_t G = group_size(n, std::min(kGroupInBytes, kGroupScratchBytes), per_req);
     for (int32_t r0 = 0; r0 < n; r0 += G) {
         const omr_status st = read_group(ctx, src, reqs, r0, std::min(n, r0 + G), width, height,
                                          static_cast<uint8_t*>(d_dst), region_stride_bytes);

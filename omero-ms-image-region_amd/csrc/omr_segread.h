@@ -1,4 +1,4 @@
-// omr_segread.h — the device-read pipeline that the TIFF and the Zarr reader share (K13 .. K16).
+// omr_segread.h — the device-read pipeline that the TIFF and the Zarr reader share (K13 .. K17).
 //
 // Both readers answer a batch of regions the same way: the segments (tiles, strips, chunks) the
 // regions touch are listed once each, their bytes go to pinned memory and in one copy to the device
@@ -41,6 +41,10 @@ struct SegPipe {
     size_t tab_cap = 0;
     void* d_lit = nullptr;       // K16a: one literal buffer per workgroup of its grid
     size_t lit_cap = 0;
+    void* d_coef = nullptr;      // K17: the JPEG segments' coefficients (int16) and sample planes
+    size_t coef_cap = 0;
+    size_t jpeg_status_off = 0;  // of the group in flight: where its statuses are in pin_tab / d_tab,
+    std::vector<int32_t> jpeg_live;   // and the jobs they belong to (jpeg_decode_group .. jpeg_group_statuses)
     ~SegPipe();
 };
 
@@ -174,7 +178,15 @@ struct TableLayout {
 
 // ---- what a front-end supplies ------------------------------------------------------------------
 
-enum class SegCodec { none, lzw, zlib, zstd, blosc };
+enum class SegCodec { none, lzw, zlib, zstd, blosc, jpeg };
+
+// What a read request of a JPEG level can need beside read_bytes_per_request: K17's workspace
+// (coefficients and sample planes) of the same segments, so that a group's workspace stays within
+// kGroupScratchBytes as its decoded bytes do.
+inline size_t jpeg_workspace_per_request(const SegGeom& g, int32_t width, int32_t height) {
+    const size_t per_seg = (size_t)3 * g.spp * (((size_t)g.seg_w + 15) / 16 * 16) * (((size_t)g.seg_h + 15) / 16 * 16) + 512;
+    return (size_t)((width - 1) / g.seg_w + 2) * (size_t)((height - 1) / g.seg_h + 2) * per_seg;
+}
 
 // One unique segment of a group: cnt bytes to read (0: the segment reads as zeros) that hold, or
 // decode to, `expected` bytes.  The pipeline sets the two offsets.
@@ -203,7 +215,32 @@ struct SegSource {
     virtual omr_status sizes(Ctx* ctx, const std::vector<SegKey>& keys, std::vector<SegBytes>& out) = 0;
     // cnt bytes of every segment to pin + in_off; in_bytes: their sum.  false: an I/O error.
     virtual bool read(const std::vector<SegKey>& keys, const std::vector<SegBytes>& segs, uint8_t* pin, size_t in_bytes) = 0;
+    // SegCodec::jpeg: the JPEGTables stream of a segment's IFD (*len = 0: none) and whether the
+    // three components are YCbCr (Photometric 6).
+    virtual const uint8_t* jpeg_tables(const SegKey&, size_t* len) const { *len = 0; return nullptr; }
+    bool jpeg_ycc = false;
 };
+
+// ---- K17: one group of JPEG segments (omr_jpegdec.hip) -------------------------------------------
+
+struct JpegPlan;
+// One stream: its bytes are at d_src + in_off, it decodes to d_dst + dst_off; parsed: what
+// jpeg_prepare said of it (anything but OMR_OK: it is not decoded and that is its status).
+struct JpegJob {
+    uint64_t in_off = 0, dst_off = 0;
+    omr_status parsed = OMR_OK;
+};
+// The descriptor table of the jobs (plans[k]: job k's jpeg_prepare) into T->pin_tab, up in one
+// copy, the workspace in T->d_coef, and K17a, K17b, K17c on the context's stream.  status: filled
+// with what is known on the host; jpeg_group_statuses then synchronises and adds the kernels'.
+omr_status jpeg_decode_group(Ctx* ctx, SegPipe* T, const std::vector<JpegJob>& jobs, const std::vector<JpegPlan>& plans,
+                             int32_t samples, bool ycc, const uint8_t* d_src, uint8_t* d_dst, std::vector<int32_t>& status);
+omr_status jpeg_group_statuses(Ctx* ctx, SegPipe* T, std::vector<int32_t>& status);
+
+// Growth of a pipe's buffers (omr_segread.cpp): device memory, and a pinned buffer with its device
+// twin of at least `total` bytes (by half again when they grow); what: the words of the message.
+omr_status grow_device(Ctx* c, void*& p, size_t& cap, size_t bytes);
+omr_status grow_pinned(Ctx* c, void*& pin, void*& dev, size_t& cap, size_t total, const std::string& what);
 
 // ---- the device route (omr_segread.cpp) ---------------------------------------------------------
 

@@ -9,10 +9,14 @@
 // pread of the segments' bytes from the one file.  omr_tiff_image_open_ex widens what a file may
 // use: Deflate and Zstandard segments (decoded on the host by omr_inflate_host and
 // omr_zstd_decode_host, on the device by K14a and K16a), the floating-point predictor and chunky
-// pixels of 2..4 samples, of which a read takes one.  The device route itself -- staging, planning,
+// pixels of 2..4 samples, of which a read takes one, and baseline JPEG segments (Compression 7 with
+// the JPEGTables of tag 347; omr_jpeg_decode_host here, K17a .. K17c on the device: omr_jpegdec.*).
+// The device route itself -- staging, planning,
 // K13a's and K13b's launches (omr_tiffread.hip), the tile renderer -- is omr_segread.cpp, shared
 // with the Zarr reader; this file calls no HIP function.
 #include "omr_segread.h"
+
+#include "omr_jpegdec.h"
 
 #include <fcntl.h>
 #include <sys/stat.h>
@@ -27,6 +31,7 @@ namespace {
 constexpr uint64_t kMaxSegmentBytes = (uint64_t)256 << 20;   // decoded size of one segment
 constexpr uint64_t kMaxStreamBytes = ((uint64_t)512 << 20) - 1;
 constexpr uint32_t kMaxIfds = 1u << 20;
+constexpr uint64_t kMaxJpegTables = 64u << 10;               // tag 347
 
 struct Level {
     int32_t w = 0, h = 0;          // image size at this level
@@ -40,6 +45,7 @@ struct Level {
 
 struct Segments {
     std::vector<uint64_t> off, cnt;   // [down][across]
+    std::vector<uint8_t> jpeg_tables; // Compression 7: the IFD's JPEGTables stream (tag 347), if any
 };
 
 }  // namespace
@@ -52,6 +58,7 @@ struct omr_tiff_image {
     int64_t stride_z = 0, stride_c = 0, stride_t = 0;   // plane index = z*stride_z + c*stride_c + t*stride_t
     int32_t pt = 0, bpp = 0, compression = 1, predictor = 1;
     int32_t spp = 1;                                    // samples per pixel (chunky): channel c is sample c % spp
+    bool jpeg_ycc = false;                              // Compression 7 with Photometric 6: YCbCr -> RGB on decode
     std::vector<Level> levels;
     std::vector<std::vector<Segments>> segs;   // [plane][level]
     ~omr_tiff_image() {
@@ -84,6 +91,7 @@ struct Ifd {
     bool has_tw = false, has_th = false;
     bool mixed = false;            // BitsPerSample or SampleFormat differ between the samples of a pixel
     std::vector<uint64_t> strip_off, strip_cnt, tile_off, tile_cnt, sub;
+    std::vector<uint8_t> jpeg_tables;
 };
 
 struct Parser {
@@ -137,6 +145,21 @@ struct Parser {
             for (uint64_t o : vals) *mixed = *mixed || o != v;
         return OMR_OK;
     }
+    // The bytes of a BYTE or UNDEFINED entry of at most `cap` values (JPEGTables).
+    omr_status bytes(const uint8_t* e, uint64_t cap, std::vector<uint8_t>& out) const {
+        const uint32_t type = (uint32_t)u(e + 2, 2);
+        const uint64_t count = bigtiff ? u(e + 4, 8) : u(e + 4, 4);
+        const uint8_t* field = e + (bigtiff ? 12 : 8);
+        const int field_bytes = bigtiff ? 8 : 4;
+        if (type != 1 && type != 7) return OMR_INVALID_ARGUMENT;
+        if (count > cap) return OMR_INVALID_ARGUMENT;
+        out.resize((size_t)count);
+        if (count <= (uint64_t)field_bytes) {
+            std::memcpy(out.data(), field, (size_t)count);
+            return OMR_OK;
+        }
+        return rd(u(field, field_bytes), out.data(), count) ? OMR_OK : OMR_INTERNAL;
+    }
     // Entry count and the offset of the next IFD; with `ifd`, the tags too.
     omr_status read_ifd(uint64_t off, Ifd* ifd, uint64_t& next) const {
         uint8_t head[8];
@@ -173,6 +196,7 @@ struct Parser {
             case 325: st = values(e, ifd->tile_cnt); break;
             case 330: st = values(e, ifd->sub); break;
             case 339: st = scalar(e, ifd->fmt, &ifd->mixed); break;
+            case 347: st = bytes(e, kMaxJpegTables, ifd->jpeg_tables); break;
             default: break;
             }
             if (st) return st;
@@ -196,12 +220,13 @@ inline int32_t rows_in_segment(const Level& L, int32_t sy) {
 // One IFD into the image: geometry, format and the segment table, all checked.
 // accept: the OMR_TIFF_ACCEPT_* bits of the open; a feature the file uses without its bit is refused.
 omr_status take_ifd(const Parser& P, const Ifd& f, uint32_t accept, Level& L, Segments& S, int32_t& pt, int32_t& comp,
-                    int32_t& pred, int32_t& spp) {
+                    int32_t& pred, int32_t& spp, bool& ycc) {
     if (f.fill != 1) return OMR_INVALID_ARGUMENT;
     if (f.spp != 1) {
         if (!(accept & OMR_TIFF_ACCEPT_SAMPLES) || f.spp < 1 || f.spp > 4) return OMR_INVALID_ARGUMENT;
-        if (f.planar != 1 || f.photometric == 6 || f.mixed) return OMR_INVALID_ARGUMENT;
+        if (f.planar != 1 || (f.photometric == 6 && f.comp != 7) || f.mixed) return OMR_INVALID_ARGUMENT;
     }
+    ycc = false;
     switch (f.comp) {
     case 1: case 5: comp = (int32_t)f.comp; break;
     case 8: case 32946:
@@ -211,6 +236,13 @@ omr_status take_ifd(const Parser& P, const Ifd& f, uint32_t accept, Level& L, Se
     case 50000:
         if (!(accept & OMR_TIFF_ACCEPT_ZSTD)) return OMR_INVALID_ARGUMENT;
         comp = 50000;
+        break;
+    case 7:                                              // one baseline JPEG stream per segment (K17)
+        if (!(accept & OMR_TIFF_ACCEPT_JPEG)) return OMR_INVALID_ARGUMENT;
+        if (f.bps != 8 || f.fmt != 1 || f.pred != 1 || f.mixed) return OMR_INVALID_ARGUMENT;
+        if (f.spp == 1 ? f.photometric > 1 : f.spp != 3 || (f.photometric != 2 && f.photometric != 6)) return OMR_INVALID_ARGUMENT;
+        ycc = f.photometric == 6;
+        comp = 7;
         break;
     default: return OMR_INVALID_ARGUMENT;
     }
@@ -266,6 +298,7 @@ omr_status take_ifd(const Parser& P, const Ifd& f, uint32_t accept, Level& L, Se
     }
     S.off = *off;
     S.cnt = *cnt;
+    if (comp == 7) S.jpeg_tables = f.jpeg_tables;
     return OMR_OK;
 }
 
@@ -430,6 +463,14 @@ omr_status load_segment(const omr_tiff_image* im, const Level& L, const Segments
         case 5: ok = lzw_decode(comp.data(), (size_t)cnt, out.data(), expected); break;
         case 8: ok = omr_inflate_host(comp.data(), (size_t)cnt, out.data(), expected) == OMR_OK; break;
         case 50000: ok = omr_zstd_decode_host(comp.data(), (size_t)cnt, out.data(), expected) == OMR_OK; break;
+        case 7: {
+            const omr_status st = omr_jpeg_decode_host(S.jpeg_tables.empty() ? nullptr : S.jpeg_tables.data(), S.jpeg_tables.size(),
+                                                       comp.data(), (size_t)cnt, L.seg_w, rows, im->spp, im->jpeg_ycc,
+                                                       out.data(), nullptr, 0);
+            if (st == OMR_INVALID_ARGUMENT) return st;      // a valid form out of scope
+            ok = st == OMR_OK;
+            break;
+        }
         default: ok = false; break;
         }
         if (!ok) return OMR_INTERNAL;
@@ -461,11 +502,18 @@ struct TiffSource final : omr::SegSource {
         case 5: codec = omr::SegCodec::lzw; break;
         case 8: codec = omr::SegCodec::zlib; break;
         case 50000: codec = omr::SegCodec::zstd; break;
+        case 7: codec = omr::SegCodec::jpeg; break;
         default: codec = omr::SegCodec::none; break;
         }
         predictor = im->predictor;
         swap = im->big == host_little_endian();
         pt = im->pt; big = im->big;
+        jpeg_ycc = im->jpeg_ycc;
+    }
+    const uint8_t* jpeg_tables(const omr::SegKey& k, size_t* len) const override {
+        const std::vector<uint8_t>& t = table(k).jpeg_tables;
+        *len = t.size();
+        return t.empty() ? nullptr : t.data();
     }
     const Segments& table(const omr::SegKey& k) const { return im->segs[(size_t)k.plane][level]; }
     size_t slot(const omr::SegKey& k) const { return (size_t)k.sy * geom.across + k.sx; }
@@ -510,7 +558,8 @@ omr_status omr_tiff_image_open_ex(const char* path, int32_t size_z, int32_t size
     if (opt) {
         if (opt->struct_size < sizeof(omr_tiff_open_options)) return OMR_INVALID_ARGUMENT;
         accept = opt->accept;
-        if (accept & ~(OMR_TIFF_ACCEPT_DEFLATE | OMR_TIFF_ACCEPT_ZSTD | OMR_TIFF_ACCEPT_PREDICTOR3 | OMR_TIFF_ACCEPT_SAMPLES))
+        if (accept & ~(OMR_TIFF_ACCEPT_DEFLATE | OMR_TIFF_ACCEPT_ZSTD | OMR_TIFF_ACCEPT_PREDICTOR3 | OMR_TIFF_ACCEPT_SAMPLES |
+                       OMR_TIFF_ACCEPT_JPEG))
             return OMR_INVALID_ARGUMENT;
     }
     if (!path || !dimension_order || size_z <= 0 || size_c <= 0 || size_t_ <= 0) return OMR_INVALID_ARGUMENT;
@@ -574,7 +623,8 @@ omr_status omr_tiff_image_open_ex(const char* path, int32_t size_z, int32_t size
                 if (st) return st;
             }
             int32_t pt = 0, comp = 0, pred = 0, spp = 1;
-            st = take_ifd(P, k ? sub : main, accept, lv[k], sg[k], pt, comp, pred, spp);
+            bool ycc = false;
+            st = take_ifd(P, k ? sub : main, accept, lv[k], sg[k], pt, comp, pred, spp, ycc);
             if (st) return st;
             if (first) {
                 im->pt = pt;
@@ -582,13 +632,14 @@ omr_status omr_tiff_image_open_ex(const char* path, int32_t size_z, int32_t size
                 im->compression = comp;
                 im->predictor = pred;
                 im->spp = spp;
+                im->jpeg_ycc = ycc;
                 first = false;
                 if (spp > 1) {                           // the chain holds Z * (C / spp) * T IFDs
                     if (size_c % spp) return OMR_INVALID_ARGUMENT;
                     n_planes = n_planes / size_c * (size_c / spp);
                     (void)set_strides(im.get(), dimension_order, size_c / spp);
                 }
-            } else if (pt != im->pt || comp != im->compression || pred != im->predictor || spp != im->spp) {
+            } else if (pt != im->pt || comp != im->compression || pred != im->predictor || spp != im->spp || ycc != im->jpeg_ycc) {
                 return OMR_INVALID_ARGUMENT;             // planes or levels that disagree
             }
         }

@@ -108,7 +108,10 @@ class TiffInfo(ctypes.Structure):
         "predictor", "tiled", "segment_width", "segment_height", "big_tiff")]
 
 
-TIFF_ACCEPT = {"deflate": 1, "zstd": 2, "predictor3": 4, "samples": 8}    # OMR_TIFF_ACCEPT_*
+TIFF_ACCEPT = {"deflate": 1, "zstd": 2, "predictor3": 4, "samples": 8, "jpeg": 16}    # OMR_TIFF_ACCEPT_*
+# OMR_JPEG_FORM_*: omr.jpeg_stream_forms returns the set of names, form f is bit f
+JPEG_FORM_NAMES = ("EOB_EARLY", "FULL_BLOCK", "ZRL", "LONG_CODE", "DC_CAT9", "STUFFED_FF", "RESTART", "PAD_BITS",
+                   "TABLE_OVERRIDE", "MULTI_TABLE", "COM", "FILL_BYTES", "TABLES_STREAM")
 
 
 class TiffOpenOptions(ctypes.Structure):
@@ -336,6 +339,9 @@ _SIGS = {
     "omr_zstd_frame_forms": (_i32, [_vp, _sz, ctypes.POINTER(ctypes.c_uint32)]),
     "omr_blosc_decode_host_ex": (_i32, [_vp, _sz, _vp, _sz, ctypes.c_uint32]),
     "omr_zstd_decode_batch_device": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "omr_jpeg_decode_host": (_i32, [_vp, _sz, _vp, _sz, _i32, _i32, _i32, _i32, _vp, _vp, _sz]),
+    "omr_jpeg_stream_forms": (_i32, [_vp, _sz, _vp, _sz, ctypes.POINTER(ctypes.c_uint32)]),
+    "omr_jpeg_decode_batch_device": (_i32, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "omr_render_shape_mask_png_batch": (_i32, [_vp, ctypes.POINTER(MaskJob), _i32, _vp, _sz, _vp, _vp, _vp]),
     "omr_split_html_color": (_i32, [ctypes.c_char_p, ctypes.POINTER(_i32)]),
     "omr_shape_mask_fill_color": (_i32, [_i32, _i32, ctypes.c_char_p, _vp]),

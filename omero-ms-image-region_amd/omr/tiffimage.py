@@ -6,7 +6,8 @@ pyramidal OME-TIFF as raw2ometiff writes it, one IFD per plane and the lower res
 SubIFDs.  Reads go through libomr.so: get_tile on the host (plain serial LZW decoder), read_regions
 and render_tiles with the LZW segments decoded on the GPU (omr_tiffread.hip).  With accept=...
 (omr_tiff_image_open_ex) also Deflate and zstd segments, the floating-point predictor and chunky
-pixels of several samples (RGB), each channel one sample.
+pixels of several samples (RGB), each channel one sample, and with "jpeg" baseline JPEG segments
+(Compression 7, K17: omr_jpegdec.hip), grey, RGB or YCbCr converted to RGB.
 """
 import ctypes
 import struct
@@ -104,6 +105,38 @@ def _predict_fp(seg):
     return d
 
 
+def _jpeg_markers(stream):
+    """A JPEG stream as ([(marker, whole marker segment) up to SOS, SOI left out], the rest from SOS on)."""
+    assert stream[:2] == b"\xff\xd8"
+    pos, out = 2, []
+    while True:
+        assert stream[pos] == 0xFF
+        m = stream[pos + 1]
+        if m == 0xDA:
+            return out, stream[pos:]
+        n = struct.unpack_from(">H", stream, pos + 2)[0]
+        out.append((m, stream[pos:pos + 2 + n]))
+        pos += 2 + n
+
+
+def _jpeg_encode(seg, opt):
+    """One segment ([rows][cols] or [rows][cols][3] uint8) as a whole baseline JFIF stream, by Pillow."""
+    import io
+    from PIL import Image
+    im = Image.fromarray(np.ascontiguousarray(seg))
+    kw = dict(format="JPEG", quality=int(opt.get("quality", 85)), optimize=bool(opt.get("optimize", False)))
+    if opt.get("restart_blocks"):
+        kw["restart_marker_blocks"] = int(opt["restart_blocks"])
+    if seg.ndim == 3:
+        if opt.get("photometric", "ycbcr") == "rgb":
+            kw.update(keep_rgb=True, subsampling="4:4:4")
+        else:
+            kw["subsampling"] = opt.get("subsampling", "4:4:4")
+    f = io.BytesIO()
+    im.save(f, **kw)
+    return f.getvalue()
+
+
 def _zstd_job(raw):
     from .zarrimage import zstd_encode
     return zstd_encode(raw)
@@ -111,7 +144,8 @@ def _zstd_job(raw):
 
 def write_tiled_tiff(path, planes, levels=(), tile=(256, 256), rows_per_strip=None, byteorder="<", bigtiff=False,
                      compression=1, predictor=1, early_clear=0, eoi=True, dimension_order="XYZCT",
-                     skip_zero_segments=False, tag_overrides=None, mapper=map, samples_per_pixel=1, encoder=None):
+                     skip_zero_segments=False, tag_overrides=None, mapper=map, samples_per_pixel=1, encoder=None,
+                     jpeg=None):
     """Write a [t][c][z][y][x] array as a TIFF with one IFD per plane (in `dimension_order`), and
     `levels` (arrays of the same [t][c][z] with their own [y][x]) as SubIFDs of each plane.
     tile = (w, h), or rows_per_strip = n for strips; byteorder "<" (II) or ">" (MM); compression 1,
@@ -124,6 +158,12 @@ def write_tiled_tiff(path, planes, levels=(), tile=(256, 256), rows_per_strip=No
     value} replaces the value written for a SHORT tag (to make files a reader must reject); mapper:
     a map() that encodes the segments of one image, e.g. a multiprocessing pool's for big files;
     encoder: a function bytes -> bytes in place of the codec's own (libzstd's, say, for 50000).
+    compression 7 (uint8, one sample or three): baseline JPEG segments encoded by Pillow (imported
+    here, a test and tooling aid), edge tiles padded by edge replication; jpeg = {"quality": 85,
+    "subsampling": "4:4:4" | "4:2:2" | "4:2:0", "restart_blocks": MCUs per restart interval,
+    "optimize": False, "photometric": "ycbcr" | "rgb" for three samples (a single sample is grey),
+    "tables": "inline" (whole streams) | "shared" (the first segment's DQT / DHT in tag 347 and
+    every marker segment equal to one of them cut out of the streams)}.
     Returns {"ifds": [offset per plane], "subifds": [[offsets] per plane]}."""
     planes = np.asarray(planes)
     assert planes.ndim == 5, "planes must be [t][c][z][y][x]"
@@ -140,6 +180,10 @@ def write_tiled_tiff(path, planes, levels=(), tile=(256, 256), rows_per_strip=No
     bo = byteorder
     fdt = dt.newbyteorder(bo) if dt.itemsize > 1 else dt
     tag_overrides = dict(tag_overrides or {})
+    jpeg = dict(jpeg or {})
+    if compression == 7:
+        assert dt == np.uint8 and spp in (1, 3) and predictor == 1, "JPEG: uint8, one or three samples, no predictor"
+    jpeg_ycc = compression == 7 and spp == 3 and jpeg.get("photometric", "ycbcr") != "rgb"
     buf = bytearray(b"II" if bo == "<" else b"MM")
     if bigtiff:
         buf += struct.pack(bo + "HHHQ", 43, 8, 0, 0)
@@ -156,7 +200,20 @@ def write_tiled_tiff(path, planes, levels=(), tile=(256, 256), rows_per_strip=No
         else:
             boxes = [(0, y, w, min(rows_per_strip, h - y)) for y in range(0, h, rows_per_strip)]
         raws = []
-        for (x, y, bw, bh) in boxes:
+        shared = None
+        for (x, y, bw, bh) in boxes if compression == 7 else ():
+            part = img[y:y + bh, x:x + bw]
+            pad = [(0, bh - part.shape[0]), (0, bw - part.shape[1])] + [(0, 0)] * (img.ndim - 2)
+            stream = _jpeg_encode(np.pad(part, pad, mode="edge"), jpeg)
+            if jpeg.get("rewrite"):                      # a function stream -> stream (the fixture's marker rewrites)
+                stream = jpeg["rewrite"](stream)
+            if jpeg.get("tables", "inline") == "shared":
+                head, rest = _jpeg_markers(stream)
+                if shared is None:
+                    shared = [s for (m, s) in head if m in (0xDB, 0xC4)]
+                stream = b"\xff\xd8" + b"".join(s for (m, s) in head if s not in shared) + rest
+            raws.append(stream)
+        for (x, y, bw, bh) in () if compression == 7 else boxes:
             seg = np.zeros((bh, bw) + img.shape[2:], dtype=fdt)
             part = img[y:y + bh, x:x + bw]
             seg[:part.shape[0], :part.shape[1]] = part
@@ -191,6 +248,8 @@ def write_tiled_tiff(path, planes, levels=(), tile=(256, 256), rows_per_strip=No
             geom = [(322, "H", [tile[0]]), (323, "H", [tile[1]]), (324, ofmt, offs), (325, ofmt, cnts)]
         else:
             geom = [(273, ofmt, offs), (278, "I", [rows_per_strip]), (279, ofmt, cnts)]
+        if shared is not None:
+            geom.append((347, "B", list(b"\xff\xd8" + b"".join(shared) + b"\xff\xd9")))
         return geom
 
     def ifd_entries(img, n_sub):
@@ -202,6 +261,11 @@ def write_tiled_tiff(path, planes, levels=(), tile=(256, 256), rows_per_strip=No
             ent.append((338, "H", [0] * n_extra))        # ExtraSamples: unspecified data
         if predictor != 1 or 317 in tag_overrides:
             ent.append((317, "H", [predictor]))
+        if compression == 7 and spp == 3:
+            ent = [e for e in ent if e[0] != 262] + [(262, "H", [6 if jpeg_ycc else 2])]
+            if jpeg_ycc:
+                hv = {"4:4:4": (1, 1), "4:2:2": (2, 1), "4:2:0": (2, 2)}[jpeg.get("subsampling", "4:4:4")]
+                ent.append((530, "H", list(hv)))
         if 266 in tag_overrides:
             ent.append((266, "H", [1]))
         ent += segments(img)
@@ -210,8 +274,7 @@ def write_tiled_tiff(path, planes, levels=(), tile=(256, 256), rows_per_strip=No
         ent = [(t, f, [tag_overrides[t]] if t in tag_overrides else v) for (t, f, v) in ent]
         return sorted(ent)
 
-    tsize = {"H": 2, "I": 4, "Q": 8}
-    tcode = {"H": 3, "I": 4, "Q": 16}
+    tcode = {"H": 3, "I": 4, "Q": 16, "B": 7}
 
     def emit_ifd(ent, next_at_end=True):
         """Out-of-line values, then the IFD itself; returns (ifd offset, {tag: position of its values})."""
@@ -279,7 +342,7 @@ class TiffImage:
 
     def __init__(self, path, size_z=1, size_c=1, size_t=1, dimension_order="XYZCT", accept=()):
         """accept: the further forms a file may use, any of "deflate", "zstd", "predictor3" and
-        "samples" (omr_tiff_image_open_ex); empty: the plain open, which refuses them all.  size_c
+        "samples" and "jpeg" (omr_tiff_image_open_ex); empty: the plain open, which refuses them all.  size_c
         counts every sample of a chunky image as a channel (3 for an RGB image)."""
         h = ctypes.c_void_p()
         accept = (accept,) if isinstance(accept, str) else tuple(accept)
@@ -387,3 +450,58 @@ def lzw_decode_host(stream, expected):
     out = np.zeros(max(int(expected), 1), dtype=np.uint8)
     _lib.check(lib.omr_lzw_decode_host(src.ctypes.data if src.size else None, src.size, out.ctypes.data, int(expected)))
     return out[:int(expected)].tobytes()
+
+
+def jpeg_decode_host(stream, width, height, samples=1, ycbcr=False, tables=None):
+    """The host JPEG decoder alone (omr_jpeg_decode_host): [height][width] or [height][width][3]
+    uint8, or OmrError (INVALID_ARGUMENT: a form out of scope, named in the message; INTERNAL: damage)."""
+    src = np.frombuffer(bytes(stream), dtype=np.uint8)
+    tab = np.frombuffer(bytes(tables or b""), dtype=np.uint8)
+    out = np.zeros(max(int(width) * int(height) * int(samples), 1), dtype=np.uint8)
+    why = ctypes.create_string_buffer(160)
+    st = lib.omr_jpeg_decode_host(tab.ctypes.data if tab.size else None, tab.size, src.ctypes.data if src.size else None,
+                                  src.size, int(width), int(height), int(samples), int(bool(ycbcr)), out.ctypes.data, why, 160)
+    if st != _lib.OK:
+        raise _lib.OmrError(st, why.value.decode())
+    out = out[:int(width) * int(height) * int(samples)]
+    return out.reshape(height, width) if samples == 1 else out.reshape(height, width, samples)
+
+
+def jpeg_stream_forms(stream, tables=None):
+    """The forms a good stream uses (omr_jpeg_stream_forms), as a set of names of _lib.JPEG_FORM_NAMES."""
+    src = np.frombuffer(bytes(stream), dtype=np.uint8)
+    tab = np.frombuffer(bytes(tables or b""), dtype=np.uint8)
+    bits = ctypes.c_uint32(0)
+    _lib.check(lib.omr_jpeg_stream_forms(tab.ctypes.data if tab.size else None, tab.size,
+                                         src.ctypes.data if src.size else None, src.size, ctypes.byref(bits)))
+    return {n for k, n in enumerate(_lib.JPEG_FORM_NAMES) if bits.value >> k & 1}
+
+
+def jpeg_decode_batch_device(ctx, streams, sizes, samples=1, ycbcr=False, tables=None):
+    """K17 alone (omr_jpeg_decode_batch_device): streams[i] with a frame of sizes[i] = (width,
+    height), decoded on ctx's GPU.  Returns ([uint8 arrays, [h][w] or [h][w][3]], [status per stream])."""
+    import torch
+    n = len(streams)
+    blob = np.frombuffer(b"".join(bytes(s) for s in streams) or b"\0", dtype=np.uint8)
+    lens = np.array([len(s) for s in streams], dtype=np.uint32)
+    offs = np.concatenate([[0], np.cumsum(lens[:-1], dtype=np.uint64)]).astype(np.uint64) if n else np.zeros(0, np.uint64)
+    ws = np.array([int(w) for w, _ in sizes], dtype=np.int32)
+    hs = np.array([int(h) for _, h in sizes], dtype=np.int32)
+    nbytes = [int(w) * int(h) * samples for w, h in sizes]
+    doffs = np.array([sum((b + 31) // 16 * 16 for b in nbytes[:i]) for i in range(n)], dtype=np.uint64)
+    total = sum((b + 31) // 16 * 16 for b in nbytes)
+    out = torch.full((max(total, 16),), 0xA5, dtype=torch.uint8, device=f"cuda:{ctx.device}")
+    ctx.order_after_torch()
+    status = np.zeros(max(n, 1), dtype=np.int32)
+    tab = np.frombuffer(bytes(tables or b""), dtype=np.uint8)
+    _lib.check(lib.omr_jpeg_decode_batch_device(ctx.h, tab.ctypes.data if tab.size else None, tab.size, blob.ctypes.data,
+                                                offs.ctypes.data, lens.ctypes.data, ws.ctypes.data, hs.ctypes.data, n,
+                                                int(samples), int(bool(ycbcr)), out.data_ptr(), doffs.ctypes.data,
+                                                status.ctypes.data), ctx.h)
+    host = out.cpu().numpy()
+    got = []
+    for i, (w, h) in enumerate(sizes):
+        a = host[int(doffs[i]):int(doffs[i]) + nbytes[i]]
+        assert (host[int(doffs[i]) + nbytes[i]:int(doffs[i]) + (nbytes[i] + 31) // 16 * 16] == 0xA5).all(), "bytes behind a stream overwritten"
+        got.append(a.reshape(h, w) if samples == 1 else a.reshape(h, w, samples))
+    return got, [int(v) for v in status[:n]]
