@@ -131,7 +131,8 @@ void*       omr_ctx_get_stream(omr_ctx* ctx);
  * omr_zstd_decode_batch_device and, with 34 or 31, omr_zarr_image_read_regions_device on a
  * Blosc-Zstd or zstd image; 36 = JPEG entropy decode, 37 = JPEG IDCT and 38 = JPEG upsample /
  * colour / store: omr_jpeg_decode_batch_device and, in front of 31,
- * omr_tiff_image_read_regions_device on a JPEG image).
+ * omr_tiff_image_read_regions_device on a JPEG image; 39 = split JPEG entropy decode and 40 = its
+ * DC sums, in place of or beside 36 after omr_ctx_set_jpeg_split).
  */
 omr_status  omr_ctx_enable_kernel_timing(omr_ctx* ctx, int32_t enable);
 int32_t     omr_ctx_kernel_timings(omr_ctx* ctx, float* ms_out, int32_t* kind_out, int32_t cap);
@@ -1430,6 +1431,49 @@ omr_status omr_jpeg_decode_batch_device(omr_ctx* ctx, const uint8_t* tables, siz
                                         const uint64_t* offsets, const uint32_t* lengths, const int32_t* widths,
                                         const int32_t* heights, int32_t n, int32_t samples, int32_t ycbcr,
                                         uint8_t* d_dst, const uint64_t* dst_offsets, int32_t* status);
+/*
+ * K18: the entropy decode of a long restart interval spread over a workgroup.  K17a gives an
+ * interval to one wave and walks its symbol chain serially, which is slow for a stream without
+ * restart markers (one interval per tile).  K18a cuts the interval into subsequences of
+ * subsequence_bits bits and decodes it by the self-synchronising parallel Huffman decode
+ * (Weissenberger and Schmidt, "Massively Parallel Huffman Decoding on GPUs", ICPP 2018, and
+ * "Accelerating JPEG Decompression on GPUs", 2021): one workgroup of 256 lanes per interval, one
+ * lane per subsequence from a guessed state, lanes adopting their predecessor's exit state until
+ * nothing changes, then a pass that writes the coefficients; K18b turns the DC differences into
+ * values.  K17b and K17c follow unchanged, and the pixels and statuses are K17's.
+ *
+ * OFF BY DEFAULT: a context that never makes this call launches what it launched before.  With
+ * min_interval_bytes != 0 every interval of at least that many entropy-coded bytes (and fewer than
+ * 128 MiB) takes K18, the others K17a; one call may launch both.  The setting applies to
+ * omr_jpeg_decode_batch_device, omr_tiff_image_read_regions_device and omr_render_tiff_tiles.
+ * opt == NULL: off.  OMR_INVALID_ARGUMENT: a struct_size below the struct's, or subsequence_bits
+ * that is neither 0 nor a multiple of 32 in [32, 4096].
+ * omr_ctx_kernel_timings reports kind 39 for K18a and 40 for K18b, in front of 37 and 38 (and
+ * behind 36 when the call launches K17a too).
+ */
+typedef struct omr_jpeg_split_options {
+    uint32_t struct_size;
+    uint32_t min_interval_bytes;   /* 0: off (the default). An interval of at least this many bytes takes K18 */
+    uint32_t subsequence_bits;     /* 0: the library's default (1024); else a multiple of 32 in [32, 4096] */
+} omr_jpeg_split_options;
+omr_status omr_ctx_set_jpeg_split(omr_ctx* ctx, const omr_jpeg_split_options* opt);   /* NULL: off */
+/*
+ * omr_jpeg_decode_host with the entropy decode done the way K18 does it, by the same per-lane
+ * functions (csrc/omr_jpegdec.h): plain loops play a workgroup of `lanes` lanes (1..256) through
+ * the rounds of K18a -- guess, settle, scan, write -- and then K18b's DC sums.  The statuses are
+ * omr_jpeg_decode_host's, and on OMR_OK so are the bytes.  OMR_INVALID_ARGUMENT also for
+ * subsequence_bits that is no multiple of 32 in [32, 4096] and lanes outside [1, 256].
+ * stats (required) says what the decode met, summed over the stream's intervals: the subsequences,
+ * the most rounds (of `lanes` subsequences) any interval took, the most settle iterations any round
+ * took before no lane changed, and the lane decodes repeated from an adopted state.
+ */
+typedef struct omr_jpeg_split_stats {
+    uint32_t subsequences, rounds, max_settle_iterations, redecodes;
+} omr_jpeg_split_stats;
+omr_status omr_jpeg_decode_host_split(const uint8_t* tables, size_t tables_length, const uint8_t* src, size_t length,
+                                      int32_t width, int32_t height, int32_t samples, int32_t ycbcr,
+                                      uint32_t subsequence_bits, uint32_t lanes, uint8_t* dst,
+                                      omr_jpeg_split_stats* stats);
 
 #ifdef __cplusplus
 }

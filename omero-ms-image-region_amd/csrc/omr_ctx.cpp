@@ -287,6 +287,21 @@ omr_status omr_ctx_set_stream(omr_ctx* c, void* s) {
     return OMR_OK;
 }
 
+omr_status omr_ctx_set_jpeg_split(omr_ctx* c, const omr_jpeg_split_options* opt) {
+    if (!c) return OMR_INVALID_ARGUMENT;
+    if (!opt) {
+        c->jpeg_split_min = c->jpeg_split_bits = 0;
+        return OMR_OK;
+    }
+    if (opt->struct_size < sizeof(omr_jpeg_split_options)) return fail(c, OMR_INVALID_ARGUMENT, "jpeg split: struct_size too small");
+    const uint32_t s = opt->subsequence_bits;
+    if (s && (s < 32 || s > 4096 || s % 32))
+        return fail(c, OMR_INVALID_ARGUMENT, "jpeg split: subsequence_bits must be 0 or a multiple of 32 in [32, 4096]");
+    c->jpeg_split_min = opt->min_interval_bytes;
+    c->jpeg_split_bits = s;
+    return OMR_OK;
+}
+
 omr_status omr_ctx_set_semantics(omr_ctx* c, uint32_t flags) {
     if (!c) return OMR_INVALID_ARGUMENT;
     if (flags & ~(uint32_t)OMR_SEM_ALL) return fail(c, OMR_INVALID_ARGUMENT, "unknown semantics flag");

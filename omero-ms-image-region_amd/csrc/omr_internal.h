@@ -133,6 +133,9 @@ struct Ctx {
     // JPEG B4a / B6 grids: chunk groups for streams of this many bytes per pixel x 100 (longer
     // streams loop; env OMR_JPEG_EST_CENTIBPP)
     int jpeg_est_centibpp = 100;
+    // K18 (omr_ctx_set_jpeg_split): a restart interval of at least jpeg_split_min bytes is decoded by
+    // k_jpeg_entropy_split in subsequences of jpeg_split_bits bits; 0: off, every interval takes K17a
+    uint32_t jpeg_split_min = 0, jpeg_split_bits = 0;
     // chunks per lane of K2's float / 32-bit grid-stride modes (env OMR_K2_EVAL_CPT=2|4; 4
     // measured 6% slower on C5, DESIGN.md §K2, so 2 by default)
     int k2_eval_cpt = -2;            // float / 32-bit K2: -1 / -2 pipelined chunks per lane, 2 / 4 plain

@@ -5,7 +5,9 @@
 // entropy-coded bytes), the serial decoder of the host route (omr_jpeg_decode_host: get_tile's, and
 // the reference of the device route) and omr_jpeg_stream_forms.  The device route
 // (omr_jpegdec.hip) takes its tables and intervals from the same jpeg_prepare and shares the
-// arithmetic behind the entropy decode with this file through omr_jpegdec.h.
+// arithmetic behind the entropy decode with this file through omr_jpegdec.h.  Also here: the host
+// emulation of the split entropy decode (K18, omr_jpeg_decode_host_split), which plays the lanes of
+// k_jpeg_entropy_split with the per-lane decoder of omr_jpegdec.h.
 //
 // All input is user-uploaded bytes: every read is behind a comparison with the stream's length
 // (Rd), the only allocations are sized by the caller's width and height (the frame must match
@@ -302,8 +304,92 @@ void reconstruct(const JpegPlan& P, bool ycc, const int16_t* coef, uint8_t* plan
         for (int32_t x = 0; x < P.w; ++x) jpeg_pixel(S, planes, x, y, out + ((size_t)y * P.w + x) * P.ncomp);
 }
 
+// ---- K18 on the host: plain loops play the lanes of k_jpeg_entropy_split ---------------------------
+
+// One interval through the rounds of K18a (omr_jpegdec.hip): guess, settle, scan, write.  The settle
+// step is the kernel's: every lane looks at its predecessor's exit state as the iteration before
+// left it (the kernel has a barrier between the look and the decode).  coef must be zero where the
+// interval's blocks are; the DC places get differences (split_dc_sums turns them into values).
+bool split_interval(const JpegPlan& P, const uint8_t* src, const JpegInterval& iv, int16_t* coef, uint32_t S, uint32_t L,
+                    omr_jpeg_split_stats& st) {
+    const uint8_t* s = src + iv.off;
+    const uint32_t len = (uint32_t)iv.len;
+    const uint32_t b0 = P.ncomp == 1 ? 1u : (uint32_t)(P.hs * P.vs), bpm = P.ncomp == 1 ? 1u : b0 + 2u;
+    const uint32_t total = iv.n_mcu * bpm;
+    const uint32_t nsub = (uint32_t)(((uint64_t)8 * len + S - 1) / S), rounds = (nsub + L - 1) / L;
+    const JpegHuff* huff = &P.tables.h[0][0];
+    std::vector<JpegLaneState> start(L);
+    std::vector<JpegLaneRun> run(L), seen(L);
+    std::vector<uint32_t> end(L);
+    JpegLaneState carry{0u, 0u};
+    uint32_t done = 0;                                     // blocks the earlier rounds finished
+    bool good = true;
+    st.subsequences += nsub;
+    uint32_t r = 0;
+    for (; r < rounds; ++r) {
+        const uint32_t live = std::min(L, nsub - r * L);   // the lanes that have a subsequence: the others sit still
+        for (uint32_t i = 0; i < L; ++i) {                 // 1. guess
+            const uint32_t sub = r * L + i;
+            start[i] = i == 0 ? carry : JpegLaneState{sub * S, 0u};
+            end[i] = sub < nsub ? (uint32_t)std::min<uint64_t>((uint64_t)(sub + 1) * S, (uint64_t)8 * len) : 0u;
+            run[i] = jpeg_lane_decode<false>(s, len, huff, kZigzag, b0, bpm, start[i], end[i], 0xFFFFFFFFu, JpegNoPut());
+        }
+        uint32_t it = 0;
+        for (; it < L; ++it) {                             // 2. settle
+            seen = run;
+            bool changed = false;
+            for (uint32_t i = 1; i < live; ++i)
+                if (seen[i - 1].exit != start[i]) {
+                    start[i] = seen[i - 1].exit;
+                    run[i] = jpeg_lane_decode<false>(s, len, huff, kZigzag, b0, bpm, start[i], end[i], 0xFFFFFFFFu, JpegNoPut());
+                    changed = true;
+                    ++st.redecodes;
+                }
+            if (!changed) break;
+        }
+        st.max_settle_iterations = std::max(st.max_settle_iterations, it);
+        uint32_t first = done;                             // 3. scan
+        for (uint32_t i = 0; i < L; ++i) {                 // 4. write
+            const uint32_t room = total > first ? total - first : 0u;
+            const uint32_t fm = iv.first_mcu;
+            jpeg_lane_decode<true>(s, len, huff, kZigzag, b0, bpm, start[i], end[i], room, [&](uint32_t b, uint32_t n, int32_t v) {
+                coef[(size_t)64 * (size_t)jpeg_block_of_ordinal(first + b, fm, P.ncomp, P.hs, P.vs, P.mcux, P.mcuy) + n] = (int16_t)v;
+            });
+            if ((run[i].exit.meta & kJpegLaneStop) && first + run[i].blocks < total) good = false;
+            if (run[i].err != kJpegLaneNoError && first + run[i].err < total) good = false;
+            first += run[i].blocks;
+        }
+        done = first;
+        carry = run[live - 1].exit;
+        if ((carry.meta & kJpegLaneStop) || done >= total) {
+            ++r;
+            break;
+        }
+    }
+    st.rounds = std::max(st.rounds, r);
+    return good && done >= total;
+}
+
+// K18b on the host: the DC differences of an interval's blocks into values, component by component
+// in decode order, the predictor from 0; false: a value outside [-2048, 2047].
+bool split_dc_sums(const JpegPlan& P, const JpegInterval& iv, int16_t* coef) {
+    for (int c = 0; c < P.ncomp; ++c) {
+        const uint32_t n = iv.n_mcu * (c == 0 ? (uint32_t)(P.hs * P.vs) : 1u);
+        int32_t pred = 0;
+        for (uint32_t t = 0; t < n; ++t) {
+            int16_t* dc = coef + (size_t)64 * (size_t)jpeg_block_of_comp(t, c, iv.first_mcu, P.hs, P.vs, P.mcux, P.mcuy);
+            pred += *dc;
+            if (pred < -2048 || pred > 2047) return false;
+            *dc = (int16_t)pred;
+        }
+    }
+    return true;
+}
+
+// split_bits != 0: the entropy decode by split_interval / split_dc_sums with `lanes` lanes.
 omr_status decode(const uint8_t* tables, size_t tables_len, const uint8_t* src, size_t len, int32_t w, int32_t h,
-                  int32_t samples, bool ycc, uint8_t* dst, uint32_t* forms, std::string* why) {
+                  int32_t samples, bool ycc, uint8_t* dst, uint32_t* forms, std::string* why, uint32_t split_bits = 0,
+                  uint32_t lanes = 0, omr_jpeg_split_stats* stats = nullptr) {
     std::unique_ptr<JpegPlan> P(new JpegPlan);
     const omr_status st = jpeg_prepare(tables, tables_len, src, len, w, h, samples, *P, why);
     if (st) return st;
@@ -311,11 +397,14 @@ omr_status decode(const uint8_t* tables, size_t tables_len, const uint8_t* src, 
     std::vector<int16_t> coef(blocks * 64);
     Decoder D{*P};
     D.forms = P->forms;
-    for (const JpegInterval& iv : P->intervals)
-        if (!D.interval(src, iv, coef.data())) {
+    for (const JpegInterval& iv : P->intervals) {
+        const bool split = split_bits && iv.len < kJpegSplitMaxLen;
+        if (split ? !(split_interval(*P, src, iv, coef.data(), split_bits, lanes, *stats) && split_dc_sums(*P, iv, coef.data()))
+                  : !D.interval(src, iv, coef.data())) {
             if (why) *why = "jpeg: damaged entropy-coded data";
             return OMR_INTERNAL;
         }
+    }
     if (forms) *forms = D.forms;
     if (dst) {
         std::vector<uint8_t> planes(blocks * 64);
@@ -494,6 +583,18 @@ omr_status omr_jpeg_decode_host(const uint8_t* tables, size_t tables_length, con
         why[why_cap - 1] = 0;
     }
     return st;
+}
+
+omr_status omr_jpeg_decode_host_split(const uint8_t* tables, size_t tables_length, const uint8_t* src, size_t length,
+                                      int32_t width, int32_t height, int32_t samples, int32_t ycbcr,
+                                      uint32_t subsequence_bits, uint32_t lanes, uint8_t* dst, omr_jpeg_split_stats* stats) {
+    if (!src || !dst || !stats || (!tables && tables_length) || width < 1 || height < 1 || (samples != 1 && samples != 3) ||
+        width > 65535 || height > 65535 || (uint64_t)width * (uint64_t)height * (uint64_t)samples > kMaxDecoded ||
+        subsequence_bits < 32 || subsequence_bits > 4096 || subsequence_bits % 32 || lanes < 1 || lanes > kJpegSplitLanes)
+        return OMR_INVALID_ARGUMENT;
+    *stats = omr_jpeg_split_stats{0, 0, 0, 0};
+    return decode(tables, tables_length, src, length, width, height, samples, ycbcr != 0, dst, nullptr, nullptr,
+                  subsequence_bits, lanes, stats);
 }
 
 omr_status omr_jpeg_stream_forms(const uint8_t* tables, size_t tables_length, const uint8_t* src, size_t length,

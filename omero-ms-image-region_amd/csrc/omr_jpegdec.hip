@@ -35,6 +35,30 @@
 // ncomp bytes at dst_off + p * ncomp, inside the w * h * ncomp bytes the segment owns.  After a
 // damaged interval they run over coefficients that were never written: any bytes give defined
 // arithmetic (omr_jpegdec.h) and the call fails on the status.
+//
+// K18 (off unless omr_ctx_set_jpeg_split asks for it): a long interval -- a tile without restart
+// markers is one -- decoded by a whole workgroup instead of K17a's one wave:
+//
+//   K18a  k_jpeg_entropy_split  one workgroup of 256 lanes per interval, by the self-synchronising
+//         split of the Huffman stream (omr_jpegdec.h has the method and the per-lane decoder, which
+//         the host emulation omr_jpeg_decode_host_split shares).  In rounds of 256 subsequences of S
+//         bits: lane 0 starts from the true state, the others guess; every lane whose predecessor's
+//         exit state differs from the state it started from decodes again from it, until no lane
+//         changed; a prefix sum of the finished blocks gives every lane its first block's ordinal; a
+//         last decode stores the non-zero AC coefficients and the DC differences into the zeroed
+//         coefficient area.
+//   K18b  k_jpeg_dc_sum         one wave per (interval, component): differences -> DC values.
+//
+// Bounds of K18.  The per-lane decoder reads src only at positions it has compared with iv.len
+// (JpegLaneBits::open and fill), whatever state it is given, and the tables as K17a does.  Its
+// loop ends after at most 8 * len symbols (each takes a bit); the rounds are counted from iv.len, the
+// settle loop stops after 256 iterations at the latest, and no workgroup waits for another.  A
+// store goes to coef[64 * block + n] with n = zigzag[k], k checked against 63, and block =
+// jpeg_block_of_ordinal(o) with o < n_mcu * blocks per MCU -- the write pass is given the room left
+// below that total and ends when it is used up -- so the MCU is one of [first_mcu, first_mcu +
+// n_mcu) and the block one of the interval's own, as in K17a: the stream's bytes steer which of
+// those places get which value, and the status.  K18b walks the same blocks by the host's counts
+// alone and keeps its running sum in 64 bits (a difference is an int16).
 #include "omr_jpegdec.h"
 #include "omr_segread.h"
 #include "omr_wave.h"
@@ -45,6 +69,8 @@ namespace {
 constexpr int kKindJpegEntropy = 36;   // omr_ctx_kernel_timings kinds (omr.h)
 constexpr int kKindJpegIdct = 37;
 constexpr int kKindJpegPixels = 38;
+constexpr int kKindJpegSplit = 39;     // K18a
+constexpr int kKindJpegDcSum = 40;     // K18b
 
 __device__ const uint8_t d_zigzag[64] = OMR_JPEG_ZIGZAG;   // zigzag position -> natural index
 
@@ -205,6 +231,123 @@ __global__ void __launch_bounds__(64) k_jpeg_entropy(const uint8_t* __restrict__
     if (!good && lane == 0) status[seg] = OMR_INTERNAL;
 }
 
+// K18a.  One workgroup of kJpegSplitLanes lanes per interval; the per-lane decode and its bounds are
+// jpeg_lane_decode's (omr_jpegdec.h), the bounds argument of the stores is at the head of this file.
+// Every barrier stands in control flow that all 256 lanes take alike: the round count comes from
+// iv.len, the settle loop leaves by __syncthreads_or, the early leave of the round loop by values all
+// lanes read from LDS behind a barrier.
+__global__ void __launch_bounds__(256) k_jpeg_entropy_split(const uint8_t* __restrict__ src, const JpegSegDesc* __restrict__ segs,
+                                                            const JpegIvDesc* __restrict__ ivs,
+                                                            const JpegTables* __restrict__ tables, uint8_t* __restrict__ ws,
+                                                            int32_t* __restrict__ status, uint32_t S) {
+    __shared__ uint32_t s_huff[3 * kJpegHuffBytes / 4];
+    __shared__ uint32_t s_pos[kJpegSplitLanes], s_meta[kJpegSplitLanes];
+    __shared__ uint32_t s_wave[kJpegSplitLanes / 64];
+    __shared__ uint8_t s_zz[64];
+    const uint32_t lane = threadIdx.x;
+    const JpegIvDesc iv = ivs[blockIdx.x];
+    const JpegSegDesc D = segs[iv.seg];
+    const int32_t ncomp = D.ncomp, hs = ncomp == 1 ? 1 : D.hs, vs = ncomp == 1 ? 1 : D.vs;
+    {
+        const uint32_t* g = reinterpret_cast<const uint32_t*>(tables + D.tables);
+        const uint32_t n = (uint32_t)ncomp * (uint32_t)(kJpegHuffBytes / 4);
+        for (uint32_t i = lane; i < n; i += kJpegSplitLanes) s_huff[i] = g[i];
+        if (lane < 64u) s_zz[lane] = d_zigzag[lane];
+    }
+    __syncthreads();
+    const JpegHuff* huff = reinterpret_cast<const JpegHuff*>(s_huff);
+    const uint8_t* in = src + iv.src_off;
+    const uint32_t len = min(iv.len, kJpegSplitMaxLen - 1u);      // the host sends no longer one
+    int16_t* coef = reinterpret_cast<int16_t*>(ws + D.coef_off);
+    const uint32_t b0 = (uint32_t)(hs * vs), bpm = ncomp == 1 ? 1u : b0 + 2u, total = iv.n_mcu * bpm;
+    const uint32_t nsub = (8u * len + S - 1u) / S, rounds = (nsub + kJpegSplitLanes - 1u) / kJpegSplitLanes;
+    JpegLaneState carry{0u, 0u};                           // where the earlier rounds ended, and
+    uint32_t done = 0;                                     // the blocks they finished
+    bool bad = false;
+    for (uint32_t r = 0; r < rounds; ++r) {
+        // 1. guess
+        const uint32_t live = min(kJpegSplitLanes, nsub - r * kJpegSplitLanes);   // lanes with a subsequence: the others sit still
+        const uint32_t sub = r * kJpegSplitLanes + lane;
+        JpegLaneState start = lane == 0u ? carry : JpegLaneState{sub * S, 0u};
+        const uint32_t end = sub < nsub ? min((sub + 1u) * S, 8u * len) : 0u;
+        JpegLaneRun run = jpeg_lane_decode<false>(in, len, huff, s_zz, b0, bpm, start, end, 0xFFFFFFFFu, JpegNoPut());
+        s_pos[lane] = run.exit.pos;
+        s_meta[lane] = run.exit.meta;
+        __syncthreads();
+        // 2. settle: after iteration j the lanes 0 .. j + 1 have the serial decoder's states
+        for (uint32_t it = 0; it < kJpegSplitLanes; ++it) {
+            JpegLaneState pred = start;
+            if (lane > 0u) pred = JpegLaneState{s_pos[lane - 1u], s_meta[lane - 1u]};
+            const bool differ = lane < live && pred != start;
+            __syncthreads();                               // every look before any new exit state
+            if (differ) {
+                start = pred;
+                run = jpeg_lane_decode<false>(in, len, huff, s_zz, b0, bpm, start, end, 0xFFFFFFFFu, JpegNoPut());
+                s_pos[lane] = run.exit.pos;
+                s_meta[lane] = run.exit.meta;
+            }
+            if (!__syncthreads_or(differ ? 1 : 0)) break;
+        }
+        // 3. scan
+        const uint32_t incl = wave_incl_scan(run.blocks, (int)(lane & 63u));
+        if ((lane & 63u) == 63u) s_wave[lane >> 6] = incl;
+        __syncthreads();
+        uint32_t first = done + incl - run.blocks, sum = 0;
+        for (uint32_t w = 0; w < kJpegSplitLanes / 64u; ++w) {
+            const uint32_t n = s_wave[w];
+            if (w < (lane >> 6)) first += n;
+            sum += n;
+        }
+        // 4. write: ordinals below the interval's total only
+        const uint32_t room = total > first ? total - first : 0u;
+        const uint32_t fm = iv.first_mcu;
+        jpeg_lane_decode<true>(in, len, huff, s_zz, b0, bpm, start, end, room, [&](uint32_t b, uint32_t n, int32_t v) {
+            coef[(size_t)64 * (size_t)jpeg_block_of_ordinal(first + b, fm, ncomp, hs, vs, D.mcux, D.mcuy) + n] = (int16_t)v;
+        });
+        if ((run.exit.meta & kJpegLaneStop) && first + run.blocks < total) bad = true;      // out of bits,
+        if (run.err != kJpegLaneNoError && first + run.err < total) bad = true;              // a hard error: below the total
+        carry = JpegLaneState{s_pos[live - 1u], s_meta[live - 1u]};
+        done += sum;
+        __syncthreads();                                   // the round's LDS is read before the next writes it
+        if ((carry.meta & kJpegLaneStop) || done >= total) break;
+    }
+    if (lane == 0u && done < total) bad = true;            // the interval ran out of bits before its last block
+    if (bad) status[iv.seg] = OMR_INTERNAL;
+}
+
+// K18b: one wave per (interval, component): the DC differences K18a left become values, in the
+// component's decode order, by a wave scan of 64 blocks and a 64-bit carry.
+__global__ void __launch_bounds__(64) k_jpeg_dc_sum(const JpegSegDesc* __restrict__ segs, const JpegIvDesc* __restrict__ ivs,
+                                                    uint8_t* __restrict__ ws, int32_t* __restrict__ status) {
+    const int lane = (int)threadIdx.x;
+    const JpegIvDesc iv = ivs[blockIdx.x];
+    const JpegSegDesc D = segs[iv.seg];
+    const int32_t c = (int32_t)blockIdx.y;
+    if (c >= D.ncomp) return;
+    const int32_t hs = D.ncomp == 1 ? 1 : D.hs, vs = D.ncomp == 1 ? 1 : D.vs;
+    int16_t* coef = reinterpret_cast<int16_t*>(ws + D.coef_off);
+    const uint32_t n = iv.n_mcu * (c == 0 ? (uint32_t)(hs * vs) : 1u);
+    int64_t carry = 0;
+    bool bad = false;
+    for (uint32_t t0 = 0; t0 < n; t0 += 64u) {
+        const uint32_t t = t0 + (uint32_t)lane;
+        int16_t* dc = nullptr;
+        int32_t d = 0;
+        if (t < n) {
+            dc = coef + (size_t)64 * (size_t)jpeg_block_of_comp(t, c, iv.first_mcu, hs, vs, D.mcux, D.mcuy);
+            d = *dc;
+        }
+        const int32_t incl = (int32_t)wave_incl_scan((uint32_t)d, lane);
+        const int64_t v = carry + incl;
+        if (dc) {
+            if (v < -2048 || v > 2047) bad = true;
+            else *dc = (int16_t)v;
+        }
+        carry += (int32_t)lane_value((uint32_t)incl, 63u);
+    }
+    if (bad) status[iv.seg] = OMR_INTERNAL;
+}
+
 // K17b: block t of segment blockIdx.y (+ k * gridDim.y).
 __global__ void __launch_bounds__(64) k_jpeg_idct(const JpegSegDesc* __restrict__ segs, int32_t n_seg,
                                                   const JpegTables* __restrict__ tables, uint8_t* __restrict__ ws) {
@@ -245,12 +388,23 @@ __global__ void __launch_bounds__(256) k_jpeg_pixels(const JpegSegDesc* __restri
 
 omr_status launch_jpeg_decode(Ctx* ctx, const uint8_t* src, const JpegSegDesc* segs, int32_t n_seg, const JpegIvDesc* ivs,
                               int32_t n_iv, const JpegTables* tables, uint8_t* ws, uint8_t* dst, int32_t* status,
-                              int32_t max_blocks, int64_t max_pixels) {
+                              int32_t max_blocks, int64_t max_pixels, int32_t n_split, uint32_t split_bits) {
     if (n_seg <= 0) return OMR_OK;
     const unsigned gy = (unsigned)std::min(n_seg, 65535);
     if (n_iv > 0) {
         KernelTimer timer(ctx, kKindJpegEntropy, true);
         omr_launch(k_jpeg_entropy, dim3((unsigned)n_iv), dim3(64), 0u, ctx->stream, src, segs, ivs, tables, ws, status);
+        OMR_HIP(ctx, hipGetLastError());
+    }
+    if (n_split > 0) {
+        {
+            KernelTimer timer(ctx, kKindJpegSplit, true);
+            omr_launch(k_jpeg_entropy_split, dim3((unsigned)n_split), dim3(kJpegSplitLanes), 0u, ctx->stream, src, segs, ivs + n_iv,
+                       tables, ws, status, split_bits);
+            OMR_HIP(ctx, hipGetLastError());
+        }
+        KernelTimer timer(ctx, kKindJpegDcSum, true);
+        omr_launch(k_jpeg_dc_sum, dim3((unsigned)n_split, 3u), dim3(64), 0u, ctx->stream, segs, ivs + n_iv, ws, status);
         OMR_HIP(ctx, hipGetLastError());
     }
     {
@@ -306,7 +460,16 @@ omr_status jpeg_decode_group(Ctx* ctx, SegPipe* T, const std::vector<JpegJob>& j
     uint8_t* dtab = static_cast<uint8_t*>(T->d_tab);
     JpegSegDesc* hs = reinterpret_cast<JpegSegDesc*>(tab);
     JpegIvDesc* hi = reinterpret_cast<JpegIvDesc*>(tab + o_iv);
-    size_t ws_bytes = 0, iv_at = 0;
+    // The intervals in two lists, K17a's in front of K18's: one of at least ctx->jpeg_split_min bytes
+    // takes the split decode (off by default: then the second list is empty and nothing changes).
+    const uint32_t split_min = ctx->jpeg_split_min;
+    const uint32_t split_bits = ctx->jpeg_split_bits ? ctx->jpeg_split_bits : kJpegSplitDefaultBits;
+    auto splits = [&](const JpegInterval& iv) { return split_min && iv.len >= split_min && iv.len < kJpegSplitMaxLen; };
+    size_t n_split = 0;
+    for (size_t j = 0; j < m; ++j)
+        for (const JpegInterval& iv : plans[(size_t)live[j]].intervals) n_split += splits(iv);
+    size_t ws_bytes = 0, iv_at = 0, split_at = n_iv - n_split;
+    size_t zero_lo = 0, zero_hi = 0;                       // the workspace from the first to the last segment K18 touches
     int32_t max_blocks = 0;
     int64_t max_pixels = 0;
     for (size_t j = 0; j < m; ++j) {
@@ -324,8 +487,14 @@ omr_status jpeg_decode_group(Ctx* ctx, SegPipe* T, const std::vector<JpegJob>& j
         S.pad = 0;
         max_blocks = std::max(max_blocks, jpeg_total_blocks(P.ncomp, P.hs, P.vs, P.mcux, P.mcuy));
         max_pixels = std::max(max_pixels, (int64_t)P.w * P.h);
-        for (const JpegInterval& iv : P.intervals)
-            hi[iv_at++] = {J.in_off + iv.off, (uint32_t)iv.len, (uint32_t)j, iv.first_mcu, iv.n_mcu};
+        for (const JpegInterval& iv : P.intervals) {
+            const bool sp = splits(iv);
+            hi[sp ? split_at++ : iv_at++] = {J.in_off + iv.off, (uint32_t)iv.len, (uint32_t)j, iv.first_mcu, iv.n_mcu};
+            if (sp) {
+                if (zero_hi == 0) zero_lo = S.coef_off;
+                zero_hi = S.plane_off;
+            }
+        }
     }
     for (size_t s = 0; s < sets.size(); ++s)
         std::memcpy(tab + o_tab + s * sizeof(JpegTables), &plans[(size_t)live[(size_t)sets[s]]].tables, sizeof(JpegTables));
@@ -333,10 +502,12 @@ omr_status jpeg_decode_group(Ctx* ctx, SegPipe* T, const std::vector<JpegJob>& j
     st = grow_device(ctx, T->d_coef, T->coef_cap, ws_bytes);
     if (st) return st;
     OMR_HIP(ctx, hipMemcpyAsync(dtab, tab, total, hipMemcpyHostToDevice, ctx->stream));
+    // K18a stores only what is not zero (the planes between two coefficient areas are zeroed along: one call)
+    if (n_split) OMR_HIP(ctx, hipMemsetAsync(static_cast<uint8_t*>(T->d_coef) + zero_lo, 0, zero_hi - zero_lo, ctx->stream));
     st = launch_jpeg_decode(ctx, d_src, reinterpret_cast<const JpegSegDesc*>(dtab), (int32_t)m,
-                            reinterpret_cast<const JpegIvDesc*>(dtab + o_iv), (int32_t)n_iv,
+                            reinterpret_cast<const JpegIvDesc*>(dtab + o_iv), (int32_t)(n_iv - n_split),
                             reinterpret_cast<const JpegTables*>(dtab + o_tab), static_cast<uint8_t*>(T->d_coef), d_dst,
-                            reinterpret_cast<int32_t*>(dtab + o_status), max_blocks, max_pixels);
+                            reinterpret_cast<int32_t*>(dtab + o_status), max_blocks, max_pixels, (int32_t)n_split, split_bits);
     if (st) return st;
     T->jpeg_status_off = o_status;
     T->jpeg_live = live;

@@ -16,8 +16,8 @@ from . import _lib
 from ._lib import OmrError
 from .context import Context, pyramid_level_count, pyramid_level_sizes, thumbnail_size
 from .pixbuf import PixelBuffer, write_pyramid, write_romio
-from .tiffimage import (TiffImage, jpeg_decode_batch_device, jpeg_decode_host, jpeg_stream_forms, lzw_decode_host,
-                        lzw_encode, write_tiled_tiff)
+from .tiffimage import (TiffImage, jpeg_decode_batch_device, jpeg_decode_host, jpeg_decode_host_split, jpeg_stream_forms,
+                        lzw_decode_host, lzw_encode, write_tiled_tiff)
 from .zarrimage import (ZarrImage, blosc_decode_host, blosc_encode, inflate_host, lz4_decode_host, lz4_encode,
                         write_zarr, zstd_decode_host, zstd_encode, zstd_frame_forms)
 from .batcher import Batcher, Pool
@@ -77,6 +77,6 @@ __all__ = ["_lib", "OmrError", "Context", "Renderer", "histogram_bin_of", "histo
            "ImageRegionRequestHandler", "InMemoryPixelBuffer", "LutProvider", "RequestError",
            "ShapeMaskCtx", "ShapeMaskRequestHandler", "PixelBuffer", "write_romio", "write_pyramid", "Batcher", "Pool",
            "TiffImage", "write_tiled_tiff", "lzw_encode", "lzw_decode_host", "jpeg_decode_host", "jpeg_stream_forms",
-           "jpeg_decode_batch_device",
+           "jpeg_decode_batch_device", "jpeg_decode_host_split",
            "ZarrImage", "write_zarr", "inflate_host", "lz4_encode", "lz4_decode_host", "blosc_encode",
            "blosc_decode_host", "zstd_encode", "zstd_decode_host", "zstd_frame_forms"]

@@ -118,6 +118,14 @@ class TiffOpenOptions(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("accept", ctypes.c_uint32)]
 
 
+class JpegSplitOptions(ctypes.Structure):                   # omr_jpeg_split_options (K18)
+    _fields_ = [("struct_size", ctypes.c_uint32), ("min_interval_bytes", ctypes.c_uint32), ("subsequence_bits", ctypes.c_uint32)]
+
+
+class JpegSplitStats(ctypes.Structure):                     # omr_jpeg_split_stats
+    _fields_ = [(n, ctypes.c_uint32) for n in ("subsequences", "rounds", "max_settle_iterations", "redecodes")]
+
+
 class ZarrInfo(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in (
         "size_x", "size_y", "size_z", "size_c", "size_t", "pixel_type", "big_endian", "n_levels", "compression",
@@ -341,6 +349,8 @@ _SIGS = {
     "omr_zstd_decode_batch_device": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
     "omr_jpeg_decode_host": (_i32, [_vp, _sz, _vp, _sz, _i32, _i32, _i32, _i32, _vp, _vp, _sz]),
     "omr_jpeg_stream_forms": (_i32, [_vp, _sz, _vp, _sz, ctypes.POINTER(ctypes.c_uint32)]),
+    "omr_ctx_set_jpeg_split": (_i32, [_vp, _vp]),
+    "omr_jpeg_decode_host_split": (_i32, [_vp, _sz, _vp, _sz, _i32, _i32, _i32, _i32, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp]),
     "omr_jpeg_decode_batch_device": (_i32, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "omr_render_shape_mask_png_batch": (_i32, [_vp, ctypes.POINTER(MaskJob), _i32, _vp, _sz, _vp, _vp, _vp]),
     "omr_split_html_color": (_i32, [ctypes.c_char_p, ctypes.POINTER(_i32)]),

@@ -172,13 +172,25 @@ class Context:
     def semantics(self):
         return int(lib.omr_ctx_get_semantics(self.h))
 
+    def set_jpeg_split(self, min_interval_bytes, subsequence_bits=0):
+        """K18 (omr_ctx_set_jpeg_split): JPEG restart intervals of at least min_interval_bytes
+        entropy-coded bytes are decoded by a whole workgroup in subsequences of subsequence_bits bits
+        (0: the library's default) in later TIFF reads, renders and jpeg_decode_batch_device calls on
+        this context.  min_interval_bytes = 0 or None: off, the default."""
+        if not min_interval_bytes:
+            check(lib.omr_ctx_set_jpeg_split(self.h, None), self.h)
+            return
+        opt = _lib.JpegSplitOptions(ctypes.sizeof(_lib.JpegSplitOptions), int(min_interval_bytes), int(subsequence_bits))
+        check(lib.omr_ctx_set_jpeg_split(self.h, ctypes.byref(opt)), self.h)
+
     def enable_kernel_timing(self, enable=True):
         check(lib.omr_ctx_enable_kernel_timing(self.h, int(enable)), self.h)
 
     def kernel_timings(self, cap=1 << 16):
         """[(ms, kind)] of the timed hot-kernel launches since the last call (kind 2 render,
         3 projection, 4 jpeg, 10 fused scaled render, 11 ARGB scaler, 12 pyramid levels, 20..26 the
-        batched PNG stages, 27 the grey wave filter, 30 LZW decode, 31 TIFF place); synchronises the stream."""
+        batched PNG stages, 27 the grey wave filter, 30 LZW decode, 31 TIFF place, 36..38 the JPEG decode,
+        39 and 40 its split entropy decode and DC sums; omr.h has the whole list); synchronises the stream."""
         ms = np.zeros(cap, np.float32)
         kind = np.zeros(cap, np.int32)
         n = lib.omr_ctx_kernel_timings(self.h, ms.ctypes.data, kind.ctypes.data, cap)

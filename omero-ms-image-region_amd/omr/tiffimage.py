@@ -467,6 +467,25 @@ def jpeg_decode_host(stream, width, height, samples=1, ycbcr=False, tables=None)
     return out.reshape(height, width) if samples == 1 else out.reshape(height, width, samples)
 
 
+def jpeg_decode_host_split(stream, width, height, samples=1, ycbcr=False, tables=None, subsequence_bits=1024, lanes=256):
+    """jpeg_decode_host with the entropy decode done as K18 does it (omr_jpeg_decode_host_split): a
+    workgroup of `lanes` lanes over subsequences of subsequence_bits bits, played by host loops.
+    Returns (pixels, stats): the pixels and errors of jpeg_decode_host, and a dict with the
+    subsequences, rounds, max_settle_iterations and redecodes of the decode."""
+    src = np.frombuffer(bytes(stream), dtype=np.uint8)
+    tab = np.frombuffer(bytes(tables or b""), dtype=np.uint8)
+    out = np.zeros(max(int(width) * int(height) * int(samples), 1), dtype=np.uint8)
+    stats = _lib.JpegSplitStats()
+    st = lib.omr_jpeg_decode_host_split(tab.ctypes.data if tab.size else None, tab.size, src.ctypes.data if src.size else None,
+                                        src.size, int(width), int(height), int(samples), int(bool(ycbcr)),
+                                        int(subsequence_bits), int(lanes), out.ctypes.data, ctypes.byref(stats))
+    if st != _lib.OK:
+        raise _lib.OmrError(st, "jpeg: split decode failed")
+    out = out[:int(width) * int(height) * int(samples)]
+    px = out.reshape(height, width) if samples == 1 else out.reshape(height, width, samples)
+    return px, {f: int(getattr(stats, f)) for f, _ in _lib.JpegSplitStats._fields_}
+
+
 def jpeg_stream_forms(stream, tables=None):
     """The forms a good stream uses (omr_jpeg_stream_forms), as a set of names of _lib.JPEG_FORM_NAMES."""
     src = np.frombuffer(bytes(stream), dtype=np.uint8)

@@ -17,6 +17,13 @@ not change them), so their renders must be equal; one region is also compared wi
 Needs Pillow to write the files.
 
     python3 tools/tiff_jpeg_probe.py --json profiles/k17/tiff_jpeg_probe.json
+
+With --split (K18) the two JPEG files are also served with the split entropy decode on every
+interval (39 K18a, 40 K18b in place of 36), at the default subsequence size and, for the file
+without restart markers, at those of --split-bits; the runs are named FILE+split and
+FILE+split_S<bits>, and all are compared with the first run's pixels.
+
+    python3 tools/tiff_jpeg_probe.py --split --json profiles/k18/tiff_jpeg_probe.json
 """
 import argparse
 import json
@@ -66,6 +73,8 @@ def main():
     ap.add_argument("--passes", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--cpu-only", action="store_true")
+    ap.add_argument("--split", action="store_true", help="also run the JPEG files with K18 (Context.set_jpeg_split) on every interval")
+    ap.add_argument("--split-bits", default="256,4096", help="with --split: further subsequence sizes for the file without restart markers")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
 
@@ -114,8 +123,13 @@ def main():
         accepts = {"rgb_deflate_256": ("deflate", "samples")}
         first = None
         with omr.Context(0) as ctx:
-            for key in ("rgb_jpeg_rst_256", "rgb_jpeg_256", "rgb_deflate_256"):
+            runs = [("rgb_jpeg_rst_256", None), ("rgb_jpeg_256", None), ("rgb_deflate_256", None)]
+            if args.split:                                   # K18 on every interval: the default S, and two others on the file it is for
+                runs[2:2] = [("rgb_jpeg_rst_256", 0), ("rgb_jpeg_256", 0)] + [("rgb_jpeg_256", int(b)) for b in args.split_bits.split(",") if b]
+            for key, split_bits in runs:
                 src = omr.TiffImage(paths[key], 1, 3, 1, accept=accepts.get(key, ("jpeg", "samples")))
+                ctx.set_jpeg_split(0 if split_bits is None else 1, split_bits or 0)
+                run_key = key if split_bits is None else key + "+split" + ("_S%d" % split_bits if split_bits else "")
                 walls, kinds = [], {}
                 ctx.enable_kernel_timing(True)
                 for p in range(args.warmup + args.passes):
@@ -134,24 +148,30 @@ def main():
                 ctx.enable_kernel_timing(False)
                 run = {"requests": len(positions), "wall_s": series(walls),
                        "region_gb_per_s_wall": region_bytes / statistics.median(walls) / 1e9}
-                for name, kind in (("k17a_entropy", 36), ("k17b_idct", 37), ("k17c_pixels", 38), ("k14a_inflate", 32),
-                                   ("k13b_place", 31), ("k2_render", 2)):
+                for name, kind in (("k17a_entropy", 36), ("k18a_entropy_split", 39), ("k18b_dc_sum", 40), ("k17b_idct", 37),
+                                   ("k17c_pixels", 38), ("k14a_inflate", 32), ("k13b_place", 31), ("k2_render", 2)):
                     if kind in kinds:
                         run[name + "_ms_per_pass"] = series(kinds[kind])
                         run[name + "_region_gb_per_s"] = region_bytes / (statistics.median(kinds[kind]) / 1e3) / 1e9
-                if 36 in kinds:
-                    k17 = [a + b + c for a, b, c in zip(kinds[36], kinds[37], kinds[38])]
-                    run["k17_abc_ms_per_pass"] = series(k17)
-                    run["k17_abc_region_gb_per_s"] = region_bytes / (statistics.median(k17) / 1e3) / 1e9
+                if 36 in kinds or 39 in kinds:
+                    if 36 in kinds:
+                        k17 = [a + b + c for a, b, c in zip(kinds[36], kinds[37], kinds[38])]
+                        run["k17_abc_ms_per_pass"] = series(k17)
+                        run["k17_abc_region_gb_per_s"] = region_bytes / (statistics.median(k17) / 1e3) / 1e9
+                    else:
+                        k18 = [a + b + c + d for a, b, c, d in zip(kinds[39], kinds[40], kinds[37], kinds[38])]
+                        run["k18_ab_k17_bc_ms_per_pass"] = series(k18)
+                        run["k18_ab_k17_bc_region_gb_per_s"] = region_bytes / (statistics.median(k18) / 1e3) / 1e9
                     got = out[:8].cpu().numpy()
                     if first is None:
                         first = got
                     run["equals_rgb_jpeg_rst"] = bool(np.array_equal(got, first))
                     dev = src.read_regions(ctx, 0, [(0, 1, 0, 300, 500)], 700, 300).cpu().numpy()[0, :700 * 300]
                     run["read_regions_equals_get_tile"] = bool(dev.tobytes() == src.get_tile(0, 0, 1, 0, 300, 500, 700, 300).tobytes())
-                result["runs"][key] = run
+                result["runs"][run_key] = run
                 src.close()
-                print(key, json.dumps(run), flush=True)
+                print(run_key, json.dumps(run), flush=True)
+            ctx.set_jpeg_split(0)
     for p in paths.values():
         os.unlink(p)
     os.rmdir(tmp)
