@@ -132,7 +132,10 @@ void*       omr_ctx_get_stream(omr_ctx* ctx);
  * Blosc-Zstd or zstd image; 36 = JPEG entropy decode, 37 = JPEG IDCT and 38 = JPEG upsample /
  * colour / store: omr_jpeg_decode_batch_device and, in front of 31,
  * omr_tiff_image_read_regions_device on a JPEG image; 39 = split JPEG entropy decode and 40 = its
- * DC sums, in place of or beside 36 after omr_ctx_set_jpeg_split).
+ * DC sums, in place of or beside 36 after omr_ctx_set_jpeg_split; 41 = JPEG 2000 code-block
+ * decode, 42 = one level of the inverse 5/3 transform and 43 = JPEG 2000 colour / level shift /
+ * store: omr_j2k_decode_batch_device and, in front of 31, omr_tiff_image_read_regions_device on a
+ * JPEG 2000 image).
  */
 omr_status  omr_ctx_enable_kernel_timing(omr_ctx* ctx, int32_t enable);
 int32_t     omr_ctx_kernel_timings(omr_ctx* ctx, float* ms_out, int32_t* kind_out, int32_t cap);
@@ -1078,6 +1081,7 @@ omr_status omr_tiff_image_open(const char* path, int32_t size_z, int32_t size_c,
 #define OMR_TIFF_ACCEPT_ZSTD       2u   /* Compression 50000: one Zstandard frame per segment     */
 #define OMR_TIFF_ACCEPT_PREDICTOR3 4u   /* floating-point predictor, float and double samples     */
 #define OMR_TIFF_ACCEPT_SAMPLES    8u   /* SamplesPerPixel 2..4, PlanarConfiguration 1 (chunky)   */
+/* (16: OMR_TIFF_ACCEPT_JPEG, K17; 32: OMR_TIFF_ACCEPT_JPEG2000, K19 -- both further down) */
 typedef struct omr_tiff_open_options {
     uint32_t struct_size;                              /* sizeof(omr_tiff_open_options) */
     uint32_t accept;                                   /* OMR_TIFF_ACCEPT_* bits */
@@ -1474,6 +1478,92 @@ omr_status omr_jpeg_decode_host_split(const uint8_t* tables, size_t tables_lengt
                                       int32_t width, int32_t height, int32_t samples, int32_t ycbcr,
                                       uint32_t subsequence_bits, uint32_t lanes, uint8_t* dst,
                                       omr_jpeg_split_stats* stats);
+
+/* ---- K19: JPEG 2000 TIFF segments (Compression 33003, 33004, 33005, 34712), the reversible path ----
+ *
+ * OMR_TIFF_ACCEPT_JPEG2000 in omr_tiff_image_open_ex admits Compression 33003, 33004 and 33005
+ * (Aperio's and Bio-Formats' numbers, as recalled) and 34712 (the registered one): every segment is
+ * one raw JPEG 2000 codestream that starts with SOC (FF 4F).  omr_tiff_image_open and an open_ex
+ * without the bit refuse them as before.  TIFF forms: Predictor 1, SampleFormat 1, tiles or strips,
+ * BitsPerSample 8 with SamplesPerPixel 1 (Photometric 0 or 1) or 3 (Photometric 2; needs
+ * OMR_TIFF_ACCEPT_SAMPLES), or BitsPerSample 16 with SamplesPerPixel 1.  The image then behaves like
+ * a Deflate file of the same sample type (info.compression reads 34712 for all four numbers):
+ * get_tile decodes on the host, read_regions_device and omr_render_tiff_tiles on the device, a
+ * segment once per call, 16-bit samples stored in the file's byte order.
+ *
+ * Codestream forms accepted: one tile that covers the image, one tile-part, image and tile offsets
+ * 0; 1 or 3 unsigned components of a precision equal to BitsPerSample, no subsampling; the
+ * reversible 5/3 transform with QCD style 0 (no quantisation), and the reversible colour transform
+ * when COD's MCT byte is 1; 0..32 decomposition levels; code-blocks of 4..1024 a side and at most
+ * 4096 samples; user precincts; 1..65535 quality layers; the progression orders LRCP, RLCP, RPCL,
+ * PCRL, CPRL; COM (and TLM, PLM, PLT, CRG) skipped; at most 30 magnitude bit-planes per subband
+ * (guard bits + exponent - 1).  A stream truncated by its encoder (fewer coding passes than its
+ * bit-planes hold) is reconstructed at the mid-point of what is left open, as OpenJPEG does
+ * (csrc/omr_j2kdec.h states the rule).  Pinned byte for byte against OpenJPEG, through Pillow, by
+ * tests/golden/tiff_j2k.npz.
+ *
+ * OMR_INVALID_ARGUMENT, the message naming the form: the irreversible 9/7 transform and
+ * quantisation styles 1 and 2; any code-block style bit (bypass, reset, termination on each pass,
+ * vertically causal, predictable termination, segmentation symbols); SOP or EPH; COC, QCC, RGN,
+ * POC, PPM, PPT; several tiles or tile-parts; non-zero offsets; subsampled or signed components; a
+ * precision other than 8 or 16; a JP2 box wrapper; 16-bit with three samples.  OMR_INTERNAL
+ * (damage): a stream cut inside a marker segment or a packet header, a packet body that runs past
+ * the tile-part, more coding passes than 3 * (M_b - zero bit-planes) - 2, more zero bit-planes than
+ * M_b, a frame size other than the segment's, no EOC.  A damaged packet BODY cannot be detected
+ * without the termination styles that are refused: it decodes to defined, in-bounds garbage with
+ * OMR_OK, the same garbage on the host and on the device.
+ */
+#define OMR_TIFF_ACCEPT_JPEG2000 32u   /* Compression 33003, 33004, 33005, 34712: one reversible JPEG 2000 codestream per segment */
+/*
+ * The host decoder alone (get_tile's): src a raw codestream whose frame must be width x height
+ * with `samples` components (1 or 3) of `bits` bits (8 or 16; 16 with one sample only), decoded to
+ * dst as chunky samples, 16-bit ones in the host's byte order (dst then 2-byte aligned).  Code-blocks
+ * go to 16 threads from 65536 samples on.  why (may be NULL): the reason of a failure, cut to why_cap.
+ */
+omr_status omr_j2k_decode_host(const uint8_t* src, size_t length, int32_t width, int32_t height, int32_t samples,
+                               int32_t bits, uint8_t* dst, char* why, size_t why_cap);
+/* The coding forms a good stream uses, bit f of *forms for form f: what the fixture is measured by. */
+enum {
+    OMR_J2K_FORM_ZC0 = 0,          /* .. 8: the nine zero-coding contexts */
+    OMR_J2K_FORM_SC9 = 9,          /* sign context 9 (it has no flip) */
+    OMR_J2K_FORM_SC10 = 10,        /* .. 17: sign contexts 10..13, each without (even bit) and with the XOR flip */
+    OMR_J2K_FORM_MR14 = 18,        /* .. 20: the refinement contexts 14, 15, 16 */
+    OMR_J2K_FORM_RUN_TAKEN = 21,   /* a run of four zeros coded as one decision */
+    OMR_J2K_FORM_RUN_BROKEN = 22,  /* a run broken, its place by the UNIFORM context */
+    OMR_J2K_FORM_MPS_EXCHANGE = 23,
+    OMR_J2K_FORM_LPS_EXCHANGE = 24,
+    OMR_J2K_FORM_FF_BODY = 25,     /* an FF byte inside a code-block's bytes */
+    OMR_J2K_FORM_FF_HEADER = 26,   /* an FF byte (and its stuffed bit) inside a packet header */
+    OMR_J2K_FORM_PASSES_1 = 27,    /* the pass-count codewords: 1, 2, 3..5, 6..36, 37..164 */
+    OMR_J2K_FORM_PASSES_2,
+    OMR_J2K_FORM_PASSES_3_5,
+    OMR_J2K_FORM_PASSES_6_36,
+    OMR_J2K_FORM_PASSES_37_164,
+    OMR_J2K_FORM_LBLOCK,           /* an Lblock increment */
+    OMR_J2K_FORM_TAG_TREE_DEEP,    /* a tag tree of more than one level */
+    OMR_J2K_FORM_LATE_INCLUSION,   /* a code-block absent from the first layer and included later */
+    OMR_J2K_FORM_ZERO_BIT_PLANES,  /* a code-block with missing bit-planes */
+    OMR_J2K_FORM_PARTIAL_BLOCK,    /* a code-block cut by its subband's or precinct's edge */
+    OMR_J2K_FORM_RCT,
+    OMR_J2K_FORM_BITS16,
+    OMR_J2K_FORM_COUNT
+};
+omr_status omr_j2k_stream_forms(const uint8_t* src, size_t length, uint64_t* forms);
+/*
+ * K19 alone: n codestreams in HOST memory (headers and packets are walked on the host, as in
+ * omr_tiff_image_read_regions_device), stream i = lengths[i] bytes at src + offsets[i] with a frame
+ * of widths[i] x heights[i], `samples` components and `bits` bits, decoded on the device into d_dst
+ * + dst_offsets[i] as chunky samples (16-bit ones little-endian, dst_offsets then even; nothing is
+ * written behind them).  The arrays and status are host arrays; status[i] = OMR_OK,
+ * OMR_INVALID_ARGUMENT or OMR_INTERNAL by the rule of omr_j2k_decode_host, one stream's failure
+ * leaving the others alone.  Synchronous.  omr_ctx_kernel_timings reports kind 41 (K19a, one launch:
+ * the code-blocks), 42 (K19b, one launch per decomposition level of the deepest stream) and 43
+ * (K19c, one launch: colour, level shift, clamp, store); omr_tiff_image_read_regions_device on a
+ * JPEG 2000 image reports them in front of 31.
+ */
+omr_status omr_j2k_decode_batch_device(omr_ctx* ctx, const uint8_t* src, const uint64_t* offsets, const uint32_t* lengths,
+                                       const int32_t* widths, const int32_t* heights, int32_t n, int32_t samples,
+                                       int32_t bits, uint8_t* d_dst, const uint64_t* dst_offsets, int32_t* status);
 
 #ifdef __cplusplus
 }

@@ -2,10 +2,12 @@
 // of a context and its growth, one group of regions from plan to status scan (the run stage with
 // the decoder of the source's codec: K13a, K14a or K16a, then K13b; Blosc chunks through their own
 // finish: container parsing, K15a and K16a side by side, K15b; JPEG segments through theirs: header
-// parsing, K17a .. K17c, K13b), the group loop and the tile renderer.  Every HIP call of the two
-// readers is in this file, but for the JPEG group's table upload and launches (omr_jpegdec.hip).
+// parsing, K17a .. K17c, K13b; JPEG 2000 segments through theirs: headers and packets, K19a .. K19c,
+// K13b), the group loop and the tile renderer.  Every HIP call of the two readers is in this file,
+// but for the JPEG and JPEG 2000 groups' table uploads and launches (omr_jpegdec.hip, omr_j2kdec.hip).
 #include "omr_segread.h"
 
+#include "omr_j2kdec.h"
 #include "omr_jpegdec.h"
 
 namespace omr {
@@ -172,6 +174,52 @@ omr_status finish_jpeg(Ctx* ctx, SegPipe* T, SegSource& S, SegPlan& plan, const 
     return OMR_OK;
 }
 
+// The JPEG 2000 half of read_group, from the segments' bytes in pinned memory on (K19).  While they
+// are there the host parses every segment's headers and walks its packets (j2k_prepare; a segment
+// it refuses ends the call before any launch: all the damage that can be seen is seen there).  The
+// bytes and the placements go up in the staging copy, the code-block descriptors behind them in a
+// copy of their own; K19a .. K19c decode into the segments' scratch as chunky samples in the file's
+// byte order and K13b places them as it places a Deflate segment of the same sample type.
+omr_status finish_j2k(Ctx* ctx, SegPipe* T, SegSource& S, SegPlan& plan, const std::vector<SegBytes>& segs, size_t in_bytes) {
+    uint8_t* pin = static_cast<uint8_t*>(T->pin);
+    uint8_t* din = static_cast<uint8_t*>(T->d_in);
+    uint8_t* dscr = static_cast<uint8_t*>(T->d_scratch);
+    std::vector<int32_t> coded;
+    for (size_t k = 0; k < segs.size(); ++k)
+        if (segs[k].cnt) coded.push_back((int32_t)k);
+    const size_t m = coded.size();
+    std::vector<J2kJob> jobs(m);
+    std::vector<J2kPlan> plans(m);
+    std::vector<std::string> why(m);
+    const int32_t spp = S.geom.spp, bits = 8 * S.geom.bpp;
+    parallel_for((int)m, in_bytes > ((size_t)1 << 18), [&](int j) {
+        const SegBytes& u = segs[(size_t)coded[(size_t)j]];
+        const int32_t rows = (int32_t)(u.expected / ((uint32_t)S.geom.seg_w * (uint32_t)spp * (uint32_t)S.geom.bpp));
+        jobs[(size_t)j].in_off = u.in_off;
+        jobs[(size_t)j].dst_off = u.scratch_off;
+        jobs[(size_t)j].parsed = j2k_prepare(pin + u.in_off, (size_t)u.cnt, S.geom.seg_w, rows, spp, bits, plans[(size_t)j], &why[(size_t)j]);
+    });
+    for (size_t j = 0; j < m; ++j)
+        if (jobs[j].parsed == OMR_INVALID_ARGUMENT) return fail(ctx, OMR_INVALID_ARGUMENT, said(S, "unsupported JPEG 2000 segment: ") + why[j]);
+        else if (jobs[j].parsed) return fail(ctx, OMR_INTERNAL, said(S, "corrupt JPEG 2000 ") + S.noun + " (" + why[j] + ")");
+    const size_t place_at = align_up(in_bytes, 256), place_bytes = plan.places.size() * sizeof(TiffPlace);
+    TiffPlace* h_place = reinterpret_cast<TiffPlace*>(pin + place_at);
+    for (size_t k = 0; k < plan.places.size(); ++k) {
+        const SegBytes& u = segs[(size_t)plan.place_seg[k]];
+        plan.places[k].src = !u.cnt ? nullptr : dscr + u.scratch_off;
+        h_place[k] = plan.places[k];
+    }
+    OMR_HIP(ctx, hipMemcpyAsync(din, pin, place_at + place_bytes, hipMemcpyHostToDevice, ctx->stream));
+    std::vector<int32_t> status;
+    omr_status st = j2k_decode_group(ctx, T, jobs, plans, S.swap, din, dscr, status);
+    if (st) return st;
+    st = launch_tiff_place(ctx, reinterpret_cast<const TiffPlace*>(din + place_at), (int32_t)plan.places.size(), plan.max_rows,
+                           S.geom.bpp, 1, false, S.geom.spp);
+    if (st) return st;
+    OMR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return OMR_OK;
+}
+
 // One group of regions: reqs[r0, r1).
 omr_status read_group(Ctx* ctx, SegSource& S, const omr_raw_tile_request* reqs, int32_t r0, int32_t r1, int32_t width,
                       int32_t height, uint8_t* d_dst, int64_t stride) {
@@ -210,6 +258,7 @@ omr_status read_group(Ctx* ctx, SegSource& S, const omr_raw_tile_request* reqs, 
     if (!S.read(plan.segs, segs, pin, in_bytes)) return fail(ctx, OMR_INTERNAL, said(S, S.noun) + " read failed");
     if (blosc) return finish_blosc(ctx, T, S, plan, segs, in_bytes);
     if (S.codec == SegCodec::jpeg) return finish_jpeg(ctx, T, S, plan, segs, in_bytes);
+    if (S.codec == SegCodec::j2k) return finish_j2k(ctx, T, S, plan, segs, in_bytes);
     for (size_t j = 0; j < m; ++j) {
         const SegBytes& u = segs[(size_t)coded[j]];
         t.off(pin)[j] = u.in_off;
@@ -256,6 +305,7 @@ omr_status read_regions(Ctx* ctx, SegSource& src, const omr_raw_tile_request* re
     OMR_HIP(ctx, hipSetDevice(ctx->device));
     size_t per_req = read_bytes_per_request(src.geom, width, height);
     if (src.codec == SegCodec::jpeg) per_req += jpeg_workspace_per_request(src.geom, width, height);   // K17's coefficients and planes
+    if (src.codec == SegCodec::j2k) per_req += j2k_workspace_per_request(src.geom, width, height);     // K19's three planes
     const int32_t G = group_size(n, std::min(kGroupInBytes, kGroupScratchBytes), per_req);
     for (int32_t r0 = 0; r0 < n; r0 += G) {
         const omr_status st = read_group(ctx, src, reqs, r0, std::min(n, r0 + G), width, height,

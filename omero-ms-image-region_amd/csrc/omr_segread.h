@@ -41,7 +41,7 @@ struct SegPipe {
     size_t tab_cap = 0;
     void* d_lit = nullptr;       // K16a: one literal buffer per workgroup of its grid
     size_t lit_cap = 0;
-    void* d_coef = nullptr;      // K17: the JPEG segments' coefficients (int16) and sample planes
+    void* d_coef = nullptr;      // K17: the JPEG segments' coefficients (int16) and sample planes; K19: the JPEG 2000 segments' planes
     size_t coef_cap = 0;
     size_t jpeg_status_off = 0;  // of the group in flight: where its statuses are in pin_tab / d_tab,
     std::vector<int32_t> jpeg_live;   // and the jobs they belong to (jpeg_decode_group .. jpeg_group_statuses)
@@ -178,13 +178,22 @@ struct TableLayout {
 
 // ---- what a front-end supplies ------------------------------------------------------------------
 
-enum class SegCodec { none, lzw, zlib, zstd, blosc, jpeg };
+enum class SegCodec { none, lzw, zlib, zstd, blosc, jpeg, j2k };
 
 // What a read request of a JPEG level can need beside read_bytes_per_request: K17's workspace
 // (coefficients and sample planes) of the same segments, so that a group's workspace stays within
 // kGroupScratchBytes as its decoded bytes do.
 inline size_t jpeg_workspace_per_request(const SegGeom& g, int32_t width, int32_t height) {
     const size_t per_seg = (size_t)3 * g.spp * (((size_t)g.seg_w + 15) / 16 * 16) * (((size_t)g.seg_h + 15) / 16 * 16) + 512;
+    return (size_t)((width - 1) / g.seg_w + 2) * (size_t)((height - 1) / g.seg_h + 2) * per_seg;
+}
+
+// The same for a JPEG 2000 level: K19's workspace of 4 bytes per coefficient, three times -- the
+// subbands as K19a leaves them and the two planes K19b's levels alternate between, the second of a
+// quarter of the size (J2kSegDesc, omr_j2kdec.h).
+inline size_t j2k_workspace_per_request(const SegGeom& g, int32_t width, int32_t height) {
+    const size_t w = (size_t)g.seg_w, h = (size_t)g.seg_h;
+    const size_t per_seg = (size_t)4 * g.spp * (2 * w * h + ((w + 1) / 2) * ((h + 1) / 2)) + 768;
     return (size_t)((width - 1) / g.seg_w + 2) * (size_t)((height - 1) / g.seg_h + 2) * per_seg;
 }
 
@@ -236,6 +245,21 @@ struct JpegJob {
 omr_status jpeg_decode_group(Ctx* ctx, SegPipe* T, const std::vector<JpegJob>& jobs, const std::vector<JpegPlan>& plans,
                              int32_t samples, bool ycc, const uint8_t* d_src, uint8_t* d_dst, std::vector<int32_t>& status);
 omr_status jpeg_group_statuses(Ctx* ctx, SegPipe* T, std::vector<int32_t>& status);
+
+// ---- K19: one group of JPEG 2000 segments (omr_j2kdec.hip) ----------------------------------------
+
+struct J2kPlan;
+// One codestream: its bytes are at d_src + in_off, it decodes to d_dst + dst_off; parsed: what
+// j2k_prepare said of it (anything but OMR_OK: it is not decoded and that is its status).
+struct J2kJob {
+    uint64_t in_off = 0, dst_off = 0;
+    omr_status parsed = OMR_OK;
+};
+// The descriptor table of the jobs (plans[k]: job k's j2k_prepare) into T->pin_tab, up in one copy,
+// the workspace in T->d_coef, and K19a, K19b per level and K19c on the context's stream.  swap16:
+// 16-bit samples are stored byte-swapped.  status: the jobs' parsed; no kernel adds to it.
+omr_status j2k_decode_group(Ctx* ctx, SegPipe* T, const std::vector<J2kJob>& jobs, const std::vector<J2kPlan>& plans,
+                            bool swap16, const uint8_t* d_src, uint8_t* d_dst, std::vector<int32_t>& status);
 
 // Growth of a pipe's buffers (omr_segread.cpp): device memory, and a pinned buffer with its device
 // twin of at least `total` bytes (by half again when they grow); what: the words of the message.

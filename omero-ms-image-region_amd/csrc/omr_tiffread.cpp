@@ -10,12 +10,15 @@
 // use: Deflate and Zstandard segments (decoded on the host by omr_inflate_host and
 // omr_zstd_decode_host, on the device by K14a and K16a), the floating-point predictor and chunky
 // pixels of 2..4 samples, of which a read takes one, and baseline JPEG segments (Compression 7 with
-// the JPEGTables of tag 347; omr_jpeg_decode_host here, K17a .. K17c on the device: omr_jpegdec.*).
+// the JPEGTables of tag 347; omr_jpeg_decode_host here, K17a .. K17c on the device: omr_jpegdec.*)
+// and reversible JPEG 2000 codestreams (Compression 33003, 33004, 33005, 34712; omr_j2k_decode_host
+// here, K19a .. K19c on the device: omr_j2kdec.*).
 // The device route itself -- staging, planning,
 // K13a's and K13b's launches (omr_tiffread.hip), the tile renderer -- is omr_segread.cpp, shared
 // with the Zarr reader; this file calls no HIP function.
 #include "omr_segread.h"
 
+#include "omr_j2kdec.h"
 #include "omr_jpegdec.h"
 
 #include <fcntl.h>
@@ -244,6 +247,13 @@ omr_status take_ifd(const Parser& P, const Ifd& f, uint32_t accept, Level& L, Se
         ycc = f.photometric == 6;
         comp = 7;
         break;
+    case 33003: case 33004: case 33005: case 34712:      // one reversible JPEG 2000 codestream per segment (K19)
+        if (!(accept & OMR_TIFF_ACCEPT_JPEG2000)) return OMR_INVALID_ARGUMENT;
+        if (f.fmt != 1 || f.pred != 1 || f.mixed) return OMR_INVALID_ARGUMENT;
+        if (f.bps == 8 ? (f.spp == 1 ? f.photometric > 1 : f.spp != 3 || f.photometric != 2) : f.bps != 16 || f.spp != 1 || f.photometric > 1)
+            return OMR_INVALID_ARGUMENT;
+        comp = 34712;
+        break;
     default: return OMR_INVALID_ARGUMENT;
     }
     if (f.pred == 3) {                                   // float and double, one sample per pixel
@@ -471,6 +481,14 @@ omr_status load_segment(const omr_tiff_image* im, const Level& L, const Segments
             ok = st == OMR_OK;
             break;
         }
+        case 34712: {
+            const omr_status st = omr_j2k_decode_host(comp.data(), (size_t)cnt, L.seg_w, rows, im->spp, 8 * im->bpp, out.data(), nullptr, 0);
+            if (st == OMR_INVALID_ARGUMENT) return st;      // a valid form out of scope
+            ok = st == OMR_OK;
+            if (ok && im->bpp == 2 && im->big == host_little_endian())   // the decoder's samples are the host's: into the file's order
+                for (size_t k = 0; k + 1 < expected; k += 2) std::swap(out[k], out[k + 1]);
+            break;
+        }
         default: ok = false; break;
         }
         if (!ok) return OMR_INTERNAL;
@@ -503,6 +521,7 @@ struct TiffSource final : omr::SegSource {
         case 8: codec = omr::SegCodec::zlib; break;
         case 50000: codec = omr::SegCodec::zstd; break;
         case 7: codec = omr::SegCodec::jpeg; break;
+        case 34712: codec = omr::SegCodec::j2k; break;
         default: codec = omr::SegCodec::none; break;
         }
         predictor = im->predictor;
@@ -559,7 +578,7 @@ omr_status omr_tiff_image_open_ex(const char* path, int32_t size_z, int32_t size
         if (opt->struct_size < sizeof(omr_tiff_open_options)) return OMR_INVALID_ARGUMENT;
         accept = opt->accept;
         if (accept & ~(OMR_TIFF_ACCEPT_DEFLATE | OMR_TIFF_ACCEPT_ZSTD | OMR_TIFF_ACCEPT_PREDICTOR3 | OMR_TIFF_ACCEPT_SAMPLES |
-                       OMR_TIFF_ACCEPT_JPEG))
+                       OMR_TIFF_ACCEPT_JPEG | OMR_TIFF_ACCEPT_JPEG2000))
             return OMR_INVALID_ARGUMENT;
     }
     if (!path || !dimension_order || size_z <= 0 || size_c <= 0 || size_t_ <= 0) return OMR_INVALID_ARGUMENT;

@@ -6,7 +6,7 @@ Layers:
   renderer  Renderer facade mirroring the omeis Renderer calls the reference makes
             (ImageRegionRequestHandler.java:436-440, :689-741, :559)
   pixbuf    PixelBuffer: ROMIO repository pixel files (getPixelBuffer, :302-309)
-  tiffimage TiffImage: tiled TIFF / OME-TIFF pixel files, LZW, Deflate, zstd and JPEG decoded on the GPU; write_tiled_tiff
+  tiffimage TiffImage: tiled TIFF / OME-TIFF pixel files, LZW, Deflate, zstd, JPEG and reversible JPEG 2000 decoded on the GPU; write_tiled_tiff
   zarrimage ZarrImage: OME-Zarr pyramids, zlib, Blosc (LZ4 or Zstd inside) and zstd chunks decoded on the GPU; write_zarr
   batcher   Batcher: concurrent requests coalesced into GPU batches; Pool: one batcher per GPU
   request   ImageRegionCtx / ShapeMaskCtx parsing and the handler glue
@@ -16,8 +16,9 @@ from . import _lib
 from ._lib import OmrError
 from .context import Context, pyramid_level_count, pyramid_level_sizes, thumbnail_size
 from .pixbuf import PixelBuffer, write_pyramid, write_romio
-from .tiffimage import (TiffImage, jpeg_decode_batch_device, jpeg_decode_host, jpeg_decode_host_split, jpeg_stream_forms,
-                        lzw_decode_host, lzw_encode, write_tiled_tiff)
+from .tiffimage import (TiffImage, j2k_decode_batch_device, j2k_decode_host, j2k_stream_forms, jpeg_decode_batch_device,
+                        jpeg_decode_host, jpeg_decode_host_split, jpeg_stream_forms, lzw_decode_host, lzw_encode,
+                        write_tiled_tiff)
 from .zarrimage import (ZarrImage, blosc_decode_host, blosc_encode, inflate_host, lz4_decode_host, lz4_encode,
                         write_zarr, zstd_decode_host, zstd_encode, zstd_frame_forms)
 from .batcher import Batcher, Pool
@@ -77,6 +78,7 @@ __all__ = ["_lib", "OmrError", "Context", "Renderer", "histogram_bin_of", "histo
            "ImageRegionRequestHandler", "InMemoryPixelBuffer", "LutProvider", "RequestError",
            "ShapeMaskCtx", "ShapeMaskRequestHandler", "PixelBuffer", "write_romio", "write_pyramid", "Batcher", "Pool",
            "TiffImage", "write_tiled_tiff", "lzw_encode", "lzw_decode_host", "jpeg_decode_host", "jpeg_stream_forms",
-           "jpeg_decode_batch_device", "jpeg_decode_host_split",
+           "jpeg_decode_batch_device", "jpeg_decode_host_split", "j2k_decode_host", "j2k_stream_forms",
+           "j2k_decode_batch_device",
            "ZarrImage", "write_zarr", "inflate_host", "lz4_encode", "lz4_decode_host", "blosc_encode",
            "blosc_decode_host", "zstd_encode", "zstd_decode_host", "zstd_frame_forms"]

@@ -108,10 +108,19 @@ class TiffInfo(ctypes.Structure):
         "predictor", "tiled", "segment_width", "segment_height", "big_tiff")]
 
 
-TIFF_ACCEPT = {"deflate": 1, "zstd": 2, "predictor3": 4, "samples": 8, "jpeg": 16}    # OMR_TIFF_ACCEPT_*
+TIFF_ACCEPT = {"deflate": 1, "zstd": 2, "predictor3": 4, "samples": 8, "jpeg": 16, "jpeg2000": 32}    # OMR_TIFF_ACCEPT_*
 # OMR_JPEG_FORM_*: omr.jpeg_stream_forms returns the set of names, form f is bit f
 JPEG_FORM_NAMES = ("EOB_EARLY", "FULL_BLOCK", "ZRL", "LONG_CODE", "DC_CAT9", "STUFFED_FF", "RESTART", "PAD_BITS",
                    "TABLE_OVERRIDE", "MULTI_TABLE", "COM", "FILL_BYTES", "TABLES_STREAM")
+
+
+# OMR_J2K_FORM_*: omr.j2k_stream_forms returns the set of names, form f is bit f
+J2K_FORM_NAMES = (tuple("ZC%d" % k for k in range(9)) + ("SC9",) +
+                  tuple("SC%d%s" % (c, x) for c in (10, 11, 12, 13) for x in ("", "_XOR")) + ("MR14", "MR15", "MR16") +
+                  ("RUN_TAKEN", "RUN_BROKEN", "MPS_EXCHANGE", "LPS_EXCHANGE", "FF_BODY", "FF_HEADER", "PASSES_1", "PASSES_2",
+                   "PASSES_3_5", "PASSES_6_36", "PASSES_37_164", "LBLOCK", "TAG_TREE_DEEP", "LATE_INCLUSION",
+                   "ZERO_BIT_PLANES", "PARTIAL_BLOCK", "RCT", "BITS16"))
+J2K_COMPRESSIONS = (33003, 33004, 33005, 34712)             # the TIFF Compression numbers of a JPEG 2000 segment
 
 
 class TiffOpenOptions(ctypes.Structure):
@@ -352,6 +361,9 @@ _SIGS = {
     "omr_ctx_set_jpeg_split": (_i32, [_vp, _vp]),
     "omr_jpeg_decode_host_split": (_i32, [_vp, _sz, _vp, _sz, _i32, _i32, _i32, _i32, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp]),
     "omr_jpeg_decode_batch_device": (_i32, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "omr_j2k_decode_host": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _vp, _vp, _sz]),
+    "omr_j2k_stream_forms": (_i32, [_vp, _sz, ctypes.POINTER(ctypes.c_uint64)]),
+    "omr_j2k_decode_batch_device": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "omr_render_shape_mask_png_batch": (_i32, [_vp, ctypes.POINTER(MaskJob), _i32, _vp, _sz, _vp, _vp, _vp]),
     "omr_split_html_color": (_i32, [ctypes.c_char_p, ctypes.POINTER(_i32)]),
     "omr_shape_mask_fill_color": (_i32, [_i32, _i32, ctypes.c_char_p, _vp]),

@@ -7,7 +7,8 @@ SubIFDs.  Reads go through libomr.so: get_tile on the host (plain serial LZW dec
 and render_tiles with the LZW segments decoded on the GPU (omr_tiffread.hip).  With accept=...
 (omr_tiff_image_open_ex) also Deflate and zstd segments, the floating-point predictor and chunky
 pixels of several samples (RGB), each channel one sample, and with "jpeg" baseline JPEG segments
-(Compression 7, K17: omr_jpegdec.hip), grey, RGB or YCbCr converted to RGB.
+(Compression 7, K17: omr_jpegdec.hip), grey, RGB or YCbCr converted to RGB, and with "jpeg2000"
+reversible JPEG 2000 codestreams (Compression 33003, 33004, 33005, 34712, K19: omr_j2kdec.hip).
 """
 import ctypes
 import struct
@@ -137,6 +138,30 @@ def _jpeg_encode(seg, opt):
     return f.getvalue()
 
 
+def _j2k_encode(seg, opt):
+    """One segment ([rows][cols] uint8 or uint16, or [rows][cols][3] uint8) as a raw reversible JPEG 2000
+    codestream, by Pillow's OpenJPEG; opt: Pillow's save options (num_resolutions, codeblock_size,
+    precinct_size, quality_mode, quality_layers, progression, mct ...)."""
+    import io
+    from PIL import Image
+    kw = dict(opt)
+    kw.pop("rewrite", None)
+    kw.update(format="JPEG2000", no_jp2=True, irreversible=False)
+    f = io.BytesIO()
+    Image.fromarray(np.ascontiguousarray(seg)).save(f, **kw)
+    return f.getvalue()
+
+
+class _J2kJob:
+    """_j2k_encode with its options, picklable for a process pool's map."""
+
+    def __init__(self, opt):
+        self.opt = {k: v for k, v in opt.items() if k != "rewrite"}
+
+    def __call__(self, seg):
+        return _j2k_encode(seg, self.opt)
+
+
 def _zstd_job(raw):
     from .zarrimage import zstd_encode
     return zstd_encode(raw)
@@ -145,7 +170,7 @@ def _zstd_job(raw):
 def write_tiled_tiff(path, planes, levels=(), tile=(256, 256), rows_per_strip=None, byteorder="<", bigtiff=False,
                      compression=1, predictor=1, early_clear=0, eoi=True, dimension_order="XYZCT",
                      skip_zero_segments=False, tag_overrides=None, mapper=map, samples_per_pixel=1, encoder=None,
-                     jpeg=None):
+                     jpeg=None, jpeg2000=None):
     """Write a [t][c][z][y][x] array as a TIFF with one IFD per plane (in `dimension_order`), and
     `levels` (arrays of the same [t][c][z] with their own [y][x]) as SubIFDs of each plane.
     tile = (w, h), or rows_per_strip = n for strips; byteorder "<" (II) or ">" (MM); compression 1,
@@ -164,6 +189,12 @@ def write_tiled_tiff(path, planes, levels=(), tile=(256, 256), rows_per_strip=No
     "optimize": False, "photometric": "ycbcr" | "rgb" for three samples (a single sample is grey),
     "tables": "inline" (whole streams) | "shared" (the first segment's DQT / DHT in tag 347 and
     every marker segment equal to one of them cut out of the streams)}.
+    compression 33003, 33004, 33005 or 34712 (uint8 with one sample or three, uint16 with one):
+    one raw reversible JPEG 2000 codestream per segment, encoded by Pillow's OpenJPEG (a test and
+    tooling aid as well), edge tiles padded by edge replication and a last strip coded at its own
+    height; jpeg2000 = Pillow's save options ({"num_resolutions": 3, "codeblock_size": (16, 16),
+    "precinct_size": (32, 32), "quality_mode": "rates", "quality_layers": [8, 1], "progression":
+    "RPCL", "mct": 1 ...}) and "rewrite": a function stream -> stream.
     Returns {"ifds": [offset per plane], "subifds": [[offsets] per plane]}."""
     planes = np.asarray(planes)
     assert planes.ndim == 5, "planes must be [t][c][z][y][x]"
@@ -184,6 +215,11 @@ def write_tiled_tiff(path, planes, levels=(), tile=(256, 256), rows_per_strip=No
     if compression == 7:
         assert dt == np.uint8 and spp in (1, 3) and predictor == 1, "JPEG: uint8, one or three samples, no predictor"
     jpeg_ycc = compression == 7 and spp == 3 and jpeg.get("photometric", "ycbcr") != "rgb"
+    j2k = compression in _lib.J2K_COMPRESSIONS
+    jpeg2000 = dict(jpeg2000 or {})
+    if j2k:
+        assert predictor == 1 and ((dt == np.uint8 and spp in (1, 3)) or (dt == np.uint16 and spp == 1)), \
+            "JPEG 2000: uint8 with one or three samples or uint16 with one, no predictor"
     buf = bytearray(b"II" if bo == "<" else b"MM")
     if bigtiff:
         buf += struct.pack(bo + "HHHQ", 43, 8, 0, 0)
@@ -213,7 +249,16 @@ def write_tiled_tiff(path, planes, levels=(), tile=(256, 256), rows_per_strip=No
                     shared = [s for (m, s) in head if m in (0xDB, 0xC4)]
                 stream = b"\xff\xd8" + b"".join(s for (m, s) in head if s not in shared) + rest
             raws.append(stream)
-        for (x, y, bw, bh) in () if compression == 7 else boxes:
+        if j2k:
+            parts = []
+            for (x, y, bw, bh) in boxes:
+                part = img[y:y + bh, x:x + bw]
+                pad = [(0, bh - part.shape[0]), (0, bw - part.shape[1])] + [(0, 0)] * (img.ndim - 2)
+                parts.append(np.pad(part, pad, mode="edge"))
+            raws = list(mapper(_J2kJob(jpeg2000), parts))
+            if jpeg2000.get("rewrite"):
+                raws = [jpeg2000["rewrite"](r) for r in raws]
+        for (x, y, bw, bh) in () if compression == 7 or j2k else boxes:
             seg = np.zeros((bh, bw) + img.shape[2:], dtype=fdt)
             part = img[y:y + bh, x:x + bw]
             seg[:part.shape[0], :part.shape[1]] = part
@@ -342,7 +387,7 @@ class TiffImage:
 
     def __init__(self, path, size_z=1, size_c=1, size_t=1, dimension_order="XYZCT", accept=()):
         """accept: the further forms a file may use, any of "deflate", "zstd", "predictor3" and
-        "samples" and "jpeg" (omr_tiff_image_open_ex); empty: the plain open, which refuses them all.  size_c
+        "samples", "jpeg" and "jpeg2000" (omr_tiff_image_open_ex); empty: the plain open, which refuses them all.  size_c
         counts every sample of a chunky image as a channel (3 for an RGB image)."""
         h = ctypes.c_void_p()
         accept = (accept,) if isinstance(accept, str) else tuple(accept)
@@ -494,6 +539,59 @@ def jpeg_stream_forms(stream, tables=None):
     _lib.check(lib.omr_jpeg_stream_forms(tab.ctypes.data if tab.size else None, tab.size,
                                          src.ctypes.data if src.size else None, src.size, ctypes.byref(bits)))
     return {n for k, n in enumerate(_lib.JPEG_FORM_NAMES) if bits.value >> k & 1}
+
+
+def j2k_decode_host(stream, width, height, samples=1, bits=8):
+    """The host JPEG 2000 decoder alone (omr_j2k_decode_host): [height][width] or [height][width][3],
+    uint8 or uint16, or OmrError (INVALID_ARGUMENT: a form out of scope, named in the message;
+    INTERNAL: damage)."""
+    src = np.frombuffer(bytes(stream), dtype=np.uint8)
+    n = int(width) * int(height) * int(samples)
+    out = np.zeros(max(n, 1), dtype=np.uint16 if bits == 16 else np.uint8)
+    why = ctypes.create_string_buffer(160)
+    st = lib.omr_j2k_decode_host(src.ctypes.data if src.size else None, src.size, int(width), int(height), int(samples),
+                                 int(bits), out.ctypes.data, why, 160)
+    if st != _lib.OK:
+        raise _lib.OmrError(st, why.value.decode())
+    out = out[:n]
+    return out.reshape(height, width) if samples == 1 else out.reshape(height, width, samples)
+
+
+def j2k_stream_forms(stream):
+    """The coding forms a good codestream uses (omr_j2k_stream_forms), as a set of names of _lib.J2K_FORM_NAMES."""
+    src = np.frombuffer(bytes(stream), dtype=np.uint8)
+    bits = ctypes.c_uint64(0)
+    _lib.check(lib.omr_j2k_stream_forms(src.ctypes.data if src.size else None, src.size, ctypes.byref(bits)))
+    return {n for k, n in enumerate(_lib.J2K_FORM_NAMES) if bits.value >> k & 1}
+
+
+def j2k_decode_batch_device(ctx, streams, sizes, samples=1, bits=8):
+    """K19 alone (omr_j2k_decode_batch_device): streams[i] with a frame of sizes[i] = (width, height),
+    decoded on ctx's GPU.  Returns ([arrays, [h][w] or [h][w][3], uint8 or uint16], [status per stream])."""
+    import torch
+    n = len(streams)
+    blob = np.frombuffer(b"".join(bytes(s) for s in streams) or b"\0", dtype=np.uint8)
+    lens = np.array([len(s) for s in streams], dtype=np.uint32)
+    offs = np.concatenate([[0], np.cumsum(lens[:-1], dtype=np.uint64)]).astype(np.uint64) if n else np.zeros(0, np.uint64)
+    ws = np.array([int(w) for w, _ in sizes], dtype=np.int32)
+    hs = np.array([int(h) for _, h in sizes], dtype=np.int32)
+    nbytes = [int(w) * int(h) * samples * (bits // 8) for w, h in sizes]
+    doffs = np.array([sum((b + 31) // 16 * 16 for b in nbytes[:i]) for i in range(n)], dtype=np.uint64)
+    total = sum((b + 31) // 16 * 16 for b in nbytes)
+    out = torch.full((max(total, 16),), 0xA5, dtype=torch.uint8, device=f"cuda:{ctx.device}")
+    ctx.order_after_torch()
+    status = np.zeros(max(n, 1), dtype=np.int32)
+    _lib.check(lib.omr_j2k_decode_batch_device(ctx.h, blob.ctypes.data, offs.ctypes.data, lens.ctypes.data, ws.ctypes.data,
+                                               hs.ctypes.data, n, int(samples), int(bits), out.data_ptr(), doffs.ctypes.data,
+                                               status.ctypes.data), ctx.h)
+    host = out.cpu().numpy()
+    got = []
+    for i, (w, h) in enumerate(sizes):
+        a = host[int(doffs[i]):int(doffs[i]) + nbytes[i]]
+        assert (host[int(doffs[i]) + nbytes[i]:int(doffs[i]) + (nbytes[i] + 31) // 16 * 16] == 0xA5).all(), "bytes behind a stream overwritten"
+        a = a.view("<u2") if bits == 16 else a
+        got.append(a.reshape(h, w) if samples == 1 else a.reshape(h, w, samples))
+    return got, [int(v) for v in status[:n]]
 
 
 def jpeg_decode_batch_device(ctx, streams, sizes, samples=1, ycbcr=False, tables=None):
