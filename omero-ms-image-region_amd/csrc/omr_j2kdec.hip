@@ -128,8 +128,8 @@ __global__ void __launch_bounds__(256) k_j2k_pixels(const J2kSegDesc* __restrict
 }  // namespace
 
 // The descriptor table of one group: [J2kSegDesc m][J2kBlock b][J2kRange r], up in one copy.
-omr_status j2k_decode_group(Ctx* ctx, SegPipe* T, const std::vector<J2kJob>& jobs, const std::vector<J2kPlan>& plans,
-                            bool swap16, const uint8_t* d_src, uint8_t* d_dst, std::vector<int32_t>& status) {
+CodecLaunched j2k_decode_group(Ctx* ctx, SegPipe* T, const std::vector<CodecJob>& jobs, const std::vector<J2kPlan>& plans,
+                               bool swap16, const uint8_t* d_src, uint8_t* d_dst, std::vector<int32_t>& status) {
     const size_t n = jobs.size();
     status.assign(n, OMR_OK);
     std::vector<int32_t> live;                             // the jobs that decode
@@ -158,7 +158,7 @@ omr_status j2k_decode_group(Ctx* ctx, SegPipe* T, const std::vector<J2kJob>& job
     int32_t max_levels = 0, max_comp = 1;
     int64_t max_pixels = 0;
     for (size_t j = 0; j < m; ++j) {
-        const J2kJob& J = jobs[(size_t)live[j]];
+        const CodecJob& J = jobs[(size_t)live[j]];
         const J2kPlan& P = plans[(size_t)live[j]];
         J2kSegDesc& S = hs[j];
         S.dst_off = J.dst_off;
@@ -231,30 +231,18 @@ extern "C" omr_status omr_j2k_decode_batch_device(omr_ctx* ctx, const uint8_t* s
     if (bits != 8 && bits != 16) return fail(ctx, OMR_INVALID_ARGUMENT, "j2k: bits must be 8 or 16");
     OMR_HIP(ctx, hipSetDevice(ctx->device));
     SegPipe* T = seg_pipe(ctx, SegKind::tiff);
-    std::vector<J2kJob> jobs((size_t)n);
+    std::vector<CodecJob> jobs((size_t)n);
     std::vector<J2kPlan> plans((size_t)n);
-    size_t in_bytes = 0;
     for (int32_t k = 0; k < n; ++k) {
-        J2kJob& J = jobs[(size_t)k];
+        CodecJob& J = jobs[(size_t)k];
         J.dst_off = dst_offsets[k];
-        J.in_off = in_bytes;
         if (!j2k_sizes_ok(widths[k], heights[k], samples, bits) || (bits == 16 && (dst_offsets[k] & 1u))) {
             J.parsed = OMR_INVALID_ARGUMENT;
             continue;
         }
         J.parsed = j2k_prepare(src + offsets[k], lengths[k], widths[k], heights[k], samples, bits, plans[(size_t)k], nullptr);
-        if (J.parsed == OMR_OK) in_bytes += align_up((size_t)lengths[k], 16);
     }
-    omr_status st = grow_pinned(ctx, T->pin, T->d_in, T->in_cap, std::max<size_t>(in_bytes, 16), "j2k staging");
-    if (st) return st;
-    uint8_t* pin = static_cast<uint8_t*>(T->pin);
-    for (int32_t k = 0; k < n; ++k)
-        if (jobs[(size_t)k].parsed == OMR_OK) std::memcpy(pin + jobs[(size_t)k].in_off, src + offsets[k], lengths[k]);
-    if (in_bytes) OMR_HIP(ctx, hipMemcpyAsync(T->d_in, pin, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-    std::vector<int32_t> stv;
-    st = j2k_decode_group(ctx, T, jobs, plans, false, static_cast<const uint8_t*>(T->d_in), d_dst, stv);
-    if (st) return st;
-    OMR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (int32_t k = 0; k < n; ++k) status[k] = stv[(size_t)k];
-    return OMR_OK;
+    return decode_batch_staged(ctx, T, "j2k", jobs, src, offsets, lengths, [&](std::vector<int32_t>& stv) {
+        return j2k_decode_group(ctx, T, jobs, plans, false, static_cast<const uint8_t*>(T->d_in), d_dst, stv);
+    }, status);
 }

@@ -423,8 +423,8 @@ omr_status launch_jpeg_decode(Ctx* ctx, const uint8_t* src, const JpegSegDesc* s
 
 // The descriptor table of one group: [JpegSegDesc m][JpegIvDesc k][JpegTables s] | [status i32 m]:
 // everything goes up in one copy (the statuses as OMR_OK), the statuses come back.
-omr_status jpeg_decode_group(Ctx* ctx, SegPipe* T, const std::vector<JpegJob>& jobs, const std::vector<JpegPlan>& plans,
-                             int32_t samples, bool ycc, const uint8_t* d_src, uint8_t* d_dst, std::vector<int32_t>& status) {
+CodecLaunched jpeg_decode_group(Ctx* ctx, SegPipe* T, const std::vector<CodecJob>& jobs, const std::vector<JpegPlan>& plans,
+                                int32_t samples, bool ycc, const uint8_t* d_src, uint8_t* d_dst, std::vector<int32_t>& status) {
     const size_t n = jobs.size();
     status.assign(n, OMR_OK);
     std::vector<int32_t> live;                             // the jobs that decode: parsed, and not empty
@@ -473,7 +473,7 @@ omr_status jpeg_decode_group(Ctx* ctx, SegPipe* T, const std::vector<JpegJob>& j
     int32_t max_blocks = 0;
     int64_t max_pixels = 0;
     for (size_t j = 0; j < m; ++j) {
-        const JpegJob& J = jobs[(size_t)live[j]];
+        const CodecJob& J = jobs[(size_t)live[j]];
         const JpegPlan& P = plans[(size_t)live[j]];
         JpegSegDesc& S = hs[j];
         S.dst_off = J.dst_off;
@@ -509,21 +509,10 @@ omr_status jpeg_decode_group(Ctx* ctx, SegPipe* T, const std::vector<JpegJob>& j
                             reinterpret_cast<const JpegTables*>(dtab + o_tab), static_cast<uint8_t*>(T->d_coef), d_dst,
                             reinterpret_cast<int32_t*>(dtab + o_status), max_blocks, max_pixels, (int32_t)n_split, split_bits);
     if (st) return st;
-    T->jpeg_status_off = o_status;
-    T->jpeg_live = live;
-    return OMR_OK;
-}
-
-omr_status jpeg_group_statuses(Ctx* ctx, SegPipe* T, std::vector<int32_t>& status) {
-    const size_t m = T->jpeg_live.size();
-    uint8_t* tab = static_cast<uint8_t*>(T->pin_tab);
-    if (m) OMR_HIP(ctx, hipMemcpyAsync(tab + T->jpeg_status_off, static_cast<uint8_t*>(T->d_tab) + T->jpeg_status_off, 4 * m,
-                                       hipMemcpyDeviceToHost, ctx->stream));
-    OMR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const int32_t* h = reinterpret_cast<const int32_t*>(tab + T->jpeg_status_off);
-    for (size_t j = 0; j < m; ++j) status[(size_t)T->jpeg_live[j]] = h[j];
-    T->jpeg_live.clear();
-    return OMR_OK;
+    CodecLaunched launched;
+    launched.off = o_status;
+    launched.live = std::move(live);
+    return launched;
 }
 
 }  // namespace omr
@@ -543,13 +532,11 @@ extern "C" omr_status omr_jpeg_decode_batch_device(omr_ctx* ctx, const uint8_t* 
     if (samples != 1 && samples != 3) return fail(ctx, OMR_INVALID_ARGUMENT, "jpeg: samples must be 1 or 3");
     OMR_HIP(ctx, hipSetDevice(ctx->device));
     SegPipe* T = seg_pipe(ctx, SegKind::tiff);
-    std::vector<JpegJob> jobs((size_t)n);
+    std::vector<CodecJob> jobs((size_t)n);
     std::vector<JpegPlan> plans((size_t)n);
-    size_t in_bytes = 0;
     for (int32_t k = 0; k < n; ++k) {
-        JpegJob& J = jobs[(size_t)k];
+        CodecJob& J = jobs[(size_t)k];
         J.dst_off = dst_offsets[k];
-        J.in_off = in_bytes;
         if (widths[k] < 1 || heights[k] < 1 || widths[k] > 65535 || heights[k] > 65535 ||
             (uint64_t)widths[k] * (uint64_t)heights[k] * (uint64_t)samples > ((uint64_t)256 << 20)) {
             J.parsed = OMR_INVALID_ARGUMENT;
@@ -557,19 +544,8 @@ extern "C" omr_status omr_jpeg_decode_batch_device(omr_ctx* ctx, const uint8_t* 
         }
         J.parsed = jpeg_prepare(tables, tables_length, src + offsets[k], lengths[k], widths[k], heights[k], samples,
                                 plans[(size_t)k], nullptr);
-        if (J.parsed == OMR_OK) in_bytes += align_up((size_t)lengths[k], 16);
     }
-    omr_status st = grow_pinned(ctx, T->pin, T->d_in, T->in_cap, std::max<size_t>(in_bytes, 16), "jpeg staging");
-    if (st) return st;
-    uint8_t* pin = static_cast<uint8_t*>(T->pin);
-    for (int32_t k = 0; k < n; ++k)
-        if (jobs[(size_t)k].parsed == OMR_OK) std::memcpy(pin + jobs[(size_t)k].in_off, src + offsets[k], lengths[k]);
-    if (in_bytes) OMR_HIP(ctx, hipMemcpyAsync(T->d_in, pin, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-    std::vector<int32_t> stv;
-    st = jpeg_decode_group(ctx, T, jobs, plans, samples, ycbcr != 0, static_cast<const uint8_t*>(T->d_in), d_dst, stv);
-    if (st) return st;
-    st = jpeg_group_statuses(ctx, T, stv);
-    if (st) return st;
-    for (int32_t k = 0; k < n; ++k) status[k] = stv[(size_t)k];
-    return OMR_OK;
+    return decode_batch_staged(ctx, T, "jpeg", jobs, src, offsets, lengths, [&](std::vector<int32_t>& stv) {
+        return jpeg_decode_group(ctx, T, jobs, plans, samples, ycbcr != 0, static_cast<const uint8_t*>(T->d_in), d_dst, stv);
+    }, status);
 }

@@ -1,10 +1,11 @@
 // omr_segread.cpp — the device route of the TIFF and the Zarr reader (omr_segread.h): the staging
 // of a context and its growth, one group of regions from plan to status scan (the run stage with
 // the decoder of the source's codec: K13a, K14a or K16a, then K13b; Blosc chunks through their own
-// finish: container parsing, K15a and K16a side by side, K15b; JPEG segments through theirs: header
-// parsing, K17a .. K17c, K13b; JPEG 2000 segments through theirs: headers and packets, K19a .. K19c,
-// K13b), the group loop and the tile renderer.  Every HIP call of the two readers is in this file,
-// but for the JPEG and JPEG 2000 groups' table uploads and launches (omr_jpegdec.hip, omr_j2kdec.hip).
+// finish: container parsing, K15a and K16a side by side, K15b; JPEG and JPEG 2000 segments through
+// the image-codec finish: the codec's prepare, K17a .. K17c or K19a .. K19c, K13b), the group loop,
+// the tile renderer, the argument checks of the front-ends' entry points and the staging of the two
+// batch decoders.  Every HIP call of the two readers is in this file, but for the JPEG and JPEG 2000
+// groups' table uploads and launches (omr_jpegdec.hip, omr_j2kdec.hip).
 #include "omr_segread.h"
 
 #include "omr_j2kdec.h"
@@ -122,102 +123,94 @@ omr_status finish_blosc(Ctx* ctx, SegPipe* T, const SegSource& S, const SegPlan&
     return scan_statuses(ctx, S, t, tab, dtab, "blosc");
 }
 
-// The JPEG half of read_group, from the segments' bytes in pinned memory on (K17).  While they are
-// there the host parses every segment's header up to SOS, merges it with its IFD's JPEGTables,
-// builds the lookup tables and lists the restart intervals (jpeg_prepare; a segment it refuses ends
-// the call before any launch).  The bytes and the placements go up in the staging copy, the
-// descriptors (identical table sets once) behind them in a copy of their own; K17a .. K17c decode
-// into the segments' scratch as chunky bytes and K13b places them as it places a chunky Deflate segment.
-omr_status finish_jpeg(Ctx* ctx, SegPipe* T, SegSource& S, SegPlan& plan, const std::vector<SegBytes>& segs, size_t in_bytes) {
+// The placements of a group behind its bytes and rows (t.o_place), their sources set, and the
+// staging copy: everything up to t.up_bytes goes up.
+omr_status upload_staging(Ctx* ctx, SegPipe* T, SegPlan& plan, const std::vector<SegBytes>& segs, const TableLayout& t, bool decoded) {
     uint8_t* pin = static_cast<uint8_t*>(T->pin);
     uint8_t* din = static_cast<uint8_t*>(T->d_in);
     uint8_t* dscr = static_cast<uint8_t*>(T->d_scratch);
-    std::vector<int32_t> coded;
-    for (size_t k = 0; k < segs.size(); ++k)
-        if (segs[k].cnt) coded.push_back((int32_t)k);
-    const size_t m = coded.size();
-    std::vector<JpegJob> jobs(m);
-    std::vector<JpegPlan> plans(m);
-    std::vector<std::string> why(m);
-    const int32_t spp = S.geom.spp;
-    parallel_for((int)m, in_bytes > ((size_t)1 << 20), [&](int j) {
-        const SegBytes& u = segs[(size_t)coded[(size_t)j]];
-        size_t tl = 0;
-        const uint8_t* tb = S.jpeg_tables(plan.segs[(size_t)coded[(size_t)j]], &tl);
-        const int32_t rows = (int32_t)(u.expected / ((uint32_t)S.geom.seg_w * (uint32_t)spp));
-        jobs[(size_t)j].in_off = u.in_off;
-        jobs[(size_t)j].dst_off = u.scratch_off;
-        jobs[(size_t)j].parsed = jpeg_prepare(tb, tl, pin + u.in_off, (size_t)u.cnt, S.geom.seg_w, rows, spp,
-                                              plans[(size_t)j], &why[(size_t)j]);
-    });
-    for (size_t j = 0; j < m; ++j)
-        if (jobs[j].parsed == OMR_INVALID_ARGUMENT) return fail(ctx, OMR_INVALID_ARGUMENT, said(S, "unsupported JPEG segment: ") + why[j]);
-        else if (jobs[j].parsed) return fail(ctx, OMR_INTERNAL, said(S, "corrupt JPEG ") + S.noun + " (" + why[j] + ")");
-    const size_t place_at = align_up(in_bytes, 256), place_bytes = plan.places.size() * sizeof(TiffPlace);
-    TiffPlace* h_place = reinterpret_cast<TiffPlace*>(pin + place_at);
+    TiffPlace* h_place = reinterpret_cast<TiffPlace*>(pin + t.o_place);
     for (size_t k = 0; k < plan.places.size(); ++k) {
         const SegBytes& u = segs[(size_t)plan.place_seg[k]];
-        plan.places[k].src = !u.cnt ? nullptr : dscr + u.scratch_off;
+        plan.places[k].src = !u.cnt ? nullptr : decoded ? dscr + u.scratch_off : din + u.in_off;
         h_place[k] = plan.places[k];
     }
-    OMR_HIP(ctx, hipMemcpyAsync(din, pin, place_at + place_bytes, hipMemcpyHostToDevice, ctx->stream));
-    std::vector<int32_t> status;
-    omr_status st = jpeg_decode_group(ctx, T, jobs, plans, spp, S.jpeg_ycc, din, dscr, status);
-    if (st) return st;
-    st = launch_tiff_place(ctx, reinterpret_cast<const TiffPlace*>(din + place_at), (int32_t)plan.places.size(), plan.max_rows,
-                           S.geom.bpp, 1, false, S.geom.spp);
-    if (st) return st;
-    st = jpeg_group_statuses(ctx, T, status);
-    if (st) return st;
-    for (int32_t s : status)
-        if (s != OMR_OK) return fail(ctx, OMR_INTERNAL, said(S, "corrupt JPEG ") + S.noun);
+    OMR_HIP(ctx, hipMemcpyAsync(din, pin, t.up_bytes, hipMemcpyHostToDevice, ctx->stream));
     return OMR_OK;
 }
 
-// The JPEG 2000 half of read_group, from the segments' bytes in pinned memory on (K19).  While they
-// are there the host parses every segment's headers and walks its packets (j2k_prepare; a segment
-// it refuses ends the call before any launch: all the damage that can be seen is seen there).  The
-// bytes and the placements go up in the staging copy, the code-block descriptors behind them in a
-// copy of their own; K19a .. K19c decode into the segments' scratch as chunky samples in the file's
-// byte order and K13b places them as it places a Deflate segment of the same sample type.
-omr_status finish_j2k(Ctx* ctx, SegPipe* T, SegSource& S, SegPlan& plan, const std::vector<SegBytes>& segs, size_t in_bytes) {
-    uint8_t* pin = static_cast<uint8_t*>(T->pin);
-    uint8_t* din = static_cast<uint8_t*>(T->d_in);
-    uint8_t* dscr = static_cast<uint8_t*>(T->d_scratch);
+// The image-codec half of read_group (JPEG: K17, JPEG 2000: K19), from the segments' bytes in pinned
+// memory on.  While they are there the host runs the codec's prepare on every coded segment (JPEG:
+// the header up to SOS merged with the IFD's JPEGTables, the lookup tables and the restart intervals;
+// JPEG 2000: the headers and the packet walk), on threads when the group holds more than
+// `threaded_over` bytes; a segment it refuses ends the call before any launch.  The bytes and the
+// placements go up in the staging copy (t: a layout without stream rows), the codec's descriptors
+// behind them in a copy of their own; its kernels decode into the segments' scratch as chunky
+// samples and K13b places them as it places a chunky Deflate segment of the same sample type.
+// prepare(key, segment, its bytes, plan, why) and decode(jobs, plans, status) are all a codec adds.
+template <typename Plan, typename Prepare, typename Decode>
+omr_status finish_image_codec(Ctx* ctx, SegPipe* T, const SegSource& S, SegPlan& plan, const std::vector<SegBytes>& segs,
+                              const TableLayout& t, size_t in_bytes, const std::string& name, size_t threaded_over,
+                              const Prepare& prepare, const Decode& decode) {
+    const uint8_t* pin = static_cast<const uint8_t*>(T->pin);
     std::vector<int32_t> coded;
     for (size_t k = 0; k < segs.size(); ++k)
         if (segs[k].cnt) coded.push_back((int32_t)k);
     const size_t m = coded.size();
-    std::vector<J2kJob> jobs(m);
-    std::vector<J2kPlan> plans(m);
+    std::vector<CodecJob> jobs(m);
+    std::vector<Plan> plans(m);
     std::vector<std::string> why(m);
-    const int32_t spp = S.geom.spp, bits = 8 * S.geom.bpp;
-    parallel_for((int)m, in_bytes > ((size_t)1 << 18), [&](int j) {
-        const SegBytes& u = segs[(size_t)coded[(size_t)j]];
-        const int32_t rows = (int32_t)(u.expected / ((uint32_t)S.geom.seg_w * (uint32_t)spp * (uint32_t)S.geom.bpp));
-        jobs[(size_t)j].in_off = u.in_off;
-        jobs[(size_t)j].dst_off = u.scratch_off;
-        jobs[(size_t)j].parsed = j2k_prepare(pin + u.in_off, (size_t)u.cnt, S.geom.seg_w, rows, spp, bits, plans[(size_t)j], &why[(size_t)j]);
+    parallel_for((int)m, in_bytes > threaded_over, [&](int j) {
+        const size_t k = (size_t)coded[(size_t)j];
+        jobs[(size_t)j].in_off = segs[k].in_off;
+        jobs[(size_t)j].dst_off = segs[k].scratch_off;
+        jobs[(size_t)j].parsed = prepare(plan.segs[k], segs[k], pin + segs[k].in_off, plans[(size_t)j], &why[(size_t)j]);
     });
     for (size_t j = 0; j < m; ++j)
-        if (jobs[j].parsed == OMR_INVALID_ARGUMENT) return fail(ctx, OMR_INVALID_ARGUMENT, said(S, "unsupported JPEG 2000 segment: ") + why[j]);
-        else if (jobs[j].parsed) return fail(ctx, OMR_INTERNAL, said(S, "corrupt JPEG 2000 ") + S.noun + " (" + why[j] + ")");
-    const size_t place_at = align_up(in_bytes, 256), place_bytes = plan.places.size() * sizeof(TiffPlace);
-    TiffPlace* h_place = reinterpret_cast<TiffPlace*>(pin + place_at);
-    for (size_t k = 0; k < plan.places.size(); ++k) {
-        const SegBytes& u = segs[(size_t)plan.place_seg[k]];
-        plan.places[k].src = !u.cnt ? nullptr : dscr + u.scratch_off;
-        h_place[k] = plan.places[k];
-    }
-    OMR_HIP(ctx, hipMemcpyAsync(din, pin, place_at + place_bytes, hipMemcpyHostToDevice, ctx->stream));
+        if (jobs[j].parsed == OMR_INVALID_ARGUMENT) return fail(ctx, OMR_INVALID_ARGUMENT, said(S, "unsupported ") + name + " segment: " + why[j]);
+        else if (jobs[j].parsed) return fail(ctx, OMR_INTERNAL, said(S, "corrupt ") + name + " " + S.noun + " (" + why[j] + ")");
+    omr_status st = upload_staging(ctx, T, plan, segs, t, true);
+    if (st) return st;
     std::vector<int32_t> status;
-    omr_status st = j2k_decode_group(ctx, T, jobs, plans, S.swap, din, dscr, status);
+    const CodecLaunched launched = decode(jobs, plans, status);
+    if (launched.st) return launched.st;
+    st = launch_tiff_place(ctx, reinterpret_cast<const TiffPlace*>(static_cast<const uint8_t*>(T->d_in) + t.o_place),
+                           (int32_t)plan.places.size(), plan.max_rows, S.geom.bpp, 1, false, S.geom.spp);
     if (st) return st;
-    st = launch_tiff_place(ctx, reinterpret_cast<const TiffPlace*>(din + place_at), (int32_t)plan.places.size(), plan.max_rows,
-                           S.geom.bpp, 1, false, S.geom.spp);
+    st = fetch_codec_statuses(ctx, T, launched, status);
     if (st) return st;
-    OMR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (int32_t s : status)
+        if (s != OMR_OK) return fail(ctx, OMR_INTERNAL, said(S, "corrupt ") + name + " " + S.noun);
     return OMR_OK;
+}
+
+// The two image codecs: their names, thresholds, row arithmetic and calls.
+omr_status finish_image(Ctx* ctx, SegPipe* T, const SegSource& S, SegPlan& plan, const std::vector<SegBytes>& segs,
+                        const TableLayout& t, size_t in_bytes) {
+    const SegGeom& g = S.geom;
+    uint8_t* din = static_cast<uint8_t*>(T->d_in);
+    uint8_t* dscr = static_cast<uint8_t*>(T->d_scratch);
+    if (S.codec == SegCodec::jpeg)
+        return finish_image_codec<JpegPlan>(
+            ctx, T, S, plan, segs, t, in_bytes, "JPEG", (size_t)1 << 20,
+            [&](const SegKey& key, const SegBytes& u, const uint8_t* bytes, JpegPlan& P, std::string* why) {
+                size_t tl = 0;
+                const uint8_t* tb = S.jpeg_tables(key, &tl);
+                const int32_t rows = (int32_t)(u.expected / ((uint32_t)g.seg_w * (uint32_t)g.spp));
+                return jpeg_prepare(tb, tl, bytes, (size_t)u.cnt, g.seg_w, rows, g.spp, P, why);
+            },
+            [&](const std::vector<CodecJob>& jobs, const std::vector<JpegPlan>& plans, std::vector<int32_t>& status) {
+                return jpeg_decode_group(ctx, T, jobs, plans, g.spp, S.jpeg_ycc, din, dscr, status);
+            });
+    return finish_image_codec<J2kPlan>(
+        ctx, T, S, plan, segs, t, in_bytes, "JPEG 2000", (size_t)1 << 18,
+        [&](const SegKey&, const SegBytes& u, const uint8_t* bytes, J2kPlan& P, std::string* why) {
+            const int32_t rows = (int32_t)(u.expected / ((uint32_t)g.seg_w * (uint32_t)g.spp * (uint32_t)g.bpp));
+            return j2k_prepare(bytes, (size_t)u.cnt, g.seg_w, rows, g.spp, 8 * g.bpp, P, why);
+        },
+        [&](const std::vector<CodecJob>& jobs, const std::vector<J2kPlan>& plans, std::vector<int32_t>& status) {
+            return j2k_decode_group(ctx, T, jobs, plans, S.swap, din, dscr, status);
+        });
 }
 
 // One group of regions: reqs[r0, r1).
@@ -231,9 +224,10 @@ omr_status read_group(Ctx* ctx, SegSource& S, const omr_raw_tile_request* reqs, 
     omr_status st = S.sizes(ctx, plan.segs, segs);
     if (st) return st;
     const bool blosc = S.codec == SegCodec::blosc;         // its tables go up behind the bytes, from T->pin_tab
+    const bool image = S.codec == SegCodec::jpeg || S.codec == SegCodec::j2k;   // descriptors of their own, as Blosc
     const bool decoded = S.codec != SegCodec::none;
     size_t in_bytes = 0, scratch_bytes = 0;
-    std::vector<int32_t> coded;                            // the segments the decoder kernel gets
+    std::vector<int32_t> coded;                            // the segments a stream-table decoder gets
     for (size_t k = 0; k < segs.size(); ++k) {
         SegBytes& u = segs[k];
         if (!u.cnt) continue;
@@ -242,7 +236,7 @@ omr_status read_group(Ctx* ctx, SegSource& S, const omr_raw_tile_request* reqs, 
         if (decoded) {
             u.scratch_off = scratch_bytes;
             scratch_bytes += align_up((size_t)u.expected, 16);
-            if (!blosc) coded.push_back((int32_t)k);
+            if (!blosc && !image) coded.push_back((int32_t)k);
         }
     }
     const size_t m = coded.size();
@@ -257,8 +251,7 @@ omr_status read_group(Ctx* ctx, SegSource& S, const omr_raw_tile_request* reqs, 
     uint8_t* dscr = static_cast<uint8_t*>(T->d_scratch);
     if (!S.read(plan.segs, segs, pin, in_bytes)) return fail(ctx, OMR_INTERNAL, said(S, S.noun) + " read failed");
     if (blosc) return finish_blosc(ctx, T, S, plan, segs, in_bytes);
-    if (S.codec == SegCodec::jpeg) return finish_jpeg(ctx, T, S, plan, segs, in_bytes);
-    if (S.codec == SegCodec::j2k) return finish_j2k(ctx, T, S, plan, segs, in_bytes);
+    if (image) return finish_image(ctx, T, S, plan, segs, t, in_bytes);
     for (size_t j = 0; j < m; ++j) {
         const SegBytes& u = segs[(size_t)coded[j]];
         t.off(pin)[j] = u.in_off;
@@ -266,13 +259,8 @@ omr_status read_group(Ctx* ctx, SegSource& S, const omr_raw_tile_request* reqs, 
         t.len(pin)[j] = (uint32_t)u.cnt;
         t.exp(pin)[j] = u.expected;
     }
-    TiffPlace* h_place = reinterpret_cast<TiffPlace*>(pin + t.o_place);
-    for (size_t k = 0; k < plan.places.size(); ++k) {
-        const SegBytes& u = segs[(size_t)plan.place_seg[k]];
-        plan.places[k].src = !u.cnt ? nullptr : decoded ? dscr + u.scratch_off : din + u.in_off;
-        h_place[k] = plan.places[k];
-    }
-    OMR_HIP(ctx, hipMemcpyAsync(din, pin, t.up_bytes, hipMemcpyHostToDevice, ctx->stream));
+    st = upload_staging(ctx, T, plan, segs, t, decoded);
+    if (st) return st;
     const StreamTable rows = t.rows(din, din, 0, m, dscr, false);
     const char* codec = "";
     switch (S.codec) {
@@ -299,26 +287,71 @@ SegPipe* seg_pipe(Ctx* c, SegKind kind) {
     return static_cast<SegPipe*>(state);
 }
 
-omr_status read_regions(Ctx* ctx, SegSource& src, const omr_raw_tile_request* reqs, int32_t n, int32_t width,
-                        int32_t height, void* d_dst, int64_t region_stride_bytes) {
+omr_status fetch_codec_statuses(Ctx* ctx, SegPipe* T, const CodecLaunched& launched, std::vector<int32_t>& status) {
+    const size_t m = launched.live.size();
+    uint8_t* tab = static_cast<uint8_t*>(T->pin_tab);
+    if (m) OMR_HIP(ctx, hipMemcpyAsync(tab + launched.off, static_cast<uint8_t*>(T->d_tab) + launched.off, 4 * m,
+                                       hipMemcpyDeviceToHost, ctx->stream));
+    OMR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const int32_t* h = reinterpret_cast<const int32_t*>(tab + launched.off);
+    for (size_t j = 0; j < m; ++j) status[(size_t)launched.live[j]] = h[j];
+    return OMR_OK;
+}
+
+omr_status decode_batch_staged(Ctx* ctx, SegPipe* T, const char* codec, std::vector<CodecJob>& jobs, const uint8_t* src,
+                               const uint64_t* offsets, const uint32_t* lengths, const DecodeGroupFn& decode,
+                               int32_t* status_out) {
+    size_t in_bytes = 0;
+    for (size_t k = 0; k < jobs.size(); ++k) {
+        jobs[k].in_off = in_bytes;
+        if (jobs[k].parsed == OMR_OK) in_bytes += align_up((size_t)lengths[k], 16);
+    }
+    omr_status st = grow_pinned(ctx, T->pin, T->d_in, T->in_cap, std::max<size_t>(in_bytes, 16), std::string(codec) + " staging");
+    if (st) return st;
+    uint8_t* pin = static_cast<uint8_t*>(T->pin);
+    for (size_t k = 0; k < jobs.size(); ++k)
+        if (jobs[k].parsed == OMR_OK) std::memcpy(pin + jobs[k].in_off, src + offsets[k], lengths[k]);
+    if (in_bytes) OMR_HIP(ctx, hipMemcpyAsync(T->d_in, pin, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    std::vector<int32_t> status;
+    const CodecLaunched launched = decode(status);
+    if (launched.st) return launched.st;
+    st = fetch_codec_statuses(ctx, T, launched, status);
+    if (st) return st;
+    std::copy(status.begin(), status.end(), status_out);
+    return OMR_OK;
+}
+
+omr_status read_regions_checked(Ctx* ctx, SegSource& S, const SegImageDims& im, const omr_raw_tile_request* reqs, int32_t n,
+                                int32_t width, int32_t height, void* d_dst, int64_t region_stride_bytes) {
+    if (n < 0 || (n && (!reqs || !d_dst))) return fail(ctx, OMR_INVALID_ARGUMENT, said(S, "null argument"));
+    if (im.level < 0 || im.level >= im.n_levels) return fail(ctx, OMR_INVALID_ARGUMENT, said(S, "no such level"));
+    if (width < 0 || height < 0) return fail(ctx, OMR_INVALID_ARGUMENT, said(S, "bad region size"));
+    const int64_t region_bytes = (int64_t)width * height * im.bpp;
+    if (region_stride_bytes < region_bytes || region_stride_bytes % im.bpp || reinterpret_cast<uintptr_t>(d_dst) % (uintptr_t)im.bpp)
+        return fail(ctx, OMR_INVALID_ARGUMENT, said(S, "region stride or destination not a multiple of the sample size"));
+    for (int32_t i = 0; i < n; ++i)
+        if (!im.in_bounds(reqs[i], width, height))
+            return fail(ctx, OMR_INVALID_ARGUMENT, said(S, "region ") + std::to_string(i) + " outside the image");
     if (n == 0 || width == 0 || height == 0) return OMR_OK;
     OMR_HIP(ctx, hipSetDevice(ctx->device));
-    size_t per_req = read_bytes_per_request(src.geom, width, height);
-    if (src.codec == SegCodec::jpeg) per_req += jpeg_workspace_per_request(src.geom, width, height);   // K17's coefficients and planes
-    if (src.codec == SegCodec::j2k) per_req += j2k_workspace_per_request(src.geom, width, height);     // K19's three planes
+    const size_t per_req = read_bytes_per_request(S.geom, width, height) + codec_workspace_per_request(S.codec, S.geom, width, height);
     const int32_t G = group_size(n, std::min(kGroupInBytes, kGroupScratchBytes), per_req);
     for (int32_t r0 = 0; r0 < n; r0 += G) {
-        const omr_status st = read_group(ctx, src, reqs, r0, std::min(n, r0 + G), width, height,
-                                         static_cast<uint8_t*>(d_dst), region_stride_bytes);
+        const omr_status st = read_group(ctx, S, reqs, r0, std::min(n, r0 + G), width, height, static_cast<uint8_t*>(d_dst),
+                                         region_stride_bytes);
         if (st) return st;
     }
     return OMR_OK;
 }
 
-omr_status render_tiles(omr_ctx* ctx, const SegSource& src, const ReadRegionsFn& read, const omr_quantum_def* qdef,
-                        const omr_channel_binding* channels, int32_t size_c, const omr_tile_request* reqs, int32_t n,
-                        int32_t width, int32_t height, int32_t flip_h, int32_t flip_v, uint32_t* argb_out,
-                        int32_t out_on_device) {
+omr_status render_tiles_checked(omr_ctx* ctx, SegSource& src, const SegImageDims& im, const omr_quantum_def* qdef,
+                                const omr_channel_binding* channels, int32_t size_c, const omr_tile_request* reqs, int32_t n,
+                                int32_t width, int32_t height, int32_t flip_h, int32_t flip_v, uint32_t* argb_out,
+                                int32_t out_on_device) {
+    if (!qdef || !channels || !reqs || !argb_out || n < 0) return fail(ctx, OMR_INVALID_ARGUMENT, "null argument");
+    if (size_c != im.sc) return fail(ctx, OMR_INVALID_ARGUMENT, "channel bindings do not match the image's sizeC");
+    if (width <= 0 || height <= 0) return fail(ctx, OMR_INVALID_ARGUMENT, "bad tile size");
+    if (im.level < 0 || im.level >= im.n_levels) return fail(ctx, OMR_INVALID_ARGUMENT, said(src, "no such level"));
     if (n == 0) return OMR_OK;
     // the rendered channels, compacted: [tile][active channel][h][w] with their bindings in order
     std::vector<int32_t> act;
@@ -348,7 +381,7 @@ omr_status render_tiles(omr_ctx* ctx, const SegSource& src, const ReadRegionsFn&
         rr.clear();
         for (int32_t i = 0; i < cnt; ++i)
             for (int a = 0; a < na; ++a) rr.push_back({reqs[t0 + i].z, act[(size_t)a], reqs[t0 + i].t, reqs[t0 + i].x, reqs[t0 + i].y});
-        st = read(rr.data(), cnt * na, T->d_regions, (int64_t)plane_al);
+        st = read_regions_checked(ctx, src, im, rr.data(), cnt * na, width, height, T->d_regions, (int64_t)plane_al);
         if (st) return st;
         uint32_t* dout = out_on_device ? argb_out + (size_t)t0 * width * height : static_cast<uint32_t*>(T->d_out);
         st = omr_render_batch_strided_device(ctx, qdef, bind.data(), (int32_t)bind.size(), T->d_regions, (int64_t)(plane_al * na),

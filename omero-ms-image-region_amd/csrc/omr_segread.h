@@ -1,4 +1,4 @@
-// omr_segread.h — the device-read pipeline that the TIFF and the Zarr reader share (K13 .. K17).
+// omr_segread.h — the device-read pipeline that the TIFF and the Zarr reader share (K13 .. K19).
 //
 // Both readers answer a batch of regions the same way: the segments (tiles, strips, chunks) the
 // regions touch are listed once each, their bytes go to pinned memory and in one copy to the device
@@ -43,8 +43,6 @@ struct SegPipe {
     size_t lit_cap = 0;
     void* d_coef = nullptr;      // K17: the JPEG segments' coefficients (int16) and sample planes; K19: the JPEG 2000 segments' planes
     size_t coef_cap = 0;
-    size_t jpeg_status_off = 0;  // of the group in flight: where its statuses are in pin_tab / d_tab,
-    std::vector<int32_t> jpeg_live;   // and the jobs they belong to (jpeg_decode_group .. jpeg_group_statuses)
     ~SegPipe();
 };
 
@@ -180,20 +178,17 @@ struct TableLayout {
 
 enum class SegCodec { none, lzw, zlib, zstd, blosc, jpeg, j2k };
 
-// What a read request of a JPEG level can need beside read_bytes_per_request: K17's workspace
-// (coefficients and sample planes) of the same segments, so that a group's workspace stays within
-// kGroupScratchBytes as its decoded bytes do.
-inline size_t jpeg_workspace_per_request(const SegGeom& g, int32_t width, int32_t height) {
-    const size_t per_seg = (size_t)3 * g.spp * (((size_t)g.seg_w + 15) / 16 * 16) * (((size_t)g.seg_h + 15) / 16 * 16) + 512;
-    return (size_t)((width - 1) / g.seg_w + 2) * (size_t)((height - 1) / g.seg_h + 2) * per_seg;
-}
-
-// The same for a JPEG 2000 level: K19's workspace of 4 bytes per coefficient, three times -- the
-// subbands as K19a leaves them and the two planes K19b's levels alternate between, the second of a
-// quarter of the size (J2kSegDesc, omr_j2kdec.h).
-inline size_t j2k_workspace_per_request(const SegGeom& g, int32_t width, int32_t height) {
+// What a read request of an image-codec level can need beside read_bytes_per_request: the decoder's
+// workspace for the same segments, so that a group's workspace stays within kGroupScratchBytes as its
+// decoded bytes do.  JPEG: K17's coefficients and sample planes.  JPEG 2000: K19's workspace of 4
+// bytes per coefficient, three times -- the subbands as K19a leaves them and the two planes K19b's
+// levels alternate between, the second of a quarter of the size (J2kSegDesc, omr_j2kdec.h).  Any
+// other codec: nothing.
+inline size_t codec_workspace_per_request(SegCodec codec, const SegGeom& g, int32_t width, int32_t height) {
     const size_t w = (size_t)g.seg_w, h = (size_t)g.seg_h;
-    const size_t per_seg = (size_t)4 * g.spp * (2 * w * h + ((w + 1) / 2) * ((h + 1) / 2)) + 768;
+    size_t per_seg = 0;
+    if (codec == SegCodec::jpeg) per_seg = (size_t)3 * g.spp * ((w + 15) / 16 * 16) * ((h + 15) / 16 * 16) + 512;
+    if (codec == SegCodec::j2k) per_seg = (size_t)4 * g.spp * (2 * w * h + ((w + 1) / 2) * ((h + 1) / 2)) + 768;
     return (size_t)((width - 1) / g.seg_w + 2) * (size_t)((height - 1) / g.seg_h + 2) * per_seg;
 }
 
@@ -230,36 +225,45 @@ struct SegSource {
     bool jpeg_ycc = false;
 };
 
-// ---- K17: one group of JPEG segments (omr_jpegdec.hip) -------------------------------------------
+// ---- K17, K19: one group of image-codec segments (omr_jpegdec.hip, omr_j2kdec.hip) ---------------
 
 struct JpegPlan;
-// One stream: its bytes are at d_src + in_off, it decodes to d_dst + dst_off; parsed: what
-// jpeg_prepare said of it (anything but OMR_OK: it is not decoded and that is its status).
-struct JpegJob {
-    uint64_t in_off = 0, dst_off = 0;
-    omr_status parsed = OMR_OK;
-};
-// The descriptor table of the jobs (plans[k]: job k's jpeg_prepare) into T->pin_tab, up in one
-// copy, the workspace in T->d_coef, and K17a, K17b, K17c on the context's stream.  status: filled
-// with what is known on the host; jpeg_group_statuses then synchronises and adds the kernels'.
-omr_status jpeg_decode_group(Ctx* ctx, SegPipe* T, const std::vector<JpegJob>& jobs, const std::vector<JpegPlan>& plans,
-                             int32_t samples, bool ycc, const uint8_t* d_src, uint8_t* d_dst, std::vector<int32_t>& status);
-omr_status jpeg_group_statuses(Ctx* ctx, SegPipe* T, std::vector<int32_t>& status);
-
-// ---- K19: one group of JPEG 2000 segments (omr_j2kdec.hip) ----------------------------------------
-
 struct J2kPlan;
-// One codestream: its bytes are at d_src + in_off, it decodes to d_dst + dst_off; parsed: what
-// j2k_prepare said of it (anything but OMR_OK: it is not decoded and that is its status).
-struct J2kJob {
+// One stream: its bytes are at d_src + in_off, it decodes to d_dst + dst_off; parsed: what the
+// codec's prepare said of it (anything but OMR_OK: it is not decoded and that is its status).
+struct CodecJob {
     uint64_t in_off = 0, dst_off = 0;
     omr_status parsed = OMR_OK;
 };
-// The descriptor table of the jobs (plans[k]: job k's j2k_prepare) into T->pin_tab, up in one copy,
-// the workspace in T->d_coef, and K19a, K19b per level and K19c on the context's stream.  swap16:
-// 16-bit samples are stored byte-swapped.  status: the jobs' parsed; no kernel adds to it.
-omr_status j2k_decode_group(Ctx* ctx, SegPipe* T, const std::vector<J2kJob>& jobs, const std::vector<J2kPlan>& plans,
-                            bool swap16, const uint8_t* d_src, uint8_t* d_dst, std::vector<int32_t>& status);
+// What a decode group leaves for fetch_codec_statuses: st, the call's own result; the statuses its
+// kernels write, one word per entry of `live` (indices into the jobs) at `off` in T->d_tab and
+// T->pin_tab.  live empty: no kernel of the group reports anything.
+struct CodecLaunched {
+    omr_status st = OMR_OK;
+    size_t off = 0;
+    std::vector<int32_t> live;
+    CodecLaunched(omr_status s = OMR_OK) : st(s) {}
+};
+// The descriptor table of the jobs (plans[k]: job k's prepare) into T->pin_tab, up in one copy, the
+// workspace in T->d_coef, and the kernels on the context's stream: K17a, K17b, K17c, or K19a, K19b
+// per level and K19c (swap16: 16-bit samples are stored byte-swapped).  status: filled with the
+// jobs' parsed; K17's kernels add theirs through fetch_codec_statuses, K19's have none to add.
+CodecLaunched jpeg_decode_group(Ctx* ctx, SegPipe* T, const std::vector<CodecJob>& jobs, const std::vector<JpegPlan>& plans,
+                                int32_t samples, bool ycc, const uint8_t* d_src, uint8_t* d_dst, std::vector<int32_t>& status);
+CodecLaunched j2k_decode_group(Ctx* ctx, SegPipe* T, const std::vector<CodecJob>& jobs, const std::vector<J2kPlan>& plans,
+                               bool swap16, const uint8_t* d_src, uint8_t* d_dst, std::vector<int32_t>& status);
+// The end of every decode group: the kernels' status words back (when there are any), the one
+// synchronisation of the stream, and the words into status[live[j]].
+omr_status fetch_codec_statuses(Ctx* ctx, SegPipe* T, const CodecLaunched& launched, std::vector<int32_t>& status);
+
+// The body of omr_{jpeg,j2k}_decode_batch_device behind its checks and its prepare loop: the parsed
+// jobs' streams (src + offsets[k], lengths[k]) laid out 16-byte aligned in the pipe's pinned buffer
+// (grown under "<codec> staging") and uploaded, decode(status) launched -- it finds the jobs' in_off
+// set and the bytes at T->d_in -- and the statuses fetched and copied to status_out[0, jobs.size()).
+using DecodeGroupFn = std::function<CodecLaunched(std::vector<int32_t>& status)>;
+omr_status decode_batch_staged(Ctx* ctx, SegPipe* T, const char* codec, std::vector<CodecJob>& jobs, const uint8_t* src,
+                               const uint64_t* offsets, const uint32_t* lengths, const DecodeGroupFn& decode,
+                               int32_t* status_out);
 
 // Growth of a pipe's buffers (omr_segread.cpp): device memory, and a pinned buffer with its device
 // twin of at least `total` bytes (by half again when they grow); what: the words of the message.
@@ -268,18 +272,26 @@ omr_status grow_pinned(Ctx* c, void*& pin, void*& dev, size_t& cap, size_t total
 
 // ---- the device route (omr_segread.cpp) ---------------------------------------------------------
 
-// n regions, checked by the caller, in groups within the staging budgets.
-omr_status read_regions(Ctx* ctx, SegSource& src, const omr_raw_tile_request* reqs, int32_t n, int32_t width,
-                        int32_t height, void* d_dst, int64_t region_stride_bytes);
+// What the four front-end entry points check before they read: the image's side of it.  in_bounds:
+// whether a width x height region at a request lies inside level `level` (called once the level is
+// known to exist).
+struct SegImageDims {
+    int32_t level, n_levels, bpp, sc;
+    std::function<bool(const omr_raw_tile_request&, int32_t width, int32_t height)> in_bounds;
+};
 
-// The body of omr_render_*_tiles after its argument checks: the active channels compacted, groups
-// of kRenderGroupBytes read by `read` (the front-end's own read_regions entry: regions, count,
-// destination, stride) into the pipe's region buffer, rendered, and copied back when the output is
-// on the host.
-using ReadRegionsFn = std::function<omr_status(const omr_raw_tile_request*, int32_t, void*, int64_t)>;
-omr_status render_tiles(omr_ctx* ctx, const SegSource& src, const ReadRegionsFn& read, const omr_quantum_def* qdef,
-                        const omr_channel_binding* channels, int32_t size_c, const omr_tile_request* reqs, int32_t n,
-                        int32_t width, int32_t height, int32_t flip_h, int32_t flip_v, uint32_t* argb_out,
-                        int32_t out_on_device);
+// omr_{tiff,zarr}_image_read_regions_device behind its null checks of ctx and img: the argument
+// checks, their messages under S.tag, then n regions in groups within the staging budgets.  S may
+// have been made for a level outside the image; it is refused here before its geometry is read.
+omr_status read_regions_checked(Ctx* ctx, SegSource& S, const SegImageDims& im, const omr_raw_tile_request* reqs, int32_t n,
+                                int32_t width, int32_t height, void* d_dst, int64_t region_stride_bytes);
+
+// omr_render_{tiff,zarr}_tiles behind the same two checks: its argument checks, the active
+// channels compacted, groups of kRenderGroupBytes read by read_regions_checked into the pipe's
+// region buffer, rendered, and copied back when the output is on the host.
+omr_status render_tiles_checked(omr_ctx* ctx, SegSource& S, const SegImageDims& im, const omr_quantum_def* qdef,
+                                const omr_channel_binding* channels, int32_t size_c, const omr_tile_request* reqs, int32_t n,
+                                int32_t width, int32_t height, int32_t flip_h, int32_t flip_v, uint32_t* argb_out,
+                                int32_t out_on_device);
 
 }  // namespace omr

@@ -510,10 +510,11 @@ struct TiffSource final : omr::SegSource {
     const omr_tiff_image* im;
     size_t level;
     TiffSource(const omr_tiff_image* img, int32_t lv) : im(img), level((size_t)lv) {
-        const Level& L = im->levels[level];
         kind = omr::SegKind::tiff;
         tag = "tiff";
         noun = "segment";
+        if (lv < 0 || level >= im->levels.size()) return;   // the checks of the entry points refuse it (dims())
+        const Level& L = im->levels[level];
         geom.seg_w = L.seg_w; geom.seg_h = L.seg_h; geom.across = L.across; geom.down = L.down; geom.bpp = im->bpp;
         geom.spp = im->spp;
         switch (im->compression) {                        // K13a, K14a, K16a
@@ -528,6 +529,12 @@ struct TiffSource final : omr::SegSource {
         swap = im->big == host_little_endian();
         pt = im->pt; big = im->big;
         jpeg_ycc = im->jpeg_ycc;
+    }
+    omr::SegImageDims dims() const {
+        return {(int32_t)level, (int32_t)im->levels.size(), im->bpp, im->sc,
+                [this](const omr_raw_tile_request& r, int32_t w, int32_t h) {
+                    return region_in_bounds(im, im->levels[level], r.z, r.c, r.t, r.x, r.y, w, h);
+                }};
     }
     const uint8_t* jpeg_tables(const omr::SegKey& k, size_t* len) const override {
         const std::vector<uint8_t>& t = table(k).jpeg_tables;
@@ -742,19 +749,9 @@ omr_status omr_tiff_image_read_regions_device(omr_ctx* ctx, const omr_tiff_image
                                               const omr_raw_tile_request* reqs, int32_t n, int32_t width,
                                               int32_t height, void* d_dst, int64_t region_stride_bytes) {
     if (!ctx) return OMR_INVALID_ARGUMENT;
-    if (!img || n < 0 || (n && (!reqs || !d_dst))) return fail(ctx, OMR_INVALID_ARGUMENT, "tiff: null argument");
-    if (level < 0 || level >= (int32_t)img->levels.size()) return fail(ctx, OMR_INVALID_ARGUMENT, "tiff: no such level");
-    if (width < 0 || height < 0) return fail(ctx, OMR_INVALID_ARGUMENT, "tiff: bad region size");
-    const Level& L = img->levels[(size_t)level];
-    const int64_t region_bytes = (int64_t)width * height * img->bpp;
-    if (region_stride_bytes < region_bytes || region_stride_bytes % img->bpp ||
-        reinterpret_cast<uintptr_t>(d_dst) % (uintptr_t)img->bpp)
-        return fail(ctx, OMR_INVALID_ARGUMENT, "tiff: region stride or destination not a multiple of the sample size");
-    for (int32_t i = 0; i < n; ++i)
-        if (!region_in_bounds(img, L, reqs[i].z, reqs[i].c, reqs[i].t, reqs[i].x, reqs[i].y, width, height))
-            return fail(ctx, OMR_INVALID_ARGUMENT, "tiff: region " + std::to_string(i) + " outside the image");
+    if (!img) return fail(ctx, OMR_INVALID_ARGUMENT, "tiff: null argument");
     TiffSource src(img, level);
-    return read_regions(ctx, src, reqs, n, width, height, d_dst, region_stride_bytes);
+    return read_regions_checked(ctx, src, src.dims(), reqs, n, width, height, d_dst, region_stride_bytes);
 }
 
 omr_status omr_render_tiff_tiles(omr_ctx* ctx, const omr_tiff_image* img, int32_t level, const omr_quantum_def* qdef,
@@ -762,15 +759,10 @@ omr_status omr_render_tiff_tiles(omr_ctx* ctx, const omr_tiff_image* img, int32_
                                  int32_t n, int32_t width, int32_t height, int32_t flip_h, int32_t flip_v,
                                  uint32_t* argb_out, int32_t out_on_device) {
     if (!ctx) return OMR_INVALID_ARGUMENT;
-    if (!img || !qdef || !channels || !reqs || !argb_out || n < 0) return fail(ctx, OMR_INVALID_ARGUMENT, "null argument");
-    if (size_c != img->sc) return fail(ctx, OMR_INVALID_ARGUMENT, "channel bindings do not match the image's sizeC");
-    if (width <= 0 || height <= 0) return fail(ctx, OMR_INVALID_ARGUMENT, "bad tile size");
-    if (level < 0 || level >= (int32_t)img->levels.size()) return fail(ctx, OMR_INVALID_ARGUMENT, "tiff: no such level");
-    return render_tiles(ctx, TiffSource(img, level),
-                        [&](const omr_raw_tile_request* rr, int32_t count, void* d_dst, int64_t stride) {
-                            return omr_tiff_image_read_regions_device(ctx, img, level, rr, count, width, height, d_dst, stride);
-                        },
-                        qdef, channels, size_c, reqs, n, width, height, flip_h, flip_v, argb_out, out_on_device);
+    if (!img) return fail(ctx, OMR_INVALID_ARGUMENT, "null argument");
+    TiffSource src(img, level);
+    return render_tiles_checked(ctx, src, src.dims(), qdef, channels, size_c, reqs, n, width, height, flip_h, flip_v, argb_out,
+                                out_on_device);
 }
 
 }  // extern "C"

@@ -606,9 +606,11 @@ omr_status load_chunk(const omr_zarr_image* im, const Level& L, int32_t t, int32
 
 struct ZarrSource final : omr::SegSource {
     const omr_zarr_image* im;
-    const Level& L;
+    const int32_t level;
+    const Level& L;                      // of a level outside the image: the first; the entry points' checks refuse it (dims())
     std::vector<std::string> paths;      // of the group's chunks, from sizes() to read()
-    ZarrSource(const omr_zarr_image* img, int32_t level) : im(img), L(img->levels[(size_t)level]) {
+    ZarrSource(const omr_zarr_image* img, int32_t lv)
+        : im(img), level(lv), L(img->levels[lv >= 0 && (size_t)lv < img->levels.size() ? (size_t)lv : 0]) {
         kind = omr::SegKind::zarr;
         tag = "zarr";
         noun = "chunk";
@@ -617,6 +619,12 @@ struct ZarrSource final : omr::SegSource {
                 : im->comp == kBlosc ? omr::SegCodec::blosc : omr::SegCodec::none;
         blosc_inner = im->inner;
         pt = im->pt; big = im->big;
+    }
+    omr::SegImageDims dims() const {
+        return {level, (int32_t)im->levels.size(), im->bpp, im->sc,
+                [this](const omr_raw_tile_request& r, int32_t w, int32_t h) {
+                    return region_in_bounds(im, L, r.z, r.c, r.t, r.x, r.y, w, h);
+                }};
     }
     bool threaded(size_t chunks) const { return chunks >= 32; }
     int64_t plane_of(const omr_raw_tile_request& r) const override { return ((int64_t)r.t * im->sc + r.c) * im->sz + r.z; }
@@ -801,19 +809,9 @@ omr_status omr_zarr_image_read_regions_device(omr_ctx* ctx, const omr_zarr_image
                                               const omr_raw_tile_request* reqs, int32_t n, int32_t width,
                                               int32_t height, void* d_dst, int64_t region_stride_bytes) {
     if (!ctx) return OMR_INVALID_ARGUMENT;
-    if (!img || n < 0 || (n && (!reqs || !d_dst))) return fail(ctx, OMR_INVALID_ARGUMENT, "zarr: null argument");
-    if (level < 0 || level >= (int32_t)img->levels.size()) return fail(ctx, OMR_INVALID_ARGUMENT, "zarr: no such level");
-    if (width < 0 || height < 0) return fail(ctx, OMR_INVALID_ARGUMENT, "zarr: bad region size");
-    const Level& L = img->levels[(size_t)level];
-    const int64_t region_bytes = (int64_t)width * height * img->bpp;
-    if (region_stride_bytes < region_bytes || region_stride_bytes % img->bpp ||
-        reinterpret_cast<uintptr_t>(d_dst) % (uintptr_t)img->bpp)
-        return fail(ctx, OMR_INVALID_ARGUMENT, "zarr: region stride or destination not a multiple of the sample size");
-    for (int32_t i = 0; i < n; ++i)
-        if (!region_in_bounds(img, L, reqs[i].z, reqs[i].c, reqs[i].t, reqs[i].x, reqs[i].y, width, height))
-            return fail(ctx, OMR_INVALID_ARGUMENT, "zarr: region " + std::to_string(i) + " outside the image");
+    if (!img) return fail(ctx, OMR_INVALID_ARGUMENT, "zarr: null argument");
     ZarrSource src(img, level);
-    return read_regions(ctx, src, reqs, n, width, height, d_dst, region_stride_bytes);
+    return read_regions_checked(ctx, src, src.dims(), reqs, n, width, height, d_dst, region_stride_bytes);
 }
 
 omr_status omr_render_zarr_tiles(omr_ctx* ctx, const omr_zarr_image* img, int32_t level, const omr_quantum_def* qdef,
@@ -821,15 +819,10 @@ omr_status omr_render_zarr_tiles(omr_ctx* ctx, const omr_zarr_image* img, int32_
                                  int32_t n, int32_t width, int32_t height, int32_t flip_h, int32_t flip_v,
                                  uint32_t* argb_out, int32_t out_on_device) {
     if (!ctx) return OMR_INVALID_ARGUMENT;
-    if (!img || !qdef || !channels || !reqs || !argb_out || n < 0) return fail(ctx, OMR_INVALID_ARGUMENT, "null argument");
-    if (size_c != img->sc) return fail(ctx, OMR_INVALID_ARGUMENT, "channel bindings do not match the image's sizeC");
-    if (width <= 0 || height <= 0) return fail(ctx, OMR_INVALID_ARGUMENT, "bad tile size");
-    if (level < 0 || level >= (int32_t)img->levels.size()) return fail(ctx, OMR_INVALID_ARGUMENT, "zarr: no such level");
-    return render_tiles(ctx, ZarrSource(img, level),
-                        [&](const omr_raw_tile_request* rr, int32_t count, void* d_dst, int64_t stride) {
-                            return omr_zarr_image_read_regions_device(ctx, img, level, rr, count, width, height, d_dst, stride);
-                        },
-                        qdef, channels, size_c, reqs, n, width, height, flip_h, flip_v, argb_out, out_on_device);
+    if (!img) return fail(ctx, OMR_INVALID_ARGUMENT, "null argument");
+    ZarrSource src(img, level);
+    return render_tiles_checked(ctx, src, src.dims(), qdef, channels, size_c, reqs, n, width, height, flip_h, flip_v, argb_out,
+                                out_on_device);
 }
 
 }  // extern "C"

@@ -18,6 +18,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import lib
+from ._segimage import _SegImage
 
 _NP_NAMES = {_lib.PIXELS_INT8: "i1", _lib.PIXELS_UINT8: "u1", _lib.PIXELS_INT16: "i2", _lib.PIXELS_UINT16: "u2",
              _lib.PIXELS_INT32: "i4", _lib.PIXELS_UINT32: "u4", _lib.PIXELS_FLOAT: "f4", _lib.PIXELS_DOUBLE: "f8"}
@@ -381,9 +382,12 @@ def write_tiled_tiff(path, planes, levels=(), tile=(256, 256), rows_per_strip=No
     return result
 
 
-class TiffImage:
+class TiffImage(_SegImage):
     """An open tiled TIFF / OME-TIFF (omr_tiff_image).  The caller gives Z, C, T and the dimension
     order as for PixelBuffer; OME-XML is not parsed."""
+
+    _CLOSE, _GET_TILE = "omr_tiff_image_close", "omr_tiff_image_get_tile"
+    _READ_REGIONS, _RENDER_TILES = "omr_tiff_image_read_regions_device", "omr_render_tiff_tiles"
 
     def __init__(self, path, size_z=1, size_c=1, size_t=1, dimension_order="XYZCT", accept=()):
         """accept: the further forms a file may use, any of "deflate", "zstd", "predictor3" and
@@ -419,75 +423,6 @@ class TiffImage:
         n = lib.omr_tiff_image_level_sizes(self.h, sizes, i.n_levels)
         self.level_sizes = [[sizes[2 * k], sizes[2 * k + 1]] for k in range(n)]
 
-    def close(self):
-        if self.h:
-            lib.omr_tiff_image_close(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def getResolutionLevels(self):
-        return len(self.level_sizes)
-
-    def getResolutionDescriptions(self):
-        return [list(s) for s in self.level_sizes]
-
-    def get_tile(self, level, z, c, t, x, y, w, h):
-        """The host route: [h][w] array in the file's byte order (omr_tiff_image_get_tile)."""
-        if w < 0 or h < 0:
-            raise _lib.OmrError(_lib.INVALID_ARGUMENT, f"tile {w}x{h} out of bounds")
-        out = np.empty((h, w), dtype=self.dtype)
-        _lib.check(lib.omr_tiff_image_get_tile(self.h, int(level), z, c, t, x, y, w, h, out.ctypes.data,
-                                               max(out.nbytes, 1)))
-        return out
-
-    def read_regions(self, ctx, level, reqs, w, h, out=None, region_stride=None):
-        """reqs = [(z, c, t, x, y)], every region w x h of `level`, read and decoded on ctx's GPU
-        (omr_tiff_image_read_regions_device).  Returns a device uint8 tensor [n][region_stride]
-        (allocated when out is None; region_stride defaults to the region's bytes rounded up to
-        16): region i is its first w*h*bytes_per_pixel bytes, rows packed, file byte order."""
-        import torch
-        n = len(reqs)
-        bpp = _lib.BYTES_PER_PIXEL[self.pixel_type]
-        if region_stride is None:
-            region_stride = (w * h * bpp + 15) // 16 * 16
-        if out is None:
-            out = torch.zeros((max(n, 1), max(region_stride, 1)), dtype=torch.uint8, device=f"cuda:{ctx.device}")
-            ctx.order_after_torch()
-        tab = (_lib.RawTileRequest * max(n, 1))()
-        for i, r in enumerate(reqs):
-            tab[i].z, tab[i].c, tab[i].t, tab[i].x, tab[i].y = [int(v) for v in r]
-        _lib.check(lib.omr_tiff_image_read_regions_device(ctx.h, self.h, int(level), ctypes.addressof(tab), n, int(w),
-                                                          int(h), out.data_ptr(), int(region_stride)), ctx.h)
-        return out[:n]
-
-    def render_tiles(self, ctx, qdef, channels, level, requests, width, height, out=None, flip_h=False,
-                     flip_v=False, bindings=None):
-        """Context.render_pixel_buffer_tiles for this image's `level` (omr_render_tiff_tiles):
-        requests = [(z, t, x, y)]; out: host numpy [n][h][w] uint32 (allocated when None) or a
-        device tensor (rendered in place)."""
-        from .context import _ptr, make_bindings
-        arr, keep = make_bindings(channels) if bindings is None else bindings
-        n = len(requests)
-        reqs = (_lib.TileRequest * max(n, 1))(*[_lib.TileRequest(*r) for r in requests])
-        on_device = out is not None and hasattr(out, "data_ptr")
-        if out is None:
-            out = np.empty((n, height, width), dtype=np.uint32)
-        _lib.check(lib.omr_render_tiff_tiles(ctx.h, self.h, int(level), ctypes.byref(qdef), arr, len(channels), reqs, n,
-                                             int(width), int(height), int(flip_h), int(flip_v), _ptr(out),
-                                             int(on_device)), ctx.h)
-        return out
-
 
 def lzw_decode_host(stream, expected):
     """The host LZW decoder alone (omr_lzw_decode_host): `expected` bytes, or OmrError(INTERNAL)."""
@@ -497,19 +432,31 @@ def lzw_decode_host(stream, expected):
     return out[:int(expected)].tobytes()
 
 
+def _decode_host_frame(call, stream, width, height, samples, dtype=np.uint8, tables=None, failed=None):
+    """The buffers of a host decode of one frame: call(tables pointer, tables size, source pointer,
+    source size, output pointer, why buffer, its size) -> status; anything but OK raises OmrError
+    with `failed`, or with what the call wrote into the why buffer.  Returns [height][width] or
+    [height][width][samples] of dtype."""
+    src = np.frombuffer(bytes(stream), dtype=np.uint8)
+    tab = np.frombuffer(bytes(tables or b""), dtype=np.uint8)
+    n = int(width) * int(height) * int(samples)
+    out = np.zeros(max(n, 1), dtype=dtype)
+    why = ctypes.create_string_buffer(160)
+    st = call(tab.ctypes.data if tab.size else None, tab.size, src.ctypes.data if src.size else None, src.size,
+              out.ctypes.data, why, 160)
+    if st != _lib.OK:
+        raise _lib.OmrError(st, failed or why.value.decode())
+    out = out[:n]
+    return out.reshape(height, width) if samples == 1 else out.reshape(height, width, samples)
+
+
 def jpeg_decode_host(stream, width, height, samples=1, ycbcr=False, tables=None):
     """The host JPEG decoder alone (omr_jpeg_decode_host): [height][width] or [height][width][3]
     uint8, or OmrError (INVALID_ARGUMENT: a form out of scope, named in the message; INTERNAL: damage)."""
-    src = np.frombuffer(bytes(stream), dtype=np.uint8)
-    tab = np.frombuffer(bytes(tables or b""), dtype=np.uint8)
-    out = np.zeros(max(int(width) * int(height) * int(samples), 1), dtype=np.uint8)
-    why = ctypes.create_string_buffer(160)
-    st = lib.omr_jpeg_decode_host(tab.ctypes.data if tab.size else None, tab.size, src.ctypes.data if src.size else None,
-                                  src.size, int(width), int(height), int(samples), int(bool(ycbcr)), out.ctypes.data, why, 160)
-    if st != _lib.OK:
-        raise _lib.OmrError(st, why.value.decode())
-    out = out[:int(width) * int(height) * int(samples)]
-    return out.reshape(height, width) if samples == 1 else out.reshape(height, width, samples)
+    return _decode_host_frame(
+        lambda tab, ntab, src, nsrc, out, why, nwhy: lib.omr_jpeg_decode_host(
+            tab, ntab, src, nsrc, int(width), int(height), int(samples), int(bool(ycbcr)), out, why, nwhy),
+        stream, width, height, samples, tables=tables)
 
 
 def jpeg_decode_host_split(stream, width, height, samples=1, ycbcr=False, tables=None, subsequence_bits=1024, lanes=256):
@@ -517,17 +464,12 @@ def jpeg_decode_host_split(stream, width, height, samples=1, ycbcr=False, tables
     workgroup of `lanes` lanes over subsequences of subsequence_bits bits, played by host loops.
     Returns (pixels, stats): the pixels and errors of jpeg_decode_host, and a dict with the
     subsequences, rounds, max_settle_iterations and redecodes of the decode."""
-    src = np.frombuffer(bytes(stream), dtype=np.uint8)
-    tab = np.frombuffer(bytes(tables or b""), dtype=np.uint8)
-    out = np.zeros(max(int(width) * int(height) * int(samples), 1), dtype=np.uint8)
     stats = _lib.JpegSplitStats()
-    st = lib.omr_jpeg_decode_host_split(tab.ctypes.data if tab.size else None, tab.size, src.ctypes.data if src.size else None,
-                                        src.size, int(width), int(height), int(samples), int(bool(ycbcr)),
-                                        int(subsequence_bits), int(lanes), out.ctypes.data, ctypes.byref(stats))
-    if st != _lib.OK:
-        raise _lib.OmrError(st, "jpeg: split decode failed")
-    out = out[:int(width) * int(height) * int(samples)]
-    px = out.reshape(height, width) if samples == 1 else out.reshape(height, width, samples)
+    px = _decode_host_frame(
+        lambda tab, ntab, src, nsrc, out, why, nwhy: lib.omr_jpeg_decode_host_split(
+            tab, ntab, src, nsrc, int(width), int(height), int(samples), int(bool(ycbcr)), int(subsequence_bits),
+            int(lanes), out, ctypes.byref(stats)),
+        stream, width, height, samples, tables=tables, failed="jpeg: split decode failed")
     return px, {f: int(getattr(stats, f)) for f, _ in _lib.JpegSplitStats._fields_}
 
 
@@ -545,16 +487,10 @@ def j2k_decode_host(stream, width, height, samples=1, bits=8):
     """The host JPEG 2000 decoder alone (omr_j2k_decode_host): [height][width] or [height][width][3],
     uint8 or uint16, or OmrError (INVALID_ARGUMENT: a form out of scope, named in the message;
     INTERNAL: damage)."""
-    src = np.frombuffer(bytes(stream), dtype=np.uint8)
-    n = int(width) * int(height) * int(samples)
-    out = np.zeros(max(n, 1), dtype=np.uint16 if bits == 16 else np.uint8)
-    why = ctypes.create_string_buffer(160)
-    st = lib.omr_j2k_decode_host(src.ctypes.data if src.size else None, src.size, int(width), int(height), int(samples),
-                                 int(bits), out.ctypes.data, why, 160)
-    if st != _lib.OK:
-        raise _lib.OmrError(st, why.value.decode())
-    out = out[:n]
-    return out.reshape(height, width) if samples == 1 else out.reshape(height, width, samples)
+    return _decode_host_frame(
+        lambda tab, ntab, src, nsrc, out, why, nwhy: lib.omr_j2k_decode_host(
+            src, nsrc, int(width), int(height), int(samples), int(bits), out, why, nwhy),
+        stream, width, height, samples, dtype=np.uint16 if bits == 16 else np.uint8)
 
 
 def j2k_stream_forms(stream):
@@ -565,9 +501,12 @@ def j2k_stream_forms(stream):
     return {n for k, n in enumerate(_lib.J2K_FORM_NAMES) if bits.value >> k & 1}
 
 
-def j2k_decode_batch_device(ctx, streams, sizes, samples=1, bits=8):
-    """K19 alone (omr_j2k_decode_batch_device): streams[i] with a frame of sizes[i] = (width, height),
-    decoded on ctx's GPU.  Returns ([arrays, [h][w] or [h][w][3], uint8 or uint16], [status per stream])."""
+def _decode_batch_device(ctx, streams, sizes, samples, bytes_per_sample, view, call):
+    """The buffers of a batch decode on ctx's GPU: streams[i] with a frame of sizes[i] = (width,
+    height) and samples of bytes_per_sample bytes; call(blob, offsets, lengths, widths, heights,
+    n, output, output offsets, statuses) -> status makes the lib call, all but n as addresses.  The
+    outputs lie 16-byte aligned with at least 16 guard bytes of 0xA5 behind each, which must come
+    back untouched.  Returns ([arrays, [h][w] or [h][w][samples], viewed as `view`], [status per stream])."""
     import torch
     n = len(streams)
     blob = np.frombuffer(b"".join(bytes(s) for s in streams) or b"\0", dtype=np.uint8)
@@ -575,50 +514,39 @@ def j2k_decode_batch_device(ctx, streams, sizes, samples=1, bits=8):
     offs = np.concatenate([[0], np.cumsum(lens[:-1], dtype=np.uint64)]).astype(np.uint64) if n else np.zeros(0, np.uint64)
     ws = np.array([int(w) for w, _ in sizes], dtype=np.int32)
     hs = np.array([int(h) for _, h in sizes], dtype=np.int32)
-    nbytes = [int(w) * int(h) * samples * (bits // 8) for w, h in sizes]
+    nbytes = [int(w) * int(h) * samples * bytes_per_sample for w, h in sizes]
     doffs = np.array([sum((b + 31) // 16 * 16 for b in nbytes[:i]) for i in range(n)], dtype=np.uint64)
     total = sum((b + 31) // 16 * 16 for b in nbytes)
     out = torch.full((max(total, 16),), 0xA5, dtype=torch.uint8, device=f"cuda:{ctx.device}")
     ctx.order_after_torch()
     status = np.zeros(max(n, 1), dtype=np.int32)
-    _lib.check(lib.omr_j2k_decode_batch_device(ctx.h, blob.ctypes.data, offs.ctypes.data, lens.ctypes.data, ws.ctypes.data,
-                                               hs.ctypes.data, n, int(samples), int(bits), out.data_ptr(), doffs.ctypes.data,
-                                               status.ctypes.data), ctx.h)
+    _lib.check(call(blob.ctypes.data, offs.ctypes.data, lens.ctypes.data, ws.ctypes.data, hs.ctypes.data, n, out.data_ptr(),
+                    doffs.ctypes.data, status.ctypes.data), ctx.h)
     host = out.cpu().numpy()
     got = []
     for i, (w, h) in enumerate(sizes):
         a = host[int(doffs[i]):int(doffs[i]) + nbytes[i]]
         assert (host[int(doffs[i]) + nbytes[i]:int(doffs[i]) + (nbytes[i] + 31) // 16 * 16] == 0xA5).all(), "bytes behind a stream overwritten"
-        a = a.view("<u2") if bits == 16 else a
+        a = a.view(view)
         got.append(a.reshape(h, w) if samples == 1 else a.reshape(h, w, samples))
     return got, [int(v) for v in status[:n]]
+
+
+def j2k_decode_batch_device(ctx, streams, sizes, samples=1, bits=8):
+    """K19 alone (omr_j2k_decode_batch_device): streams[i] with a frame of sizes[i] = (width, height),
+    decoded on ctx's GPU.  Returns ([arrays, [h][w] or [h][w][3], uint8 or uint16], [status per stream])."""
+    return _decode_batch_device(
+        ctx, streams, sizes, samples, bits // 8, "<u2" if bits == 16 else "u1",
+        lambda blob, offs, lens, ws, hs, n, out, doffs, status: lib.omr_j2k_decode_batch_device(
+            ctx.h, blob, offs, lens, ws, hs, n, int(samples), int(bits), out, doffs, status))
 
 
 def jpeg_decode_batch_device(ctx, streams, sizes, samples=1, ycbcr=False, tables=None):
     """K17 alone (omr_jpeg_decode_batch_device): streams[i] with a frame of sizes[i] = (width,
     height), decoded on ctx's GPU.  Returns ([uint8 arrays, [h][w] or [h][w][3]], [status per stream])."""
-    import torch
-    n = len(streams)
-    blob = np.frombuffer(b"".join(bytes(s) for s in streams) or b"\0", dtype=np.uint8)
-    lens = np.array([len(s) for s in streams], dtype=np.uint32)
-    offs = np.concatenate([[0], np.cumsum(lens[:-1], dtype=np.uint64)]).astype(np.uint64) if n else np.zeros(0, np.uint64)
-    ws = np.array([int(w) for w, _ in sizes], dtype=np.int32)
-    hs = np.array([int(h) for _, h in sizes], dtype=np.int32)
-    nbytes = [int(w) * int(h) * samples for w, h in sizes]
-    doffs = np.array([sum((b + 31) // 16 * 16 for b in nbytes[:i]) for i in range(n)], dtype=np.uint64)
-    total = sum((b + 31) // 16 * 16 for b in nbytes)
-    out = torch.full((max(total, 16),), 0xA5, dtype=torch.uint8, device=f"cuda:{ctx.device}")
-    ctx.order_after_torch()
-    status = np.zeros(max(n, 1), dtype=np.int32)
     tab = np.frombuffer(bytes(tables or b""), dtype=np.uint8)
-    _lib.check(lib.omr_jpeg_decode_batch_device(ctx.h, tab.ctypes.data if tab.size else None, tab.size, blob.ctypes.data,
-                                                offs.ctypes.data, lens.ctypes.data, ws.ctypes.data, hs.ctypes.data, n,
-                                                int(samples), int(bool(ycbcr)), out.data_ptr(), doffs.ctypes.data,
-                                                status.ctypes.data), ctx.h)
-    host = out.cpu().numpy()
-    got = []
-    for i, (w, h) in enumerate(sizes):
-        a = host[int(doffs[i]):int(doffs[i]) + nbytes[i]]
-        assert (host[int(doffs[i]) + nbytes[i]:int(doffs[i]) + (nbytes[i] + 31) // 16 * 16] == 0xA5).all(), "bytes behind a stream overwritten"
-        got.append(a.reshape(h, w) if samples == 1 else a.reshape(h, w, samples))
-    return got, [int(v) for v in status[:n]]
+    return _decode_batch_device(
+        ctx, streams, sizes, samples, 1, "u1",
+        lambda blob, offs, lens, ws, hs, n, out, doffs, status: lib.omr_jpeg_decode_batch_device(
+            ctx.h, tab.ctypes.data if tab.size else None, tab.size, blob, offs, lens, ws, hs, n, int(samples),
+            int(bool(ycbcr)), out, doffs, status))

@@ -21,6 +21,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import lib
+from ._segimage import _SegImage
 from .tiffimage import _NP_NAMES
 
 
@@ -459,12 +460,14 @@ def write_zarr(path, planes, levels=(), chunk=(256, 256), byteorder="<", compres
                                 f.write(raw)
 
 
-class ZarrImage:
+class ZarrImage(_SegImage):
     """An open OME-Zarr image group (omr_zarr_image): `path` is the image (series) group, for
     instance image.zarr/0.  Z, C and T come from the array shape; OME-XML is not read."""
 
     CODECS = {"zlib": _lib.ZARR_CODEC_ZLIB, "blosc": _lib.ZARR_CODEC_BLOSC,
               "blosc-zstd": _lib.ZARR_CODEC_BLOSC_ZSTD, "zstd": _lib.ZARR_CODEC_ZSTD}
+    _CLOSE, _GET_TILE = "omr_zarr_image_close", "omr_zarr_image_get_tile"
+    _READ_REGIONS, _RENDER_TILES = "omr_zarr_image_read_regions_device", "omr_render_zarr_tiles"
 
     def __init__(self, path, codecs=("zlib",)):
         """codecs: the chunk compressors accepted, ("zlib",) as omr_zarr_image_open or any of
@@ -496,83 +499,11 @@ class ZarrImage:
         n = lib.omr_zarr_image_level_sizes(self.h, sizes, i.n_levels)
         self.level_sizes = [[sizes[2 * k], sizes[2 * k + 1]] for k in range(n)]
 
-    def close(self):
-        if self.h:
-            lib.omr_zarr_image_close(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def getResolutionLevels(self):
-        return len(self.level_sizes)
-
-    def getResolutionDescriptions(self):
-        return [list(s) for s in self.level_sizes]
-
-    def get_tile(self, level, z, c, t, x, y, w, h):
-        """The host route: [h][w] array in the arrays' byte order (omr_zarr_image_get_tile)."""
-        if w < 0 or h < 0:
-            raise _lib.OmrError(_lib.INVALID_ARGUMENT, f"tile {w}x{h} out of bounds")
-        out = np.empty((h, w), dtype=self.dtype)
-        _lib.check(lib.omr_zarr_image_get_tile(self.h, int(level), z, c, t, x, y, w, h, out.ctypes.data,
-                                               max(out.nbytes, 1)))
-        return out
-
-    def read_regions(self, ctx, level, reqs, w, h, out=None, region_stride=None):
-        """reqs = [(z, c, t, x, y)], every region w x h of `level`, read and inflated on ctx's GPU
-        (omr_zarr_image_read_regions_device).  Returns a device uint8 tensor [n][region_stride]
-        (allocated when out is None; region_stride defaults to the region's bytes rounded up to
-        16): region i is its first w*h*bytes_per_pixel bytes, rows packed, the arrays' byte order."""
-        import torch
-        n = len(reqs)
-        bpp = _lib.BYTES_PER_PIXEL[self.pixel_type]
-        if region_stride is None:
-            region_stride = (w * h * bpp + 15) // 16 * 16
-        if out is None:
-            out = torch.zeros((max(n, 1), max(region_stride, 1)), dtype=torch.uint8, device=f"cuda:{ctx.device}")
-            ctx.order_after_torch()
-        tab = (_lib.RawTileRequest * max(n, 1))()
-        for i, r in enumerate(reqs):
-            tab[i].z, tab[i].c, tab[i].t, tab[i].x, tab[i].y = [int(v) for v in r]
-        _lib.check(lib.omr_zarr_image_read_regions_device(ctx.h, self.h, int(level), ctypes.addressof(tab), n, int(w),
-                                                          int(h), out.data_ptr(), int(region_stride)), ctx.h)
-        return out[:n]
-
-    def render_tiles(self, ctx, qdef, channels, level, requests, width, height, out=None, flip_h=False,
-                     flip_v=False, bindings=None):
-        """Context.render_pixel_buffer_tiles for this image's `level` (omr_render_zarr_tiles):
-        requests = [(z, t, x, y)]; out: host numpy [n][h][w] uint32 (allocated when None) or a
-        device tensor (rendered in place)."""
-        from .context import _ptr, make_bindings
-        arr, keep = make_bindings(channels) if bindings is None else bindings
-        n = len(requests)
-        reqs = (_lib.TileRequest * max(n, 1))(*[_lib.TileRequest(*r) for r in requests])
-        on_device = out is not None and hasattr(out, "data_ptr")
-        if out is None:
-            out = np.empty((n, height, width), dtype=np.uint32)
-        _lib.check(lib.omr_render_zarr_tiles(ctx.h, self.h, int(level), ctypes.byref(qdef), arr, len(channels), reqs, n,
-                                             int(width), int(height), int(flip_h), int(flip_v), _ptr(out),
-                                             int(on_device)), ctx.h)
-        return out
-
 
 def inflate_host(stream, expected):
     """The host inflate alone (omr_inflate_host): a zlib stream into exactly `expected` bytes, or
     OmrError(INTERNAL)."""
-    src = np.frombuffer(bytes(stream), dtype=np.uint8)
-    out = np.zeros(max(int(expected), 1), dtype=np.uint8)
-    _lib.check(lib.omr_inflate_host(src.ctypes.data if src.size else None, src.size, out.ctypes.data, int(expected)))
-    return out[:int(expected)].tobytes()
+    return _decode_host(lib.omr_inflate_host, stream, expected)
 
 
 def _decode_host(fn, stream, expected):

@@ -18,11 +18,12 @@ int bytes_per_pixel(int32_t t) {
     }
 }
 omr_status fail(Ctx*, omr_status s, const std::string&) { return s; }
-omr_status read_regions(Ctx*, SegSource&, const omr_raw_tile_request*, int32_t, int32_t, int32_t, void*, int64_t) {
+omr_status read_regions_checked(Ctx*, SegSource&, const SegImageDims&, const omr_raw_tile_request*, int32_t, int32_t, int32_t,
+                                void*, int64_t) {
     return OMR_DEVICE;
 }
-omr_status render_tiles(omr_ctx*, const SegSource&, const ReadRegionsFn&, const omr_quantum_def*, const omr_channel_binding*,
-                        int32_t, const omr_tile_request*, int32_t, int32_t, int32_t, int32_t, int32_t, uint32_t*, int32_t) {
+omr_status render_tiles_checked(omr_ctx*, SegSource&, const SegImageDims&, const omr_quantum_def*, const omr_channel_binding*,
+                                int32_t, const omr_tile_request*, int32_t, int32_t, int32_t, int32_t, int32_t, uint32_t*, int32_t) {
     return OMR_DEVICE;
 }
 }  // namespace omr

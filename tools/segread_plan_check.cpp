@@ -195,6 +195,14 @@ int main() {
     CHECK(omr::group_size(7, omr::kRenderGroupBytes, omr::kRenderGroupBytes / 4) == 4);
     CHECK(omr::read_bytes_per_request(make_case(16, 8, 2, true).g, 17, 9) == 3u * 3u * 256u);
     CHECK(omr::read_bytes_per_request(make_case(kW, 8, 1, false).g, 1, 1) == 2u * 2u * 320u);
+    // a layout without stream rows (the image codecs'): the placements lie right behind the padded bytes
+    for (size_t in_bytes : {(size_t)0, (size_t)1, (size_t)255, (size_t)256, (size_t)257, (size_t)4096 + 16})
+        for (size_t place_bytes : {(size_t)0, (size_t)48, (size_t)4800}) {
+            const omr::TableLayout t(in_bytes, 0, place_bytes, false);
+            CHECK(t.o_place == (in_bytes + 255) / 256 * 256);
+            CHECK(t.up_bytes == t.o_place + place_bytes);
+            CHECK(t.total >= t.up_bytes);
+        }
     std::printf(g_fail ? "segread_plan_check: %d check(s) failed\n" : "segread_plan_check: ok\n", g_fail);
     return g_fail ? 1 : 0;
 }

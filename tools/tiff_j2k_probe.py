@@ -141,9 +141,11 @@ def main():
                             per[kind] = per.get(kind, 0.0) + ms
                         for kind, ms in per.items():
                             kinds.setdefault(kind, []).append(ms)
+                        launches = {str(kind): sum(1 for _, k in tm if k == kind) for kind in sorted(per)}
                 ctx.enable_kernel_timing(False)
                 run = {"requests": len(positions), "region_bytes": region_bytes, "wall_s": series(walls),
                        "region_gb_per_s_wall": region_bytes / statistics.median(walls) / 1e9}
+                run["launches_per_pass"] = launches              # of the last pass, by timing kind
                 for name, kind in (("k19a_t1", 41), ("k19b_idwt53", 42), ("k19c_pixels", 43), ("k13b_place", 31), ("k2_render", 2)):
                     if kind in kinds:
                         run[name + "_ms_per_pass"] = series(kinds[kind])

@@ -145,9 +145,11 @@ def main():
                             per[kind] = per.get(kind, 0.0) + ms
                         for kind, ms in per.items():
                             kinds.setdefault(kind, []).append(ms)
+                        launches = {str(kind): sum(1 for _, k in tm if k == kind) for kind in sorted(per)}
                 ctx.enable_kernel_timing(False)
                 run = {"requests": len(positions), "wall_s": series(walls),
                        "region_gb_per_s_wall": region_bytes / statistics.median(walls) / 1e9}
+                run["launches_per_pass"] = launches              # of the last pass, by timing kind
                 for name, kind in (("k17a_entropy", 36), ("k18a_entropy_split", 39), ("k18b_dc_sum", 40), ("k17b_idct", 37),
                                    ("k17c_pixels", 38), ("k14a_inflate", 32), ("k13b_place", 31), ("k2_render", 2)):
                     if kind in kinds:
