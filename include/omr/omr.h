@@ -135,7 +135,8 @@ void*       omr_ctx_get_stream(omr_ctx* ctx);
  * DC sums, in place of or beside 36 after omr_ctx_set_jpeg_split; 41 = JPEG 2000 code-block
  * decode, 42 = one level of the inverse 5/3 transform and 43 = JPEG 2000 colour / level shift /
  * store: omr_j2k_decode_batch_device and, in front of 31, omr_tiff_image_read_regions_device on a
- * JPEG 2000 image).
+ * JPEG 2000 image; 44 = one level of the inverse 9/7 transform, in place of or beside 42 for
+ * irreversible streams).
  */
 omr_status  omr_ctx_enable_kernel_timing(omr_ctx* ctx, int32_t enable);
 int32_t     omr_ctx_kernel_timings(omr_ctx* ctx, float* ms_out, int32_t* kind_out, int32_t cap);
@@ -1081,7 +1082,7 @@ omr_status omr_tiff_image_open(const char* path, int32_t size_z, int32_t size_c,
 #define OMR_TIFF_ACCEPT_ZSTD       2u   /* Compression 50000: one Zstandard frame per segment     */
 #define OMR_TIFF_ACCEPT_PREDICTOR3 4u   /* floating-point predictor, float and double samples     */
 #define OMR_TIFF_ACCEPT_SAMPLES    8u   /* SamplesPerPixel 2..4, PlanarConfiguration 1 (chunky)   */
-/* (16: OMR_TIFF_ACCEPT_JPEG, K17; 32: OMR_TIFF_ACCEPT_JPEG2000, K19 -- both further down) */
+/* (16: OMR_TIFF_ACCEPT_JPEG, K17; 32: OMR_TIFF_ACCEPT_JPEG2000, K19; 64: OMR_TIFF_ACCEPT_JPEG2000_LOSSY, K20 -- all further down) */
 typedef struct omr_tiff_open_options {
     uint32_t struct_size;                              /* sizeof(omr_tiff_open_options) */
     uint32_t accept;                                   /* OMR_TIFF_ACCEPT_* bits */
@@ -1503,7 +1504,8 @@ omr_status omr_jpeg_decode_host_split(const uint8_t* tables, size_t tables_lengt
  * tests/golden/tiff_j2k.npz.
  *
  * OMR_INVALID_ARGUMENT, the message naming the form: the irreversible 9/7 transform and
- * quantisation styles 1 and 2; any code-block style bit (bypass, reset, termination on each pass,
+ * quantisation styles 1 and 2 (K20, further down, takes them behind switches of its own); any
+ * code-block style bit (bypass, reset, termination on each pass,
  * vertically causal, predictable termination, segmentation symbols); SOP or EPH; COC, QCC, RGN,
  * POC, PPM, PPT; several tiles or tile-parts; non-zero offsets; subsampled or signed components; a
  * precision other than 8 or 16; a JP2 box wrapper; 16-bit with three samples.  OMR_INTERNAL
@@ -1564,6 +1566,64 @@ omr_status omr_j2k_stream_forms(const uint8_t* src, size_t length, uint64_t* for
 omr_status omr_j2k_decode_batch_device(omr_ctx* ctx, const uint8_t* src, const uint64_t* offsets, const uint32_t* lengths,
                                        const int32_t* widths, const int32_t* heights, int32_t n, int32_t samples,
                                        int32_t bits, uint8_t* d_dst, const uint64_t* dst_offsets, int32_t* status);
+
+/* ---- K20: JPEG 2000 TIFF segments, the irreversible path ("JPEG-2000 Lossy") ----
+ *
+ * OMR_TIFF_ACCEPT_JPEG2000_LOSSY in omr_tiff_image_open_ex admits the same four Compression
+ * numbers with segments coded by the irreversible 9/7 transform.  It implies nothing: 32 | 64 reads
+ * both kinds (the transform is a property of a segment, and one file may mix them), 64 alone opens
+ * the file and refuses a reversible segment by name when it is read, as 32 alone goes on refusing
+ * an irreversible one ("j2k: the irreversible 9/7 transform").  Compression 33003's components are
+ * passed through as stored, as K19 does; Aperio's YCbCr reading of that number is out of scope.
+ *
+ * Codestream forms: K19's, with the transform byte 0 (9/7), QCD style 1 (scalar derived: one
+ * exponent and mantissa, the other subbands' exponents derived from it) or 2 (scalar expounded:
+ * one pair per subband), and COD's MCT byte 1 meaning the irreversible colour transform.
+ * OMR_INVALID_ARGUMENT by name in addition to K19's list: 9/7 with QCD style 0, and 5/3 with style
+ * 1 or 2.
+ *
+ * Arithmetic (csrc/omr_j2kdec.h): float32 in a fixed order without contraction, the same functions
+ * on the host and on the device, so the two routes give the same bytes.  The reference is OpenJPEG
+ * 2.5.4: step = 0.5f * float((1 + mantissa / 2048) * 2^(precision - exponent)), coefficient =
+ * (float)(signed value with its fractional bit) * step; per level all rows, then all columns: the
+ * low-pass samples times 1.230174105f, the high-pass ones times 1.625732422f, then four lifting
+ * steps a + (left + right) * c with c = -0.443506852f (even places), -0.882911075f (odd),
+ * 0.052980118f (even), 1.586134342f (odd) and whole-sample symmetric extension, a line of one
+ * sample untouched; r = y + v * 1.402f, g = y - u * 0.34413f - v * 0.71414f, b = y + u * 1.772f;
+ * round to nearest, ties to even; add 2^(bits - 1); clamp.  tests/golden/tiff_j2k97.npz holds
+ * OpenJPEG's pixels and, per stream, the number of samples where the host decoder differs from
+ * them (by 1 at most).
+ */
+#define OMR_TIFF_ACCEPT_JPEG2000_LOSSY 64u   /* the same Compression numbers: irreversible (9/7) JPEG 2000 codestreams */
+#define OMR_J2K_ALLOW_IRREVERSIBLE 1u        /* flags of the _ex calls: take 9/7 streams as well as 5/3 ones */
+/* omr_j2k_decode_host with flags (0: the same call). */
+omr_status omr_j2k_decode_host_ex(const uint8_t* src, size_t length, int32_t width, int32_t height, int32_t samples,
+                                  int32_t bits, uint32_t flags, uint8_t* dst, char* why, size_t why_cap);
+/* What an irreversible stream shows beyond the OMR_J2K_FORM_* bits (bit f of *lossy_forms; 0 for a reversible stream). */
+enum {
+    OMR_J2K_LOSSY_FORM_W97 = 0,          /* the 9/7 transform */
+    OMR_J2K_LOSSY_FORM_QCD_EXPOUNDED,    /* QCD style 2 */
+    OMR_J2K_LOSSY_FORM_QCD_DERIVED,      /* QCD style 1 */
+    OMR_J2K_LOSSY_FORM_ICT,              /* three components with the irreversible colour transform */
+    OMR_J2K_LOSSY_FORM_NO_MCT_3,         /* three components without a transform */
+    OMR_J2K_LOSSY_FORM_TRUNCATED_BLOCK,  /* a code-block with fewer coding passes than its bit-planes allow */
+    OMR_J2K_LOSSY_FORM_LINE_OF_1,        /* a lifted line of one sample (it passes through) */
+    OMR_J2K_LOSSY_FORM_LINE_OF_2,        /* a lifted line of two samples */
+    OMR_J2K_LOSSY_FORM_BITS16,
+    OMR_J2K_LOSSY_FORM_COUNT
+};
+/* omr_j2k_stream_forms with flags; lossy_forms may be NULL. */
+omr_status omr_j2k_stream_forms_ex(const uint8_t* src, size_t length, uint32_t flags, uint64_t* forms, uint32_t* lossy_forms);
+/*
+ * omr_j2k_decode_batch_device with flags.  Reversible and irreversible streams may share a call:
+ * per level K19b (kind 42) runs for the reversible ones and K20b (kind 44, k_j2k_idwt97: one
+ * workgroup per 64 x 32 output tile of a level, staged in LDS with a halo of four samples) for the
+ * irreversible ones, neither when it has no stream; K19a and K19c serve both.
+ */
+omr_status omr_j2k_decode_batch_device_ex(omr_ctx* ctx, const uint8_t* src, const uint64_t* offsets, const uint32_t* lengths,
+                                          const int32_t* widths, const int32_t* heights, int32_t n, int32_t samples,
+                                          int32_t bits, uint32_t flags, uint8_t* d_dst, const uint64_t* dst_offsets,
+                                          int32_t* status);
 
 #ifdef __cplusplus
 }

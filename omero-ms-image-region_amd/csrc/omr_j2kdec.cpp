@@ -1,5 +1,5 @@
-// omr_j2kdec.cpp — K19, host half: reversible JPEG 2000 codestreams, the segments of a TIFF with
-// Compression 33003, 33004, 33005 or 34712.
+// omr_j2kdec.cpp — K19 and K20, host half: JPEG 2000 codestreams, reversible (K19) and irreversible
+// (K20), the segments of a TIFF with Compression 33003, 33004, 33005 or 34712.
 //
 // j2k_prepare parses the main header and the one tile-part header and walks tier 2 -- the packets
 // in the stream's progression order, the inclusion and zero-bit-plane tag trees, the pass counts,
@@ -18,7 +18,10 @@
 // of 8 or 16 bits without subsampling; the reversible 5/3 transform without quantisation (QCD style
 // 0), with the reversible colour transform when COD says so; 0..32 decomposition levels; every legal
 // code-block size; user precincts; 1..65535 layers; the five progression orders; COM (and the
-// pointer segments TLM, PLM, PLT, CRG, which say nothing the walk needs) skipped.
+// pointer segments TLM, PLM, PLT, CRG, which say nothing the walk needs) skipped.  For a caller that
+// takes irreversible streams (kJ2kTakeIrreversible) also the 9/7 transform with QCD style 1 or 2
+// and the irreversible colour transform: tier 2 and the code-blocks are the same, j2k_prepare adds
+// every block's quantiser step, and the decoder runs the float path of omr_j2kdec.h.
 //
 // Damage that cannot be seen: without the termination styles (which are refused) nothing in a
 // code-block's bytes can be checked, so a damaged packet BODY decodes to defined, in-bounds
@@ -139,6 +142,7 @@ bool tag_decode(TagTree& T, HeaderBits& B, uint32_t leaf, uint32_t threshold) {
 struct BandGeom {
     uint32_t orient = 0, w = 0, h = 0, ox = 0, oy = 0;     // its size and its place in the nested layout
     int32_t mb = 0;
+    float step = 0.f;                                      // K20: half the quantiser step (0: reversible)
 };
 struct PrecinctBand {
     uint32_t ncw = 0, nch = 0, first = 0;                  // its code-blocks: first .. first + ncw * nch in raster order
@@ -170,6 +174,9 @@ struct Header {
     uint8_t pp[33] = {0};
     uint8_t guard = 0;
     uint8_t expo[97] = {0};
+    uint16_t mant[97] = {0};
+    bool lossy = false;                                    // the 9/7 transform
+    int qstyle = 0;
     size_t body = 0, body_end = 0;
 };
 
@@ -177,7 +184,11 @@ size_t be16(const uint8_t* p) { return (size_t)p[0] << 8 | p[1]; }
 uint64_t be32(const uint8_t* p) { return (uint64_t)p[0] << 24 | (uint64_t)p[1] << 16 | (uint64_t)p[2] << 8 | p[3]; }
 
 // The main header and the tile-part header, up to SOD; then what follows the tile-part.
-omr_status parse_headers(const uint8_t* src, size_t len, int32_t w, int32_t h, int32_t samples, int32_t bits, Header& H, Fail& F) {
+omr_status parse_headers(const uint8_t* src, size_t len, int32_t w, int32_t h, int32_t samples, int32_t bits, uint32_t kinds,
+                         Header& H, Fail& F) {
+    const bool take97 = (kinds & kJ2kTakeIrreversible) != 0;
+    const uint8_t* qcd = nullptr;                          // QCD's body behind Sqcd, looked at once the transform is known
+    size_t qcd_n = 0;
     if (len >= 12 && be32(src) == 12 && be32(src + 4) == 0x6A502020u) return F.set(OMR_INVALID_ARGUMENT, "j2k: a JP2 box wrapper");
     if (len < 2 || src[0] != 0xFF || src[1] != 0x4F) return F.set(OMR_INTERNAL, "j2k: no SOC");
     size_t pos = 2;
@@ -248,8 +259,9 @@ omr_status parse_headers(const uint8_t* src, size_t len, int32_t w, int32_t h, i
             if (style & 16) return F.set(OMR_INVALID_ARGUMENT, "j2k: code-block style: predictable termination");
             if (style & 32) return F.set(OMR_INVALID_ARGUMENT, "j2k: code-block style: segmentation symbols");
             if (style & 0xC0) return F.set(OMR_INVALID_ARGUMENT, "j2k: code-block style of a later part of the standard");
-            if (p[9] == 0) return F.set(OMR_INVALID_ARGUMENT, "j2k: the irreversible 9/7 transform");
-            if (p[9] != 1) return F.set(OMR_INVALID_ARGUMENT, "j2k: a transform other than 5/3");
+            if (p[9] == 0 && !take97) return F.set(OMR_INVALID_ARGUMENT, "j2k: the irreversible 9/7 transform");
+            if (p[9] > 1) return F.set(OMR_INVALID_ARGUMENT, take97 ? "j2k: a transform other than 5/3 and 9/7" : "j2k: a transform other than 5/3");
+            H.lossy = p[9] == 0;
             if (n != (size_t)10 + (H.user_precincts ? (size_t)H.levels + 1 : 0)) return F.set(OMR_INTERNAL, "j2k: bad COD");
             for (int r = 0; r <= H.levels; ++r) H.pp[r] = H.user_precincts ? p[10 + r] : 0xFF;
             have_cod = true;
@@ -259,12 +271,13 @@ omr_status parse_headers(const uint8_t* src, size_t len, int32_t w, int32_t h, i
             if (in_tile) return F.set(OMR_INVALID_ARGUMENT, "j2k: QCD in a tile-part header");
             if (n < 1) return F.set(OMR_INTERNAL, "j2k: bad QCD");
             const int style = p[0] & 31;
-            if (style == 1) return F.set(OMR_INVALID_ARGUMENT, "j2k: scalar derived quantisation");
-            if (style == 2) return F.set(OMR_INVALID_ARGUMENT, "j2k: scalar expounded quantisation");
-            if (style != 0 || n - 1 > 97) return F.set(OMR_INTERNAL, "j2k: bad QCD");
+            if (style == 1 && !take97) return F.set(OMR_INVALID_ARGUMENT, "j2k: scalar derived quantisation");
+            if (style == 2 && !take97) return F.set(OMR_INVALID_ARGUMENT, "j2k: scalar expounded quantisation");
+            if (style > 2 || (style == 0 && n - 1 > 97)) return F.set(OMR_INTERNAL, "j2k: bad QCD");
             H.guard = (uint8_t)(p[0] >> 5);
-            std::memset(H.expo, 0xFF, sizeof H.expo);
-            for (size_t k = 0; k + 1 < n; ++k) H.expo[k] = (uint8_t)(p[1 + k] >> 3);
+            H.qstyle = style;
+            qcd = p + 1;
+            qcd_n = n - 1;
             have_qcd = true;
             break;
         }
@@ -301,6 +314,28 @@ omr_status parse_headers(const uint8_t* src, size_t len, int32_t w, int32_t h, i
         return F.set(OMR_INVALID_ARGUMENT, "j2k: several tiles or tile-parts");
     if (len - H.body_end < 2 || src[H.body_end] != 0xFF || src[H.body_end + 1] != 0xD9) return F.set(OMR_INTERNAL, "j2k: no EOC");
     if ((size_t)(3 * H.levels + 1) > 97) return F.set(OMR_INTERNAL, "j2k: bad COD");
+    // the transform and the quantisation style come in pairs: 5/3 with none, 9/7 with a scalar one
+    if (H.lossy && H.qstyle == 0) return F.set(OMR_INVALID_ARGUMENT, "j2k: the 9/7 transform without quantisation (QCD style 0)");
+    if (!H.lossy && H.qstyle != 0) return F.set(OMR_INVALID_ARGUMENT, "j2k: the 5/3 transform with scalar quantisation (QCD style 1 or 2)");
+    if (!H.lossy && !(kinds & kJ2kTakeReversible))
+        return F.set(OMR_INVALID_ARGUMENT, "j2k: the reversible 5/3 transform (only irreversible streams are taken here)");
+    std::memset(H.expo, 0xFF, sizeof H.expo);
+    if (H.qstyle == 0) {
+        for (size_t k = 0; k < qcd_n; ++k) H.expo[k] = (uint8_t)(qcd[k] >> 3);
+    } else if (H.qstyle == 1) {                            // one pair; a subband n levels up has the exponent less n (OpenJPEG stops at 0)
+        if (qcd_n != 2) return F.set(OMR_INTERNAL, "j2k: bad QCD");
+        const int e0 = qcd[0] >> 3;
+        for (int k = 0; k < 3 * H.levels + 1; ++k) {
+            H.expo[k] = (uint8_t)std::max(e0 - (k ? (k - 1) / 3 : 0), 0);
+            H.mant[k] = (uint16_t)(be16(qcd) & 0x7FFu);
+        }
+    } else {
+        if ((qcd_n & 1) || qcd_n / 2 > 97) return F.set(OMR_INTERNAL, "j2k: bad QCD");
+        for (size_t k = 0; k < qcd_n / 2; ++k) {
+            H.expo[k] = (uint8_t)(qcd[2 * k] >> 3);
+            H.mant[k] = (uint16_t)(be16(qcd + 2 * k) & 0x7FFu);
+        }
+    }
     for (int k = 0; k < 3 * H.levels + 1; ++k) {
         if (H.expo[k] == 0xFF) return F.set(OMR_INTERNAL, "j2k: QCD holds too few subbands");
         const int mb = (int)H.guard + (int)H.expo[k] - 1;
@@ -313,15 +348,35 @@ omr_status parse_headers(const uint8_t* src, size_t len, int32_t w, int32_t h, i
 }  // namespace
 
 omr_status j2k_prepare(const uint8_t* src, size_t len, int32_t w, int32_t h, int32_t samples, int32_t bits, J2kPlan& out,
-                       std::string* why) {
+                       std::string* why, uint32_t kinds) {
     Fail F{why};
     Header H;
-    omr_status st = parse_headers(src, len, w, h, samples, bits, H, F);
+    omr_status st = parse_headers(src, len, w, h, samples, bits, kinds, H, F);
     if (st) return st;
     uint64_t forms = 0;
-    if (H.mct && H.ncomp == 3) forms |= 1ull << OMR_J2K_FORM_RCT;
+    uint32_t lossy_forms = 0;
+    if (H.mct && H.ncomp == 3 && !H.lossy) forms |= 1ull << OMR_J2K_FORM_RCT;
     if (H.bits == 16) forms |= 1ull << OMR_J2K_FORM_BITS16;
     const int NL = H.levels, NC = H.ncomp;
+    if (H.lossy) {
+        lossy_forms |= 1u << OMR_J2K_LOSSY_FORM_W97;
+        lossy_forms |= 1u << (H.qstyle == 1 ? OMR_J2K_LOSSY_FORM_QCD_DERIVED : OMR_J2K_LOSSY_FORM_QCD_EXPOUNDED);
+        if (NC == 3) lossy_forms |= 1u << (H.mct ? OMR_J2K_LOSSY_FORM_ICT : OMR_J2K_LOSSY_FORM_NO_MCT_3);
+        if (H.bits == 16) lossy_forms |= 1u << OMR_J2K_LOSSY_FORM_BITS16;
+        for (int r = 1; r <= NL; ++r) {
+            const int32_t rw = j2k_ceil_shift(w, NL - r), rh = j2k_ceil_shift(h, NL - r);
+            if (rw == 1 || rh == 1) lossy_forms |= 1u << OMR_J2K_LOSSY_FORM_LINE_OF_1;
+            if (rw == 2 || rh == 2) lossy_forms |= 1u << OMR_J2K_LOSSY_FORM_LINE_OF_2;
+        }
+    }
+    // K20: half the quantiser step of subband q of the QCD.  OpenJPEG adds no subband gain for 9/7
+    // (the lifting's scaling makes up for it): delta = (1 + mantissa / 2048) * 2^(precision - exponent),
+    // exact in double and in float (12 significant bits, an exponent in [-31, 17]).
+    auto half_step = [&](int q) -> float {
+        if (!H.lossy) return 0.f;
+        const float delta = (float)std::ldexp(1.0 + (double)H.mant[q] / 2048.0, H.bits - (int)H.expo[q]);
+        return 0.5f * delta;
+    };
     // the geometry: resolutions, subbands, precincts, code-blocks
     std::vector<std::vector<Resolution>> comps((size_t)NC);
     std::vector<J2kBlock> blocks;
@@ -342,13 +397,13 @@ omr_status j2k_prepare(const uint8_t* src, size_t len, int32_t w, int32_t h, int
             const uint32_t lw = (R.w + 1) / 2, lh = (R.h + 1) / 2;
             if (r == 0) {
                 R.nb = 1;
-                R.band[0] = {0u, R.w, R.h, 0u, 0u, (int32_t)H.guard + H.expo[0] - 1};
+                R.band[0] = {0u, R.w, R.h, 0u, 0u, (int32_t)H.guard + H.expo[0] - 1, half_step(0)};
             } else {
                 R.nb = 3;
                 const int q = 3 * (r - 1) + 1;
-                R.band[0] = {1u, R.w / 2, lh, lw, 0u, (int32_t)H.guard + H.expo[q] - 1};
-                R.band[1] = {2u, lw, R.h / 2, 0u, lh, (int32_t)H.guard + H.expo[q + 1] - 1};
-                R.band[2] = {3u, R.w / 2, R.h / 2, lw, lh, (int32_t)H.guard + H.expo[q + 2] - 1};
+                R.band[0] = {1u, R.w / 2, lh, lw, 0u, (int32_t)H.guard + H.expo[q] - 1, half_step(q)};
+                R.band[1] = {2u, lw, R.h / 2, 0u, lh, (int32_t)H.guard + H.expo[q + 1] - 1, half_step(q + 1)};
+                R.band[2] = {3u, R.w / 2, R.h / 2, lw, lh, (int32_t)H.guard + H.expo[q + 2] - 1, half_step(q + 2)};
             }
             const uint32_t cpx = r ? R.ppx - 1 : R.ppx, cpy = r ? R.ppy - 1 : R.ppy;
             const uint32_t bx = std::min<uint32_t>((uint32_t)H.xcb, cpx), by = std::min<uint32_t>((uint32_t)H.ycb, cpy);
@@ -380,6 +435,7 @@ omr_status j2k_prepare(const uint8_t* src, size_t len, int32_t w, int32_t h, int
                                 K.w = (uint16_t)(ax1 - ax0);
                                 K.h = (uint16_t)(ay1 - ay0);
                                 K.orient = (uint8_t)G.orient;
+                                K.step = G.step;
                                 if (K.w != (1u << bx) || K.h != (1u << by)) forms |= 1ull << OMR_J2K_FORM_PARTIAL_BLOCK;
                                 blocks.push_back(K);
                             }
@@ -513,10 +569,14 @@ omr_status j2k_prepare(const uint8_t* src, size_t len, int32_t w, int32_t h, int
         blocks[k].n_ranges = count[k + 1] - count[k];
         blocks[k].passes = (uint16_t)state[k].passes;
         blocks[k].planes = (uint8_t)std::max(state[k].planes, 0);
+        if (H.lossy && state[k].passes && (int64_t)state[k].passes < 3 * (int64_t)state[k].planes - 2)
+            lossy_forms |= 1u << OMR_J2K_LOSSY_FORM_TRUNCATED_BLOCK;
     }
     std::vector<uint32_t> at(count.begin(), count.end() - 1);
     for (const Piece& p : pieces) out.ranges[at[p.block]++] = {p.off, p.len};
     out.w = w; out.h = h; out.ncomp = NC; out.bits = H.bits; out.levels = NL; out.mct = H.mct && NC == 3;
+    out.lossy = H.lossy;
+    out.lossy_forms = lossy_forms;
     out.blocks = std::move(blocks);
     out.forms = forms;
     return OMR_OK;
@@ -526,11 +586,56 @@ namespace {
 
 // The blocks into the coefficient area a (ncomp planes of w x h), then level by level into x and
 // y, then the pixels: what K19a, K19b and K19c do, by the same functions.
+void store_sample(uint8_t* dst, int32_t bits, size_t at, uint32_t v) {
+    if (bits == 8) dst[at] = (uint8_t)v;
+    else reinterpret_cast<uint16_t*>(dst)[at] = (uint16_t)v;
+}
+
+// K20: the float half of decode below: a holds the coefficients' bits.  Level by level, all rows
+// and then all columns (OpenJPEG's order; in float the order decides the bits), each line by
+// j2k_lift97_line, then the pixels by j2k_pixel97: what K20b and K19c compute.
+void finish97(const J2kPlan& P, const std::vector<int32_t>& a, int32_t w, int32_t h, int32_t bits, uint8_t* dst) {
+    const size_t plane = (size_t)w * h;
+    const int32_t L = P.levels, NC = P.ncomp;
+    const float* af = reinterpret_cast<const float*>(a.data());
+    std::vector<float> prev, cur;                          // NC planes of the level before and of this one, rows pw and rw apart
+    int32_t pw = 0, ph = 0;
+    for (int32_t l = 1; l <= L; ++l) {
+        const int32_t rw = j2k_ceil_shift(w, L - l), rh = j2k_ceil_shift(h, L - l), lw = (rw + 1) / 2, lh = (rh + 1) / 2;
+        cur.assign((size_t)rw * rh * NC, 0.f);
+        const bool threaded = (size_t)rw * rh >= kThreadedCoefficients;
+        for (int32_t c = 0; c < NC; ++c) {
+            const float* ap = af + plane * (size_t)c;
+            const float* lp = l == 1 ? ap : prev.data() + (size_t)pw * ph * c;
+            const int32_t lstride = l == 1 ? w : pw;
+            float* op = cur.data() + (size_t)rw * rh * c;
+            parallel_for(rh, threaded, [&](int r) {        // nested row r is interleaved row y
+                float* line = op + (size_t)(r < lh ? 2 * r : 2 * (r - lh) + 1) * rw;
+                for (int32_t j = 0; j < rw; ++j)
+                    line[j < lw ? 2 * j : 2 * (j - lw) + 1] = j < lw && r < lh ? lp[(size_t)r * lstride + j] : ap[(size_t)r * w + j];
+                j2k_lift97_line(line, rw, 1);
+            });
+            parallel_for(rw, threaded, [&](int x) { j2k_lift97_line(op + x, rh, (size_t)rw); });
+        }
+        prev.swap(cur);
+        pw = rw;
+        ph = rh;
+    }
+    for (size_t p = 0; p < plane; ++p) {
+        float v[3] = {0.f, 0.f, 0.f};
+        uint32_t o[3];
+        for (int32_t c = 0; c < NC; ++c) v[c] = L ? prev[plane * (size_t)c + p] : af[plane * (size_t)c + p];
+        j2k_pixel97(v, NC, P.mct, bits, o);
+        for (int32_t c = 0; c < NC; ++c) store_sample(dst, bits, p * (size_t)NC + c, o[c]);
+    }
+}
+
 omr_status decode(const uint8_t* src, size_t len, int32_t w, int32_t h, int32_t samples, int32_t bits, uint8_t* dst,
-                  uint64_t* forms, std::string* why) {
+                  uint64_t* forms, std::string* why, uint32_t kinds = kJ2kTakeReversible, uint32_t* lossy_forms = nullptr) {
     std::unique_ptr<J2kPlan> P(new J2kPlan);
-    const omr_status st = j2k_prepare(src, len, w, h, samples, bits, *P, why);
+    const omr_status st = j2k_prepare(src, len, w, h, samples, bits, *P, why, kinds);
     if (st) return st;
+    if (lossy_forms) *lossy_forms = P->lossy_forms;
     const size_t plane = (size_t)w * h, total = plane * (size_t)P->ncomp;
     std::vector<int32_t> a(total);
     std::atomic<uint64_t> met{P->forms};
@@ -551,12 +656,17 @@ omr_status decode(const uint8_t* src, size_t len, int32_t w, int32_t h, int32_t 
             for (uint32_t y = 0; y < K.h; ++y)
                 for (uint32_t x = 0; x < K.w; ++x)
                     a[(size_t)K.ws_off + (size_t)y * K.stride + x] =
-                        j2k_coefficient(mag[(size_t)y * K.w + x], fl[(size_t)(y + 1) * (K.w + 2) + x + 1]);
+                        P->lossy ? (int32_t)j2k_float_bits(j2k_dequantise(mag[(size_t)y * K.w + x], fl[(size_t)(y + 1) * (K.w + 2) + x + 1], K.step))
+                                 : j2k_coefficient(mag[(size_t)y * K.w + x], fl[(size_t)(y + 1) * (K.w + 2) + x + 1]);
         }
         met.fetch_or(f);
     });
     if (forms) *forms = met.load();
     if (!dst) return OMR_OK;
+    if (P->lossy) {
+        finish97(*P, a, w, h, bits, dst);
+        return OMR_OK;
+    }
     const int32_t L = P->levels, yw = (w + 1) / 2, yh = (h + 1) / 2;
     std::vector<int32_t> xb(L ? total : 0), yb(L > 1 ? (size_t)yw * yh * P->ncomp : 0);
     for (int32_t l = 1; l <= L; ++l) {
@@ -599,6 +709,13 @@ bool sizes_ok(int32_t w, int32_t h, int32_t samples, int32_t bits) {
 
 bool j2k_sizes_ok(int32_t w, int32_t h, int32_t samples, int32_t bits) { return sizes_ok(w, h, samples, bits); }
 
+omr_status j2k_decode_host_kinds(const uint8_t* src, size_t len, int32_t w, int32_t h, int32_t samples, int32_t bits, uint8_t* dst,
+                                 uint32_t kinds, std::string* why) {
+    if (!src || !dst || !sizes_ok(w, h, samples, bits)) return OMR_INVALID_ARGUMENT;
+    if (bits == 16 && (reinterpret_cast<uintptr_t>(dst) & 1u)) return OMR_INVALID_ARGUMENT;
+    return decode(src, len, w, h, samples, bits, dst, nullptr, why, kinds);
+}
+
 }  // namespace omr
 
 using namespace omr;
@@ -607,11 +724,16 @@ extern "C" {
 
 omr_status omr_j2k_decode_host(const uint8_t* src, size_t length, int32_t width, int32_t height, int32_t samples, int32_t bits,
                                uint8_t* dst, char* why, size_t why_cap) {
+    return omr_j2k_decode_host_ex(src, length, width, height, samples, bits, 0u, dst, why, why_cap);
+}
+
+omr_status omr_j2k_decode_host_ex(const uint8_t* src, size_t length, int32_t width, int32_t height, int32_t samples, int32_t bits,
+                                  uint32_t flags, uint8_t* dst, char* why, size_t why_cap) {
     if (why && why_cap) why[0] = 0;
-    if (!src || !dst || !sizes_ok(width, height, samples, bits)) return OMR_INVALID_ARGUMENT;
-    if (bits == 16 && (reinterpret_cast<uintptr_t>(dst) & 1u)) return OMR_INVALID_ARGUMENT;
+    if (flags & ~OMR_J2K_ALLOW_IRREVERSIBLE) return OMR_INVALID_ARGUMENT;
     std::string msg;
-    const omr_status st = decode(src, length, width, height, samples, bits, dst, nullptr, &msg);
+    const omr_status st = j2k_decode_host_kinds(src, length, width, height, samples, bits, dst,
+                                                kJ2kTakeReversible | (flags ? kJ2kTakeIrreversible : 0u), &msg);
     if (why && why_cap) {
         std::strncpy(why, msg.c_str(), why_cap - 1);
         why[why_cap - 1] = 0;
@@ -620,8 +742,13 @@ omr_status omr_j2k_decode_host(const uint8_t* src, size_t length, int32_t width,
 }
 
 omr_status omr_j2k_stream_forms(const uint8_t* src, size_t length, uint64_t* forms) {
-    if (!src || !forms) return OMR_INVALID_ARGUMENT;
+    return omr_j2k_stream_forms_ex(src, length, 0u, forms, nullptr);
+}
+
+omr_status omr_j2k_stream_forms_ex(const uint8_t* src, size_t length, uint32_t flags, uint64_t* forms, uint32_t* lossy_forms) {
+    if (!src || !forms || (flags & ~OMR_J2K_ALLOW_IRREVERSIBLE)) return OMR_INVALID_ARGUMENT;
     *forms = 0;
+    if (lossy_forms) *lossy_forms = 0;
     // the frame's own size, component count and precision: SIZ stands behind SOC
     if (length < 2 + 4 + 36 + 3 || src[0] != 0xFF || src[1] != 0x4F || src[2] != 0xFF || src[3] != 0x51) return OMR_INTERNAL;
     const uint8_t* p = src + 6;
@@ -629,7 +756,8 @@ omr_status omr_j2k_stream_forms(const uint8_t* src, size_t length, uint64_t* for
     const size_t nc = be16(p + 34);
     const int bits = (p[36] & 0x7F) + 1;
     if (w > 0x7FFFFFFFull || h > 0x7FFFFFFFull || !sizes_ok((int32_t)w, (int32_t)h, (int32_t)nc, bits)) return OMR_INVALID_ARGUMENT;
-    return decode(src, length, (int32_t)w, (int32_t)h, (int32_t)nc, bits, nullptr, forms, nullptr);
+    return decode(src, length, (int32_t)w, (int32_t)h, (int32_t)nc, bits, nullptr, forms, nullptr,
+                  kJ2kTakeReversible | (flags ? kJ2kTakeIrreversible : 0u), lossy_forms);
 }
 
 }  // extern "C"

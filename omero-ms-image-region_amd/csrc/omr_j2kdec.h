@@ -1,11 +1,11 @@
-// omr_j2kdec.h — K19: what the host decoder (omr_j2kdec.cpp) and the device decoder
-// (omr_j2kdec.hip) of reversible JPEG 2000 codestreams share: the descriptors the host writes for
+// omr_j2kdec.h — K19 and K20: what the host decoder (omr_j2kdec.cpp) and the device decoder
+// (omr_j2kdec.hip) of JPEG 2000 codestreams, reversible (K19) and irreversible (K20), share: the descriptors the host writes for
 // the kernels, and all arithmetic behind tier 2 -- the MQ decoder, the three coding passes of one
 // code-block, the 5/3 inverse lifting of one output sample, the inverse RCT with level shift and
 // clamp -- as one set of __host__ __device__ functions, so that the two routes cannot differ (the
 // omr_jpegdec.h pattern).
 //
-// All of it is integer arithmetic.  Sums are taken in uint32_t, that is modulo 2^32: for every
+// All of K19 is integer arithmetic.  Sums are taken in uint32_t, that is modulo 2^32: for every
 // stream an encoder writes they are OpenJPEG's numbers, and for a crafted stream they are still
 // defined and the same on both routes.  Shifts of such sums to the right are arithmetic (j2k_asr).
 //
@@ -16,6 +16,14 @@
 // passes than 3 * planes - 2) it is the mid-point of what is left open: magnitude | 1 << (p - 1)
 // for a sample whose last coded bit-plane is p >= 1.  tests/golden/tiff_j2k.npz pins this rule on
 // two truncated streams against OpenJPEG's decode.
+//
+// K20, the irreversible path (the 9/7 transform, scalar quantisation, the irreversible colour
+// transform), is float32 arithmetic with a fixed order and no contraction (the library is built
+// with -ffp-contract=off), written once below for both routes: a finished sample keeps its
+// fractional bit and becomes (float)signed value * step, step = half the subband's quantiser step
+// (j2k_dequantise); a coefficient then is that float's bits in the 4 bytes that hold the int32 of
+// the reversible path.  Every lifting step is j2k_lift97_step, every scaling a single product, the
+// pixel j2k_pixel97: each sample has one expression tree, whichever route evaluates it.
 #pragma once
 
 #include "omr_internal.h"
@@ -48,6 +56,7 @@ struct J2kBlock {
     uint16_t passes;
     uint8_t orient, planes;
     uint32_t seg;
+    float step;              // K20: half the quantiser step of the block's subband; 0 in a reversible stream
 };
 // One segment for the kernels.  The workspace holds, per component, the subbands in the nested
 // (Mallat) layout in a plane of w x h int32 (a), and two planes the lifting alternates between: x
@@ -59,7 +68,7 @@ struct J2kSegDesc {
     uint64_t a_off, x_off, y_off;   // bytes into the workspace, multiples of 256
     int32_t w, h, ncomp, bits, levels, mct;
     int32_t swap16;          // 16-bit samples are stored byte-swapped (a big-endian file)
-    int32_t pad;
+    int32_t lossy;           // K20: the coefficients are floats, the transform is 9/7 and mct means the ICT
 };
 
 __host__ __device__ inline int32_t j2k_asr(uint32_t v, int n) {
@@ -355,6 +364,23 @@ __host__ __device__ inline int32_t j2k_coefficient(uint32_t value, uint32_t flag
     return (int32_t)((flags & kJ2kNeg) ? 0u - m : m);
 }
 
+// K20: the coefficient of a decoded sample of an irreversible stream.  The fractional bit stays: a
+// truncated block's samples land on the mid-point OpenJPEG reconstructs.
+__host__ __device__ inline float j2k_dequantise(uint32_t value, uint32_t flags, float step) {
+    const int32_t v = (int32_t)((flags & kJ2kNeg) ? 0u - value : value);
+    return (float)v * step;
+}
+__host__ __device__ inline uint32_t j2k_float_bits(float f) {
+    uint32_t u;
+    memcpy(&u, &f, 4);
+    return u;
+}
+__host__ __device__ inline float j2k_bits_float(uint32_t u) {
+    float f;
+    memcpy(&f, &u, 4);
+    return f;
+}
+
 // ---- the 5/3 inverse lifting (T.800 F.3.8.1, origin 0, whole-sample symmetric extension) ----------
 
 // Output sample i of n from the low-pass samples s(0 .. ceil(n / 2)) and the high-pass samples
@@ -386,6 +412,45 @@ __host__ __device__ inline int32_t j2k_idwt53_at(int32_t rw, int32_t rh, int32_t
     return j2k_lift_at(y, rh, [&](int32_t k) { return row(k); }, [&](int32_t k) { return row(lh + k); });
 }
 
+// ---- K20: the 9/7 inverse lifting (T.800 F.3.8.2 with OpenJPEG's constants and its order) ----------
+//
+// A line of n >= 2 interleaved samples, the low-pass ones at the even places: both parities are
+// scaled, then four steps follow, each adding to every sample of one parity the sum of its two
+// neighbours times a constant; a missing neighbour is the one across the edge (whole-sample
+// symmetric extension, which every step preserves, so a route may as well extend the line first
+// and let the steps run over the extension).  A line of one sample is left as it is.
+
+constexpr int kJ2kLift97Steps = 4;
+constexpr int kJ2kLift97Halo = 4;      // samples a tile needs beyond each edge: one per step
+// step k adds to parity (k & 1): even, odd, even, odd
+__host__ __device__ inline float j2k_lift97_const(int k) {
+    return k == 0 ? -0.443506852f : k == 1 ? -0.882911075f : k == 2 ? 0.052980118f : 1.586134342f;
+}
+__host__ __device__ inline float j2k_lift97_scale(float v, int parity) { return v * (parity ? 1.625732422f : 1.230174105f); }
+__host__ __device__ inline float j2k_lift97_step(float a, float l, float r, float c) { return a + (l + r) * c; }
+// i reflected into [0, n) with period 2 * (n - 1), for any i; n >= 1
+__host__ __device__ inline int32_t j2k_reflect(int32_t i, int32_t n) {
+    if (n <= 1) return 0;
+    const int32_t p = 2 * (n - 1);
+    int32_t m = i % p;
+    if (m < 0) m += p;
+    return m < n ? m : p - m;
+}
+// The place in the nested layout of interleaved sample i of a line of n: the low-pass half in front.
+__host__ __device__ inline int32_t j2k_nested_index(int32_t i, int32_t n) { return (i & 1) ? ((n + 1) >> 1) + (i >> 1) : i >> 1; }
+// A whole line in place (the host route): v[i * stride], i < n, interleaved.
+__host__ __device__ inline void j2k_lift97_line(float* v, int32_t n, size_t stride) {
+    if (n < 2) return;
+    for (int32_t i = 0; i < n; ++i) v[i * stride] = j2k_lift97_scale(v[i * stride], i & 1);
+    for (int k = 0; k < kJ2kLift97Steps; ++k) {
+        const float c = j2k_lift97_const(k);
+        for (int32_t i = k & 1; i < n; i += 2) {
+            const int32_t l = i > 0 ? i - 1 : 1, r = i + 1 < n ? i + 1 : n - 2;
+            v[i * stride] = j2k_lift97_step(v[i * stride], v[l * stride], v[r * stride], c);
+        }
+    }
+}
+
 // ---- colour, level shift, clamp -----------------------------------------------------------------
 
 // v: the ncomp reconstructed values of one pixel -> its unsigned samples of `bits` bits.
@@ -403,6 +468,34 @@ __host__ __device__ inline void j2k_pixel(const int32_t* v, int32_t ncomp, bool 
     }
 }
 
+// K20: the same for an irreversible stream: the inverse ICT when mct, then round to nearest (ties to
+// even), level shift and clamp.  A value outside int32 (or a NaN, which no stream an encoder writes
+// gives) is clamped before it is converted.
+__host__ __device__ inline int32_t j2k_round97(float v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __float2int_rn(v);
+#else
+    return (int32_t)lrintf(v);
+#endif
+}
+__host__ __device__ inline void j2k_pixel97(const float* v, int32_t ncomp, bool mct, int32_t bits, uint32_t* out) {
+    float c[3] = {v[0], ncomp == 3 ? v[1] : 0.f, ncomp == 3 ? v[2] : 0.f};
+    if (mct && ncomp == 3) {
+        const float y = c[0], u = c[1], w = c[2];
+        c[0] = y + w * 1.402f;
+        c[1] = y - u * 0.34413f - w * 0.71414f;
+        c[2] = y + u * 1.772f;
+    }
+    const int32_t top = (1 << bits) - 1, shift = 1 << (bits - 1);
+    for (int k = 0; k < ncomp; ++k) {
+        int32_t s;
+        if (!(c[k] > -1073741824.f)) s = c[k] != c[k] ? shift : 0;
+        else if (c[k] >= 1073741824.f) s = top;
+        else s = j2k_round97(c[k]) + shift;
+        out[k] = (uint32_t)(s < 0 ? 0 : s > top ? top : s);
+    }
+}
+
 // The resolution a level writes and where: see J2kSegDesc.
 __host__ __device__ inline bool j2k_level_writes_x(int32_t levels, int32_t level) { return ((levels - level) & 1) == 0; }
 
@@ -412,6 +505,8 @@ __host__ __device__ inline bool j2k_level_writes_x(int32_t levels, int32_t level
 struct J2kPlan {
     int32_t w = 0, h = 0, ncomp = 0, bits = 0, levels = 0;
     bool mct = false;
+    bool lossy = false;      // K20: the 9/7 transform with scalar quantisation; mct then means the ICT
+    uint32_t lossy_forms = 0;   // the OMR_J2K_LOSSY_FORM_* bits the headers and tier 2 show (0 for a reversible stream)
     std::vector<J2kBlock> blocks;     // every code-block of every subband: together they cover the coefficient area
     std::vector<J2kRange> ranges;
     uint64_t forms = 0;      // the OMR_J2K_FORM_* bits tier 2 and the headers show
@@ -420,9 +515,15 @@ struct J2kPlan {
 // OMR_INVALID_ARGUMENT with *why naming it: a valid form that is out of scope; OMR_INTERNAL: damage
 // (*why says what).  On OMR_OK every range lies inside src, every block inside the coefficient area
 // of ncomp * w * h values (ws_off and stride say where), and passes <= 3 * planes - 2 and planes <=
-// kJ2kMaxPlanes hold for every block with passes.
+// kJ2kMaxPlanes hold for every block with passes.  kinds: the kJ2kTake* bits of the transforms the
+// caller takes; a stream of another is OMR_INVALID_ARGUMENT by name.  In an irreversible plan every
+// block's step is finite and positive.
+constexpr uint32_t kJ2kTakeReversible = 1u, kJ2kTakeIrreversible = 2u;
 omr_status j2k_prepare(const uint8_t* src, size_t len, int32_t w, int32_t h, int32_t samples, int32_t bits, J2kPlan& out,
-                       std::string* why);
+                       std::string* why, uint32_t kinds = kJ2kTakeReversible);
+// get_tile's decoder: omr_j2k_decode_host_ex with the kinds spelled out.
+omr_status j2k_decode_host_kinds(const uint8_t* src, size_t len, int32_t w, int32_t h, int32_t samples, int32_t bits, uint8_t* dst,
+                                 uint32_t kinds, std::string* why);
 
 bool j2k_sizes_ok(int32_t w, int32_t h, int32_t samples, int32_t bits);   // what the entry points accept
 

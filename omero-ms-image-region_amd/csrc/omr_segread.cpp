@@ -206,7 +206,7 @@ omr_status finish_image(Ctx* ctx, SegPipe* T, const SegSource& S, SegPlan& plan,
         ctx, T, S, plan, segs, t, in_bytes, "JPEG 2000", (size_t)1 << 18,
         [&](const SegKey&, const SegBytes& u, const uint8_t* bytes, J2kPlan& P, std::string* why) {
             const int32_t rows = (int32_t)(u.expected / ((uint32_t)g.seg_w * (uint32_t)g.spp * (uint32_t)g.bpp));
-            return j2k_prepare(bytes, (size_t)u.cnt, g.seg_w, rows, g.spp, 8 * g.bpp, P, why);
+            return j2k_prepare(bytes, (size_t)u.cnt, g.seg_w, rows, g.spp, 8 * g.bpp, P, why, S.j2k_kinds);
         },
         [&](const std::vector<CodecJob>& jobs, const std::vector<J2kPlan>& plans, std::vector<int32_t>& status) {
             return j2k_decode_group(ctx, T, jobs, plans, S.swap, din, dscr, status);

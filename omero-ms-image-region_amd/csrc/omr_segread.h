@@ -223,6 +223,7 @@ struct SegSource {
     // three components are YCbCr (Photometric 6).
     virtual const uint8_t* jpeg_tables(const SegKey&, size_t* len) const { *len = 0; return nullptr; }
     bool jpeg_ycc = false;
+    uint32_t j2k_kinds = 1u;     // SegCodec::j2k: the kJ2kTake* transforms the open allowed (omr_j2kdec.h)
 };
 
 // ---- K17, K19: one group of image-codec segments (omr_jpegdec.hip, omr_j2kdec.hip) ---------------

@@ -11,8 +11,9 @@
 // omr_zstd_decode_host, on the device by K14a and K16a), the floating-point predictor and chunky
 // pixels of 2..4 samples, of which a read takes one, and baseline JPEG segments (Compression 7 with
 // the JPEGTables of tag 347; omr_jpeg_decode_host here, K17a .. K17c on the device: omr_jpegdec.*)
-// and reversible JPEG 2000 codestreams (Compression 33003, 33004, 33005, 34712; omr_j2k_decode_host
-// here, K19a .. K19c on the device: omr_j2kdec.*).
+// and JPEG 2000 codestreams (Compression 33003, 33004, 33005, 34712; the host decoder of
+// omr_j2kdec.cpp here, K19a .. K19c and K20b on the device: omr_j2kdec.*), reversible ones with
+// OMR_TIFF_ACCEPT_JPEG2000 and irreversible ones with OMR_TIFF_ACCEPT_JPEG2000_LOSSY.
 // The device route itself -- staging, planning,
 // K13a's and K13b's launches (omr_tiffread.hip), the tile renderer -- is omr_segread.cpp, shared
 // with the Zarr reader; this file calls no HIP function.
@@ -62,6 +63,7 @@ struct omr_tiff_image {
     int32_t pt = 0, bpp = 0, compression = 1, predictor = 1;
     int32_t spp = 1;                                    // samples per pixel (chunky): channel c is sample c % spp
     bool jpeg_ycc = false;                              // Compression 7 with Photometric 6: YCbCr -> RGB on decode
+    uint32_t j2k_kinds = 0;                             // JPEG 2000: the omr::kJ2kTake* transforms the open's accept bits allow
     std::vector<Level> levels;
     std::vector<std::vector<Segments>> segs;   // [plane][level]
     ~omr_tiff_image() {
@@ -247,8 +249,8 @@ omr_status take_ifd(const Parser& P, const Ifd& f, uint32_t accept, Level& L, Se
         ycc = f.photometric == 6;
         comp = 7;
         break;
-    case 33003: case 33004: case 33005: case 34712:      // one reversible JPEG 2000 codestream per segment (K19)
-        if (!(accept & OMR_TIFF_ACCEPT_JPEG2000)) return OMR_INVALID_ARGUMENT;
+    case 33003: case 33004: case 33005: case 34712:      // one JPEG 2000 codestream per segment (K19; K20: irreversible ones)
+        if (!(accept & (OMR_TIFF_ACCEPT_JPEG2000 | OMR_TIFF_ACCEPT_JPEG2000_LOSSY))) return OMR_INVALID_ARGUMENT;
         if (f.fmt != 1 || f.pred != 1 || f.mixed) return OMR_INVALID_ARGUMENT;
         if (f.bps == 8 ? (f.spp == 1 ? f.photometric > 1 : f.spp != 3 || f.photometric != 2) : f.bps != 16 || f.spp != 1 || f.photometric > 1)
             return OMR_INVALID_ARGUMENT;
@@ -482,7 +484,8 @@ omr_status load_segment(const omr_tiff_image* im, const Level& L, const Segments
             break;
         }
         case 34712: {
-            const omr_status st = omr_j2k_decode_host(comp.data(), (size_t)cnt, L.seg_w, rows, im->spp, 8 * im->bpp, out.data(), nullptr, 0);
+            const omr_status st = omr::j2k_decode_host_kinds(comp.data(), (size_t)cnt, L.seg_w, rows, im->spp, 8 * im->bpp, out.data(),
+                                                             im->j2k_kinds, nullptr);
             if (st == OMR_INVALID_ARGUMENT) return st;      // a valid form out of scope
             ok = st == OMR_OK;
             if (ok && im->bpp == 2 && im->big == host_little_endian())   // the decoder's samples are the host's: into the file's order
@@ -529,6 +532,7 @@ struct TiffSource final : omr::SegSource {
         swap = im->big == host_little_endian();
         pt = im->pt; big = im->big;
         jpeg_ycc = im->jpeg_ycc;
+        j2k_kinds = im->j2k_kinds;
     }
     omr::SegImageDims dims() const {
         return {(int32_t)level, (int32_t)im->levels.size(), im->bpp, im->sc,
@@ -585,7 +589,7 @@ omr_status omr_tiff_image_open_ex(const char* path, int32_t size_z, int32_t size
         if (opt->struct_size < sizeof(omr_tiff_open_options)) return OMR_INVALID_ARGUMENT;
         accept = opt->accept;
         if (accept & ~(OMR_TIFF_ACCEPT_DEFLATE | OMR_TIFF_ACCEPT_ZSTD | OMR_TIFF_ACCEPT_PREDICTOR3 | OMR_TIFF_ACCEPT_SAMPLES |
-                       OMR_TIFF_ACCEPT_JPEG | OMR_TIFF_ACCEPT_JPEG2000))
+                       OMR_TIFF_ACCEPT_JPEG | OMR_TIFF_ACCEPT_JPEG2000 | OMR_TIFF_ACCEPT_JPEG2000_LOSSY))
             return OMR_INVALID_ARGUMENT;
     }
     if (!path || !dimension_order || size_z <= 0 || size_c <= 0 || size_t_ <= 0) return OMR_INVALID_ARGUMENT;
@@ -595,6 +599,8 @@ omr_status omr_tiff_image_open_ex(const char* path, int32_t size_z, int32_t size
         return OMR_INVALID_ARGUMENT;
     std::unique_ptr<omr_tiff_image> im(new omr_tiff_image);
     im->sz = size_z; im->sc = size_c; im->st = size_t_;
+    im->j2k_kinds = ((accept & OMR_TIFF_ACCEPT_JPEG2000) ? omr::kJ2kTakeReversible : 0u) |
+                    ((accept & OMR_TIFF_ACCEPT_JPEG2000_LOSSY) ? omr::kJ2kTakeIrreversible : 0u);
     if (!set_strides(im.get(), dimension_order, size_c)) return OMR_INVALID_ARGUMENT;   // again below, once spp is known
     im->fd = ::open(path, O_RDONLY | O_CLOEXEC);
     if (im->fd < 0) return errno == ENOENT ? OMR_NOT_FOUND : OMR_INVALID_ARGUMENT;

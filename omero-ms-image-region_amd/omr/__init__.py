@@ -6,13 +6,15 @@ Layers:
   renderer  Renderer facade mirroring the omeis Renderer calls the reference makes
             (ImageRegionRequestHandler.java:436-440, :689-741, :559)
   pixbuf    PixelBuffer: ROMIO repository pixel files (getPixelBuffer, :302-309)
-  tiffimage TiffImage: tiled TIFF / OME-TIFF pixel files, LZW, Deflate, zstd, JPEG and reversible JPEG 2000 decoded on the GPU; write_tiled_tiff
+  tiffimage TiffImage: tiled TIFF / OME-TIFF pixel files, LZW, Deflate, zstd, JPEG and JPEG 2000 decoded on the GPU; write_tiled_tiff
+  j2k       JPEG 2000 codestreams alone, irreversible (9/7) ones included: decode_host, decode_batch_device, stream_forms
   zarrimage ZarrImage: OME-Zarr pyramids, zlib, Blosc (LZ4 or Zstd inside) and zstd chunks decoded on the GPU; write_zarr
   batcher   Batcher: concurrent requests coalesced into GPU batches; Pool: one batcher per GPU
   request   ImageRegionCtx / ShapeMaskCtx parsing and the handler glue
             (ImageRegionCtx.java, ImageRegionRequestHandler.java, ShapeMaskRequestHandler.java)
 """
 from . import _lib
+from . import j2k
 from ._lib import OmrError
 from .context import Context, pyramid_level_count, pyramid_level_sizes, thumbnail_size
 from .pixbuf import PixelBuffer, write_pyramid, write_romio

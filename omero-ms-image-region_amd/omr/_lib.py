@@ -108,7 +108,8 @@ class TiffInfo(ctypes.Structure):
         "predictor", "tiled", "segment_width", "segment_height", "big_tiff")]
 
 
-TIFF_ACCEPT = {"deflate": 1, "zstd": 2, "predictor3": 4, "samples": 8, "jpeg": 16, "jpeg2000": 32}    # OMR_TIFF_ACCEPT_*
+TIFF_ACCEPT = {"deflate": 1, "zstd": 2, "predictor3": 4, "samples": 8, "jpeg": 16, "jpeg2000": 32,
+               "jpeg2000-lossy": 64}                        # OMR_TIFF_ACCEPT_*
 # OMR_JPEG_FORM_*: omr.jpeg_stream_forms returns the set of names, form f is bit f
 JPEG_FORM_NAMES = ("EOB_EARLY", "FULL_BLOCK", "ZRL", "LONG_CODE", "DC_CAT9", "STUFFED_FF", "RESTART", "PAD_BITS",
                    "TABLE_OVERRIDE", "MULTI_TABLE", "COM", "FILL_BYTES", "TABLES_STREAM")
@@ -120,6 +121,10 @@ J2K_FORM_NAMES = (tuple("ZC%d" % k for k in range(9)) + ("SC9",) +
                   ("RUN_TAKEN", "RUN_BROKEN", "MPS_EXCHANGE", "LPS_EXCHANGE", "FF_BODY", "FF_HEADER", "PASSES_1", "PASSES_2",
                    "PASSES_3_5", "PASSES_6_36", "PASSES_37_164", "LBLOCK", "TAG_TREE_DEEP", "LATE_INCLUSION",
                    "ZERO_BIT_PLANES", "PARTIAL_BLOCK", "RCT", "BITS16"))
+# OMR_J2K_LOSSY_FORM_*: what omr.j2k.stream_forms reports of an irreversible stream beside the names above
+J2K_LOSSY_FORM_NAMES = ("W97", "QCD_EXPOUNDED", "QCD_DERIVED", "ICT", "NO_MCT_3", "TRUNCATED_BLOCK", "LINE_OF_1", "LINE_OF_2",
+                        "BITS16")
+J2K_ALLOW_IRREVERSIBLE = 1                                  # OMR_J2K_ALLOW_IRREVERSIBLE
 J2K_COMPRESSIONS = (33003, 33004, 33005, 34712)             # the TIFF Compression numbers of a JPEG 2000 segment
 
 
@@ -364,6 +369,9 @@ _SIGS = {
     "omr_j2k_decode_host": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _vp, _vp, _sz]),
     "omr_j2k_stream_forms": (_i32, [_vp, _sz, ctypes.POINTER(ctypes.c_uint64)]),
     "omr_j2k_decode_batch_device": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "omr_j2k_decode_host_ex": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, ctypes.c_uint32, _vp, _vp, _sz]),
+    "omr_j2k_stream_forms_ex": (_i32, [_vp, _sz, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)]),
+    "omr_j2k_decode_batch_device_ex": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, ctypes.c_uint32, _vp, _vp, _vp]),
     "omr_render_shape_mask_png_batch": (_i32, [_vp, ctypes.POINTER(MaskJob), _i32, _vp, _sz, _vp, _vp, _vp]),
     "omr_split_html_color": (_i32, [ctypes.c_char_p, ctypes.POINTER(_i32)]),
     "omr_shape_mask_fill_color": (_i32, [_i32, _i32, ctypes.c_char_p, _vp]),

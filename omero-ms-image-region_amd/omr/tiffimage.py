@@ -8,7 +8,8 @@ and render_tiles with the LZW segments decoded on the GPU (omr_tiffread.hip).  W
 (omr_tiff_image_open_ex) also Deflate and zstd segments, the floating-point predictor and chunky
 pixels of several samples (RGB), each channel one sample, and with "jpeg" baseline JPEG segments
 (Compression 7, K17: omr_jpegdec.hip), grey, RGB or YCbCr converted to RGB, and with "jpeg2000"
-reversible JPEG 2000 codestreams (Compression 33003, 33004, 33005, 34712, K19: omr_j2kdec.hip).
+reversible JPEG 2000 codestreams (Compression 33003, 33004, 33005, 34712, K19: omr_j2kdec.hip), with
+"jpeg2000-lossy" irreversible ones (K20).
 """
 import ctypes
 import struct
@@ -140,14 +141,15 @@ def _jpeg_encode(seg, opt):
 
 
 def _j2k_encode(seg, opt):
-    """One segment ([rows][cols] uint8 or uint16, or [rows][cols][3] uint8) as a raw reversible JPEG 2000
+    """One segment ([rows][cols] uint8 or uint16, or [rows][cols][3] uint8) as a raw JPEG 2000
     codestream, by Pillow's OpenJPEG; opt: Pillow's save options (num_resolutions, codeblock_size,
-    precinct_size, quality_mode, quality_layers, progression, mct ...)."""
+    precinct_size, quality_mode, quality_layers, progression, mct ...); reversible unless opt says
+    "irreversible": True (the 9/7 transform, K20)."""
     import io
     from PIL import Image
     kw = dict(opt)
     kw.pop("rewrite", None)
-    kw.update(format="JPEG2000", no_jp2=True, irreversible=False)
+    kw.update(format="JPEG2000", no_jp2=True, irreversible=bool(opt.get("irreversible", False)))
     f = io.BytesIO()
     Image.fromarray(np.ascontiguousarray(seg)).save(f, **kw)
     return f.getvalue()
@@ -195,7 +197,8 @@ def write_tiled_tiff(path, planes, levels=(), tile=(256, 256), rows_per_strip=No
     tooling aid as well), edge tiles padded by edge replication and a last strip coded at its own
     height; jpeg2000 = Pillow's save options ({"num_resolutions": 3, "codeblock_size": (16, 16),
     "precinct_size": (32, 32), "quality_mode": "rates", "quality_layers": [8, 1], "progression":
-    "RPCL", "mct": 1 ...}) and "rewrite": a function stream -> stream.
+    "RPCL", "mct": 1 ...}), "irreversible": True for the 9/7 transform (the default is the reversible
+    5/3 one) and "rewrite": a function stream -> stream.
     Returns {"ifds": [offset per plane], "subifds": [[offsets] per plane]}."""
     planes = np.asarray(planes)
     assert planes.ndim == 5, "planes must be [t][c][z][y][x]"
@@ -391,7 +394,7 @@ class TiffImage(_SegImage):
 
     def __init__(self, path, size_z=1, size_c=1, size_t=1, dimension_order="XYZCT", accept=()):
         """accept: the further forms a file may use, any of "deflate", "zstd", "predictor3" and
-        "samples", "jpeg" and "jpeg2000" (omr_tiff_image_open_ex); empty: the plain open, which refuses them all.  size_c
+        "samples", "jpeg", "jpeg2000" and "jpeg2000-lossy" (omr_tiff_image_open_ex); empty: the plain open, which refuses them all.  size_c
         counts every sample of a chunky image as a channel (3 for an RGB image)."""
         h = ctypes.c_void_p()
         accept = (accept,) if isinstance(accept, str) else tuple(accept)

@@ -15,7 +15,16 @@ medians of the passes after a warm-up with min..max beside them.  CPU figures fo
 omr_j2k_decode_host on 16 threads (one tile per thread at a time) and Pillow's OpenJPEG on one
 thread.  One region of each file is also compared with get_tile.  Needs Pillow.
 
+--lossy (K20) serves one file in their place:
+
+  rgb8_j2k97_256   the same 8-bit RGB, irreversible: the 9/7 transform and the ICT, rate-cut to about
+                   10 : 1 (Pillow's quality_mode "rates", one layer of 10)
+
+with kind 44 (K20b inverse 9/7) in place of 42, the host decoder through omr_j2k_decode_host_ex,
+and the largest error against the source picture in place of equality with it.
+
     python3 tools/tiff_j2k_probe.py --json profiles/k19/tiff_j2k_probe.json
+    python3 tools/tiff_j2k_probe.py --lossy --json profiles/k20/tiff_j2k_probe_lossy.json
 """
 import argparse
 import io
@@ -40,7 +49,7 @@ TILE = 256
 
 
 def host_decoder(path, samples, bits):
-    """omr_j2k_decode_host over every tile of the file, 16 tiles at a time: seconds."""
+    """omr_j2k_decode_host_ex over every tile of the file, 16 tiles at a time: seconds."""
     from omr import _lib
     segs = segment_table(path, 1)
     with open(path, "rb") as f:
@@ -49,7 +58,8 @@ def host_decoder(path, samples, bits):
 
     def work(k):
         for off, cnt in segs[k::16]:
-            st = _lib.lib.omr_j2k_decode_host(blob.ctypes.data + off, cnt, TILE, TILE, samples, bits, outs[k].ctypes.data, None, 0)
+            st = _lib.lib.omr_j2k_decode_host_ex(blob.ctypes.data + off, cnt, TILE, TILE, samples, bits, _lib.J2K_ALLOW_IRREVERSIBLE,
+                                                 outs[k].ctypes.data, None, 0)
             assert st == 0
     t0 = time.perf_counter()
     with ThreadPoolExecutor(16) as ex:
@@ -75,6 +85,7 @@ def main():
     ap.add_argument("--passes", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--cpu-only", action="store_true")
+    ap.add_argument("--lossy", action="store_true", help="K20: one irreversible RGB file at about 10 : 1")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
 
@@ -87,6 +98,8 @@ def main():
     tmp = tempfile.mkdtemp(prefix="tiff_j2k_probe_")
     opt = dict(codeblock_size=(64, 64))
     files = {"rgb8_j2k_256": (rgb, 3, 8, dict(opt, mct=1)), "grey16_j2k_256": (grey, 1, 16, opt)}
+    if args.lossy:
+        files = {"rgb8_j2k97_256": (rgb, 3, 8, dict(opt, mct=1, irreversible=True, quality_mode="rates", quality_layers=[10]))}
     paths = {}
     with multiprocessing.Pool(15) as pool:                       # before the GPU is opened
         for key, (a, n, bits, o) in files.items():
@@ -125,7 +138,7 @@ def main():
                     chans = c2_channels(1)
                 binds = make_bindings(chans)
                 region_bytes = len(positions) * n * SIDE * SIDE * (bits // 8)
-                src = omr.TiffImage(paths[key], 1, n, 1, accept=("jpeg2000", "samples"))
+                src = omr.TiffImage(paths[key], 1, n, 1, accept=("jpeg2000", "jpeg2000-lossy", "samples"))
                 walls, kinds = [], {}
                 ctx.enable_kernel_timing(True)
                 for p in range(args.warmup + args.passes):
@@ -146,17 +159,21 @@ def main():
                 run = {"requests": len(positions), "region_bytes": region_bytes, "wall_s": series(walls),
                        "region_gb_per_s_wall": region_bytes / statistics.median(walls) / 1e9}
                 run["launches_per_pass"] = launches              # of the last pass, by timing kind
-                for name, kind in (("k19a_t1", 41), ("k19b_idwt53", 42), ("k19c_pixels", 43), ("k13b_place", 31), ("k2_render", 2)):
+                for name, kind in (("k19a_t1", 41), ("k19b_idwt53", 42), ("k20b_idwt97", 44), ("k19c_pixels", 43), ("k13b_place", 31), ("k2_render", 2)):
                     if kind in kinds:
                         run[name + "_ms_per_pass"] = series(kinds[kind])
                         run[name + "_region_gb_per_s"] = region_bytes / (statistics.median(kinds[kind]) / 1e3) / 1e9
-                k19 = [x + y + z for x, y, z in zip(kinds[41], kinds[42], kinds[43])]
+                k19 = [x + y + z for x, y, z in zip(kinds[41], kinds[44 if args.lossy else 42], kinds[43])]
                 run["k19_abc_ms_per_pass"] = series(k19)
                 run["k19_abc_region_gb_per_s"] = region_bytes / (statistics.median(k19) / 1e3) / 1e9
                 dev = src.read_regions(ctx, 0, [(0, n - 1, 0, 300, 500)], 700, 300).cpu().numpy()[0, :700 * 300 * (bits // 8)]
                 run["read_regions_equals_get_tile"] = bool(dev.tobytes() == src.get_tile(0, 0, n - 1, 0, 300, 500, 700, 300).tobytes())
                 want = a[0, n - 1, 0, 500:800, 300:1000]
-                run["get_tile_equals_source"] = bool(np.array_equal(src.get_tile(0, 0, n - 1, 0, 300, 500, 700, 300), want))
+                got = src.get_tile(0, 0, n - 1, 0, 300, 500, 700, 300)
+                if args.lossy:
+                    run["get_tile_max_error_against_source"] = int(np.abs(got.astype(np.int64) - want.astype(np.int64)).max())
+                else:
+                    run["get_tile_equals_source"] = bool(np.array_equal(got, want))
                 result["runs"][key] = run
                 src.close()
                 print(key, json.dumps(run), flush=True)
